@@ -14,9 +14,16 @@ data-path collective.  ``--scaling strong`` (default, the north-star metric): ``
 over RCCL, i.e. env-steps/s of a PPO iteration's env + communication legs (the policy network itself is PyTorch's and is
 not part of this benchmark).
 
-The JSON carries ``roofline`` (dominant kernel; hipEvent-measured duration on the launch stream) and, at N=1,
-``cpu_baseline`` (the CPU oracle — a scalar C port of the reference step, pinned against the reference's golden vectors —
-timed on this host's cores on a bounded sample).
+A plain run sets up, warms up, times ``--steps`` steps and prints the headline (``value``, ``ms_per_step``, the
+configuration, the dynamics health counter).  ``--full`` adds what takes measurements of its own: ``roofline``
+(dominant kernel; hipEvent-measured duration on the launch stream, plus ``--kernel-sample-steps`` untimed steps) and,
+at N=1, ``cpu_baseline`` (the CPU oracle — a scalar C port of the reference step, pinned against the reference's golden
+vectors — timed on this host's cores on a bounded sample).
+
+``--dump-outputs DIR`` writes what the last timed step handed its caller (observation, reward, done and the ``info``
+tensors, after the reset of the finished envs) as ``DIR/<name>.npy``: float32 as computed, integer buffers as float64,
+rows sampled with a fixed seed above ``DUMP_ROWS`` envs.  Inputs are seeded, so two builds compare output for output.
+With N > 1 rank 0 writes its own shard.
 """
 import argparse
 import json
@@ -38,6 +45,7 @@ HBM_PEAK_GBS = 8000.0    # MI355X_MICROARCH.md: 8 TB/s spec
 VALU_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: fp32 vector peak = 1024 SIMDs x 64 lanes x 2 flop / 2 cycles x 2.4 GHz
 GRAD_BUCKET_FLOATS = 10638877  # parameters of the default actor/critic (dm_agent_default.yaml), one flat fp32 bucket = 42.56 MB
 PPO_STEPS_PER_ITER, PPO_ALLREDUCES_PER_ITER = 32, 40  # dm_agent_default.yaml: steps_per_iter, update_epochs x minibatches
+DUMP_ROWS = 8192  # --dump-outputs: envs kept per array (the 1 312-float observation rows: 43 MB, under the 64 MB cap)
 
 
 def parse(argv=None):
@@ -58,9 +66,16 @@ def parse(argv=None):
     ap.add_argument("--dynamics", type=int, default=1, help="1: full step (rigid-body dynamics + contact), 0: kinematic step only")
     ap.add_argument("--ppo", type=int, default=0, help="1: add the 40 x 42.56 MB gradient all-reduces of a PPO iteration to every 32 steps (cfg 4)")
     ap.add_argument("--kernel-sample-steps", type=int, default=200,
-                    help="UNTIMED steps after the timed region whose per-step hipEvent kernel durations give roofline.kernel_sample (median / p95): "
-                         "a thicker sample than a short --steps; `value` and ms_per_step never include them")
-    return ap.parse_args(argv)
+                    help="with --full: UNTIMED steps after the timed region whose per-step hipEvent kernel durations give roofline.kernel_sample "
+                         "(median / p95): a thicker sample than a short --steps; `value` and ms_per_step never include them")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline (kernel timings, --kernel-sample-steps) and, at one rank, the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float32 / float64)")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -314,7 +329,6 @@ def _profile_json(suffix, build=None):
 
 
 def worker(a):
-    import ctypes as C
     import torch
     from parc_amd import lib as L
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -361,10 +375,13 @@ def worker(a):
                 (f"{ncl} bundled clips" if ncl > 1 else f"clip {env._scene.clips[0].name}")) + \
                {"square": " on a square blocky grid", "wide": " on a wide blocky grid", "file": " on its own terrain"}.get(mode, "")
     D = env._char_dof_pos.shape[1]
-    # untrained-policy actions (SURVEY §8(d) cfg 3): action-normalizer mean + N(0, 0.05^2) * std
+    # untrained-policy actions (SURVEY §8(d) cfg 3): action-normalizer mean + N(0, 0.05^2) * std.  A generator of their own with a
+    # fixed seed: torch's default one may be seeded per process, and --dump-outputs needs the same inputs on every run
     lo, hi = env._action_bound_low, env._action_bound_high
     mean, std = 0.5 * (hi + lo), 0.5 * (hi - lo)
-    actions = [mean + 0.05 * std * torch.randn(n_local, D, device=dev) for _ in range(4)]
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1234 + rank)
+    actions = [mean + 0.05 * std * torch.randn(n_local, D, device=dev, generator=gen) for _ in range(4)]
     env.reset()
     grad = None
     if a.ppo:
@@ -374,9 +391,9 @@ def worker(a):
 
     def one_step(i):
         if a.graph:
-            env.step_and_reset_done(actions[i & 3] if dynamics_on else None)
+            res = env.step_and_reset_done(actions[i & 3] if dynamics_on else None)
         else:
-            env.step(actions[i & 3])
+            res = env.step(actions[i & 3])
             env.reset_done()
         if grad is not None and (i + 1) % PPO_STEPS_PER_ITER == 0:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if grad.is_cuda else None
@@ -388,6 +405,7 @@ def worker(a):
             if ev:
                 ev[1].record()
                 coll_events.append(ev)
+        return res
 
     for i in range(a.warmup):
         one_step(i)
@@ -396,10 +414,11 @@ def worker(a):
         dist.barrier()
     torch.cuda.synchronize()
     coll_events.clear()
-    L.check(env._lib.parc_env_set_kernel_timing(env._handle, 1))  # hipEvents around the kernels of the timed steps, no sync
+    if a.full:
+        L.check(env._lib.parc_env_set_kernel_timing(env._handle, 1))  # hipEvents around the kernels of the timed steps, no sync
     t0 = time.perf_counter()
     for i in range(a.steps):
-        one_step(i)
+        res = one_step(i)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -409,10 +428,92 @@ def worker(a):
         t = torch.tensor([dt], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    outputs = collect_outputs(*res) if a.dump_outputs and rank == 0 else None   # before --full steps the env further
+
+    build = (L.csrc_hash(), env._lib.parc_build_flags().decode())
+    roof = roofline(env, a, actions, dt, n_local, n_total, world, dynamics_on, build) if a.full else None
+    out = {
+        "metric": "env-steps/s", "value": n_total * a.steps / dt, "unit": "env-steps/s", "n_gpus": world,
+        "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * dt / a.steps, "higher_is_better": True,
+        "scaling": a.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": ("full step (dynamics + obs/reward/done)" if dynamics_on else "kinematic step (ref slerp + FK + 441-ray hf + obs + reward + done), no physics")
+                               + f", {n_total} envs total = {n_local} per GPU, " + lib_desc + ", reset of finished envs included"
+                               + (f", + {PPO_ALLREDUCES_PER_ITER} x {GRAD_BUCKET_FLOATS * 4 / 1e6:.2f} MB gradient all-reduces per {PPO_STEPS_PER_ITER} steps ({backend})" if a.ppo else ""),
+                   "envs_per_gpu": n_local, "total_envs": n_total, "dynamics": dynamics_on, "parallelism": f"env-shard x{world}",
+                   "launch": "hipGraph (step + reset_done)" if a.graph else "stream launches",
+                   # what the library handle resolved to: dynamics kernel, envs per block, collision set, contact parameters, manifold
+                   # period and margins, curriculum path, and every developer switch it was created with (none in the product)
+                   "library": env.describe(), "library_abi": int(env._lib.parc_abi_version()), "library_build_flags": build[1], "library_csrc_sha16": build[0]},
+    }
+    if roof is not None:
+        out["roofline"] = roof
+    timeouts = int(env._lib.parc_env_dynamics_timeouts(env._handle)) if dynamics_on else 0
+    out["dynamics_timeouts"] = timeouts   # LDS-flag hand-offs of k_dynamics_wave that hit their bound: must be 0
+    if a.full:
+        out["dynamics_manifold_drops"] = env.dynamics_manifold_drops() if dynamics_on else 0   # contact planes that found no slot: expected 0
+    if a.ppo:
+        ms = [e0.elapsed_time(e1) for e0, e1 in coll_events]
+        out["collective"] = {"backend": backend, "world": world, "allreduce_bytes": GRAD_BUCKET_FLOATS * 4, "allreduces_per_iter": PPO_ALLREDUCES_PER_ITER,
+                             "iters_timed": len(ms), "ms_per_iter_leg": (sum(ms) / len(ms)) if ms else None,
+                             "note": "40 all-reduces + the 1/world scale of the flat fp32 gradient bucket, torch.cuda events on the launch stream"
+                                     + ("; one rank: RCCL's single-rank path (a device copy), exercised so the library is loaded and timed" if world == 1 else "")}
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(env, a.cpu_seconds, dynamics_on, actions)
+    if outputs is not None:
+        write_outputs(outputs, a.dump_outputs)
+    if rank == 0:
+        sys.stdout = sys.__stdout__
+        print(json.dumps(out))
+    if dist is not None:
+        dist.destroy_process_group()
+    if timeouts:
+        sys.stderr.write(f"bench.py: rank {rank}: {timeouts} dynamics hand-off timeout(s): the measurement is void\n")
+        sys.exit(5)
+
+
+def collect_outputs(obs, reward, done, info, rows=DUMP_ROWS, seed=0):
+    """Host copies of what one step (+ reset of the finished envs) returns to its caller, keyed by file name: every array
+    has the envs on axis 0; above ``rows`` envs the same seeded, sorted sample of envs is kept in all of them."""
+    import numpy as np
+    import torch
+    arrays = {"obs": obs, "reward": reward, "done": done}
+    for k, v in info.items():
+        if isinstance(v, dict):
+            arrays.update({f"info_{k}_{kk}": vv for kk, vv in v.items()})
+        elif torch.is_tensor(v):
+            arrays[f"info_{k}"] = v
+    n = obs.shape[0]
+    idx = None
+    if n > rows:
+        idx = torch.as_tensor(np.sort(np.random.default_rng(seed).choice(n, rows, replace=False)), device=obs.device)
+    out = {}
+    for name, t in arrays.items():
+        assert t.shape[0] == n, (name, tuple(t.shape))
+        t = t if idx is None else t.index_select(0, idx)
+        t = t.detach().cpu().numpy()
+        out[name] = t if t.dtype in (np.float32, np.float64) else t.astype(np.float64)
+    return out
+
+
+def write_outputs(arrays, out_dir, cap_bytes=64 << 20):
+    import numpy as np
+    total = sum(x.nbytes for x in arrays.values())
+    if total > cap_bytes:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {cap_bytes}-byte cap")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+
+
+def roofline(env, a, actions, dt, n_local, n_total, world, dynamics_on, build):
+    """--full: kernel durations of the timed steps (+ ``--kernel-sample-steps`` untimed ones) against the roofline of the dominant
+    kernel, with the counter figures of profiles/ when they were collected on this build."""
+    import ctypes as C
+    import numpy as np
+    import torch
+    from parc_amd import lib as L
 
     # kernel durations over the timed region: hipEvents recorded on the launch stream by every parc_env_step
-    import numpy as np
-
     def read_samples():
         cap = 65536
         bufs = [np.zeros(cap, np.float32) for _ in range(3)]
@@ -451,7 +552,6 @@ def worker(a):
     # Counter-derived figures come from the committed rocprofv3 --pmc passes (profiles/, collected on the 65 536-env
     # default configuration in separate runs), NOT from this run; they are attached only to that configuration.
     at_profiled_cfg = n_local == 65536 and a.motions == 0
-    build = (L.csrc_hash(), env._lib.parc_build_flags().decode())
     post_traffic = None
     pmc = _profile_json("pmc_hbm_traffic.json", build)
     if pmc and at_profiled_cfg:
@@ -507,39 +607,7 @@ def worker(a):
     if extra_samples is not None:
         roof["kernel_sample"] = {"steps": a.kernel_sample_steps, "note": "untimed steps after the timed region, hipEvents on the launch stream, per step",
                                  **{nm: stats(x) for nm, x in zip(names, extra_samples)}}
-    out = {
-        "metric": "env-steps/s", "value": n_total * a.steps / dt, "unit": "env-steps/s", "n_gpus": world,
-        "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * dt / a.steps, "higher_is_better": True,
-        "scaling": a.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": ("full step (dynamics + obs/reward/done)" if dynamics_on else "kinematic step (ref slerp + FK + 441-ray hf + obs + reward + done), no physics")
-                               + f", {n_total} envs total = {n_local} per GPU, " + lib_desc + ", reset of finished envs included"
-                               + (f", + {PPO_ALLREDUCES_PER_ITER} x {GRAD_BUCKET_FLOATS * 4 / 1e6:.2f} MB gradient all-reduces per {PPO_STEPS_PER_ITER} steps ({backend})" if a.ppo else ""),
-                   "envs_per_gpu": n_local, "total_envs": n_total, "dynamics": dynamics_on, "parallelism": f"env-shard x{world}",
-                   "launch": "hipGraph (step + reset_done)" if a.graph else "stream launches",
-                   # what the library handle resolved to: dynamics kernel, envs per block, collision set, contact parameters, manifold
-                   # period and margins, curriculum path, and every developer switch it was created with (none in the product)
-                   "library": env.describe(), "library_abi": int(env._lib.parc_abi_version()), "library_build_flags": build[1], "library_csrc_sha16": build[0]},
-        "roofline": roof,
-    }
-    timeouts = int(env._lib.parc_env_dynamics_timeouts(env._handle)) if dynamics_on else 0
-    out["dynamics_timeouts"] = timeouts   # LDS-flag hand-offs of k_dynamics_wave that hit their bound: must be 0
-    out["dynamics_manifold_drops"] = env.dynamics_manifold_drops() if dynamics_on else 0   # contact planes that found no slot: expected 0
-    if a.ppo:
-        ms = [e0.elapsed_time(e1) for e0, e1 in coll_events]
-        out["collective"] = {"backend": backend, "world": world, "allreduce_bytes": GRAD_BUCKET_FLOATS * 4, "allreduces_per_iter": PPO_ALLREDUCES_PER_ITER,
-                             "iters_timed": len(ms), "ms_per_iter_leg": (sum(ms) / len(ms)) if ms else None,
-                             "note": "40 all-reduces + the 1/world scale of the flat fp32 gradient bucket, torch.cuda events on the launch stream"
-                                     + ("; one rank: RCCL's single-rank path (a device copy), exercised so the library is loaded and timed" if world == 1 else "")}
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(env, a.cpu_seconds, dynamics_on, actions)
-    if rank == 0:
-        sys.stdout = sys.__stdout__
-        print(json.dumps(out))
-    if dist is not None:
-        dist.destroy_process_group()
-    if timeouts:
-        sys.stderr.write(f"bench.py: rank {rank}: {timeouts} dynamics hand-off timeout(s): the measurement is void\n")
-        sys.exit(5)
+    return roof
 
 
 def main():

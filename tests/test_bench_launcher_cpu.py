@@ -58,3 +58,34 @@ def test_launcher_deadline(tmp_path):
     t0 = time.time()
     rc, _ = bench.launch_ranks(2, [], script=str(slow), deadline_s=1.0)
     assert rc == 124 and time.time() - t0 < 30.0
+
+
+def test_plain_run_is_the_default_and_steps_are_checked():
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "out", "--steps", "7"])
+    assert a.full is True and a.dump_outputs == "out" and a.steps == 7
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def test_dumped_outputs_keep_one_seeded_sample_of_envs(tmp_path):
+    """What a caller of env.step receives, with the envs sampled the same way in every array; integers become float64."""
+    import numpy as np
+    import torch
+    n = 50
+    obs = torch.arange(n * 3, dtype=torch.float32).view(n, 3)
+    info = {"rewards": {"pose_r": torch.arange(n, dtype=torch.float32)}, "timestep": torch.arange(n, dtype=torch.int32),
+            "ep_num": torch.arange(n, dtype=torch.int64), "compute_time": 0.5}
+    out = bench.collect_outputs(obs, torch.arange(n, dtype=torch.float32), torch.ones(n, dtype=torch.int32), info, rows=8)
+    assert sorted(out) == ["done", "info_ep_num", "info_rewards_pose_r", "info_timestep", "obs", "reward"]
+    rows = out["reward"].astype(np.int64)
+    assert len(rows) == 8 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(out["obs"], obs.numpy()[rows]) and np.array_equal(out["info_timestep"], rows.astype(np.float64))
+    assert out["obs"].dtype == np.float32 and out["done"].dtype == np.float64 and out["info_ep_num"].dtype == np.float64
+    again = bench.collect_outputs(obs, torch.arange(n, dtype=torch.float32), torch.ones(n, dtype=torch.int32), info, rows=8)
+    assert np.array_equal(again["reward"], out["reward"])
+    bench.write_outputs(out, str(tmp_path / "d"))
+    assert np.array_equal(np.load(tmp_path / "d" / "obs.npy"), out["obs"])
+    with pytest.raises(ValueError):
+        bench.write_outputs(out, str(tmp_path / "e"), cap_bytes=64)

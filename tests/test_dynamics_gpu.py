@@ -365,7 +365,7 @@ def test_bench_launches_its_own_ranks_on_the_gpu():
     env = dict(os.environ, PARC_BENCH_SHARE_GPU="1")
     env.pop("RANK", None); env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--envs", "8192", "--steps", "20", "--warmup", "5",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+                        "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -378,6 +378,45 @@ def test_bench_launches_its_own_ranks_on_the_gpu():
     assert abs(d["value"] - 8192 * 20 / (d["ms_per_step"] * 20e-3)) < 1e-6 * d["value"]
     assert d["roofline"]["kernel"] == "k_dynamics_wave" and d["roofline"]["kernel_ms"] > 0 and 0 < d["roofline"]["frac"] < 1
     assert 1e6 < d["value"] < 1e9
+
+
+def test_bench_plain_run_is_lean_and_its_dumped_outputs_repeat(tmp_path):
+    """A plain `bench.py` run prints the headline without what `--full` measures, and `--dump-outputs` writes bit-identical arrays
+    on two runs with the same arguments (16 384 envs: the seeded sample of DUMP_ROWS envs is taken on the device)."""
+    import json
+    import subprocess
+    import sys
+    from conftest import REPO
+    sys.path.insert(0, REPO)
+    import bench
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "PARC_BENCH_SHARE_GPU", "PARC_BENCH_BACKEND"):
+        env.pop(k, None)
+    runs = []
+    for tag in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--envs", "16384", "--steps", "10", "--warmup", "3",
+                            "--dump-outputs", str(tmp_path / tag)], env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        runs.append(json.loads(lines[0]))
+    d = runs[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config"):
+        assert k in d, k
+    assert d["steps"] == 10 and d["warmup"] == 3 and d["dynamics_timeouts"] == 0
+    assert "roofline" not in d and "cpu_baseline" not in d
+    assert abs(d["value"] - 16384 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"obs.npy", "reward.npy", "done.npy", "info_char_contact_forces.npy", "info_timestep.npy"} <= set(names)
+    total = 0
+    for nm in names:
+        x, y = np.load(tmp_path / "a" / nm), np.load(tmp_path / "b" / nm)
+        assert x.dtype in (np.float32, np.float64) and x.shape[0] == bench.DUMP_ROWS, (nm, x.dtype, x.shape)
+        assert np.isfinite(x).all() and x.tobytes() == y.tobytes(), nm
+        total += x.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "a" / "obs.npy").shape == (bench.DUMP_ROWS, 1312)
 
 
 def test_bench_ppo_leg_runs_over_rccl_on_one_gpu():

@@ -4,7 +4,7 @@ TAG=${1:-r02}
 OUT=gpurun_out/bench_set_$TAG
 mkdir -p $OUT
 CIV=data/configs/tracker_config/dm_env_civilization.yaml
-run() { name=$1; shift; python bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err || tail -3 $OUT/$name.err; python - <<PY
+run() { name=$1; shift; python bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err || tail -3 $OUT/$name.err; python - <<PY
 import json
 d = json.load(open("$OUT/$name.json"))
 r = d["roofline"]

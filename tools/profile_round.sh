@@ -10,7 +10,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $ROOT/bench.py --steps 100 --warmup 10 > $OUT/bench_under_profiler.json 2> $OUT/stats.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $ROOT/bench.py --full --steps 100 --warmup 10 > $OUT/bench_under_profiler.json 2> $OUT/stats.log
 echo "stats pass done"
 pmc() { # <dir> <counters> <bench args...>
   local d=$1 c=$2; shift 2
