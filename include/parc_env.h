@@ -375,6 +375,33 @@ const char *parc_env_dynamics_kernel(ParcEnv *env);
  * "" before parc_env_bind_buffers.  The parity tests assert which one they exercised. */
 const char *parc_env_post_kernel(ParcEnv *env);
 
+/* Headless renderer (the reference's viewer, ig_parkour_env.py:417-441 / :1046-1064 / :1123-1132, without a display): ray-casts the scene of k
+ * envs into W x H images on the device.  Scene = what the physics collides with: the heightfield as blocky cell columns (cell (i, j) solid
+ * below hf[i][j] over min + (i, j) d +- d/2, walls between neighbours, nothing outside the grid), the simulated character's collision geoms at
+ * FK of char_root_pos / rot + char_dof_pos and, with draw_ref, the reference character's at FK of ref_root_pos / rot + ref_joint_rot +
+ * ref_offset in (0.5, 0.9, 0.1).  Lambert shading from one sun + ambient, a checker on the column tops, optional hard shadows.
+ * Camera: PARC_CAMERA_TRACK looks at the env's root from root + offset; PARC_CAMERA_STILL from eye to target, both relative to the env's origin.
+ * The struct carries its own size (checked like ParcEnvConfig's); the ABI version does not change with it.
+ * Outputs (caller-owned device buffers, NULL = not written), row-major [k][H][W]:
+ *   rgba  u8 x 4;   depth f32 ray distance, +inf for sky;
+ *   id    u8: 0 sky, 1 terrain top, 2 terrain wall, 16 + b simulated body b, 32 + b reference body b; bit 0x80 = the point is in shadow.
+ * env_ids_dev: int64 [k] device, or NULL for envs 0 .. k-1.  Needs the ref_* mirrors bound when draw_ref is set (else PARC_ERR_STATE). */
+#define PARC_CAMERA_TRACK 0
+#define PARC_CAMERA_STILL 1
+typedef struct {
+    uint32_t struct_size;       /* sizeof(ParcRenderParams) */
+    int32_t width, height;      /* [8, 4096] */
+    int32_t camera_mode;        /* PARC_CAMERA_* */
+    float offset[3];            /* TRACK: eye = root + offset (the reference's default camera sits at (0, -5) and 3 m absolute height) */
+    float eye[3], target[3];    /* STILL: relative to the env's origin */
+    float fov_y;                /* vertical field of view, radians */
+    float sun_dir[3];           /* direction toward the sun (normalised by the library) */
+    float ref_offset[3];        /* ref_char_offset (ig_parkour_env.py:1131) */
+    int32_t draw_ref, shadows, debug_visuals;
+} ParcRenderParams;
+int parc_env_render(ParcEnv *env, const ParcRenderParams *p, const int64_t *env_ids_dev, int32_t k, uint8_t *rgba_dev, float *depth_dev,
+                    uint8_t *id_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1584,6 +1584,8 @@ __global__ __launch_bounds__(1024) void k_build_cdf(const float *fail_rates, con
     }
 }
 
+#include "parc_render.hpp"   // k_render (parc_env_render): reuses joint_dof_to_rot / fk_thread above
+
 // ================================================================================================
 // host side
 // ================================================================================================
@@ -1644,6 +1646,8 @@ struct ParcEnv {
     int *d_done_list = nullptr, *d_done_key = nullptr, *d_chunk_count = nullptr, *d_motion_done = nullptr, *d_reset_count = nullptr;
     int nchunks = 0;
     float *d_scratch_jr = nullptr, *d_start_frac = nullptr;
+    RenderGeoms *d_rgeom = nullptr;                // parc_env_render: the collision geoms, uploaded at creation
+    float hf_max = 0.f;                            // highest column top (parc_env_load_terrain), bounds the renderer's terrain traversal
     unsigned long long *d_reset_calls = nullptr;   // device counter of sampling resets (Philox call index)
     const float *action_bound = nullptr;           // parc_env_bind_action
     hipGraphExec_t graph_exec = nullptr;           // parc_env_step_reset_graph
@@ -1670,7 +1674,7 @@ extern "C" int parc_abi_version(void) { return PARC_ABI_VERSION; }
 static void free_dev(ParcEnv *e) {
     void *ptrs[] = {e->d_man_ovf, e->d_root_shadow, e->d_prep, e->d_dyn, e->d_coop, e->d_wave, e->d_tab, e->d_ray, e->d_env_off, e->d_hf, e->d_motion_off, e->d_records, e->d_meta, e->d_weights, e->d_fail,
                     e->d_cdf, e->d_ema, e->d_done_list, e->d_done_key, e->d_chunk_count, e->d_motion_done, e->d_reset_count, e->d_reset_calls,
-                    e->d_scratch_jr};
+                    e->d_scratch_jr, e->d_rgeom};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (e->h_health) (void)hipHostFree(e->h_health);
     for (auto &ev : e->ev) if (ev) (void)hipEventDestroy(ev);
@@ -1786,6 +1790,22 @@ extern "C" int parc_env_create(const ParcEnvConfig *cfg, ParcEnv **out) {
         (r = up((void **)&e->d_reset_count, nullptr, 2 * sizeof(int))) != hipSuccess ||
         (r = up((void **)&e->d_reset_calls, nullptr, sizeof(unsigned long long))) != hipSuccess ||
         (r = up((void **)&e->d_scratch_jr, nullptr, sizeof(float) * 4 * J * N)) != hipSuccess) {
+        free_dev(e); delete e;
+        return fail(PARC_ERR_HIP, std::string("device allocation failed: ") + hipGetErrorString(r));
+    }
+    { // render geometry: the MJCF collision geoms the scene builder puts into ParcDynamicsParams whether or not the dynamics run
+        RenderGeoms rg;
+        memset(&rg, 0, sizeof(rg));
+        const ParcDynamicsParams &dp = cfg->dynamics;
+        for (int g = 0; g < dp.num_geoms && g < PARC_MAX_GEOMS; ++g) {
+            if (dp.geom_body[g] < 0 || dp.geom_body[g] >= B || dp.geom_type[g] < PARC_GEOM_BOX || dp.geom_type[g] > PARC_GEOM_CAPSULE) continue;
+            const int n = rg.n++;
+            rg.body[n] = dp.geom_body[g]; rg.type[n] = dp.geom_type[g];
+            for (int c = 0; c < 3; ++c) { rg.p0[n][c] = dp.geom_pos[g][c]; rg.p1[n][c] = dp.geom_pos2[g][c]; rg.size[n][c] = dp.geom_size[g][c]; }
+        }
+        r = up((void **)&e->d_rgeom, &rg, sizeof(rg));
+    }
+    if (r != hipSuccess) {
         free_dev(e); delete e;
         return fail(PARC_ERR_HIP, std::string("device allocation failed: ") + hipGetErrorString(r));
     }
@@ -1985,6 +2005,8 @@ extern "C" int parc_env_load_terrain(ParcEnv *e, const float *hf, int32_t X, int
     sp.rdx = (float)(1.0L / (long double)dx); sp.rdy = (float)(1.0L / (long double)dy);
     sp.motion_offsets = e->d_motion_off;
     e->T = T;
+    e->hf_max = hf[0];
+    for (size_t q = 1; q < (size_t)X * Y; ++q) e->hf_max = fmaxf(e->hf_max, hf[q]);
     // terrain tile radius: farthest ray sample in cells, +1 for the two independent roundings
     std::vector<float> ray(2 * (size_t)e->R);
     HIPCHK(hipMemcpy(ray.data(), e->d_ray, sizeof(float) * 2 * e->R, hipMemcpyDeviceToHost));
@@ -2711,6 +2733,52 @@ extern "C" const char *parc_env_dynamics_kernel(ParcEnv *e) {
 extern "C" const char *parc_env_post_kernel(ParcEnv *e) {
     if (!e || !e->bound) return "";
     return (wants_mirror(e->sp.buf) || obs_variant(e->cfg)) ? "k_env_post<MODE,true>" : "k_env_post<MODE,false>";
+}
+
+// Headless renderer (parc_render.hpp).  Every argument is checked before the device is touched; the launch is one kernel on the caller's
+// stream, outside the captured step graph, and reads the state buffers without writing any of them.
+extern "C" int parc_env_render(ParcEnv *e, const ParcRenderParams *p, const int64_t *env_ids_dev, int32_t k, uint8_t *rgba_dev, float *depth_dev,
+                               uint8_t *id_dev, void *stream) {
+    if (!p) return fail(PARC_ERR_INVALID, "null ParcRenderParams");
+    if (p->struct_size != sizeof(ParcRenderParams)) return fail(PARC_ERR_INVALID, "ParcRenderParams ABI mismatch (struct_size)");
+    if (int rc = check_ready(e)) return rc;
+    if (p->width < 8 || p->width > 4096 || p->height < 8 || p->height > 4096) return fail(PARC_ERR_INVALID, "render: width and height must be in [8, 4096]");
+    if (k < 1 || k > e->N) return fail(PARC_ERR_INVALID, "render: k must be in [1, num_envs]");
+    if (k > 65535) return fail(PARC_ERR_INVALID, "render: at most 65535 envs per call");
+    if (p->camera_mode != PARC_CAMERA_TRACK && p->camera_mode != PARC_CAMERA_STILL) return fail(PARC_ERR_INVALID, "render: unknown camera_mode");
+    if (!(p->fov_y > 0.f && p->fov_y < 3.1f)) return fail(PARC_ERR_INVALID, "render: fov_y must be in (0, 3.1) radians");
+    const ParcEnvBuffers &b = e->sp.buf;
+    if (p->draw_ref && (!b.ref_root_pos || !b.ref_root_rot || !b.ref_joint_rot || (p->debug_visuals && !b.ref_contacts)))
+        return fail(PARC_ERR_STATE, "render: the reference character needs the ref_* mirrors bound (ref_root_pos, ref_root_rot, ref_joint_rot, ref_contacts)");
+    const float sl = sqrtf(p->sun_dir[0] * p->sun_dir[0] + p->sun_dir[1] * p->sun_dir[1] + p->sun_dir[2] * p->sun_dir[2]);
+    if (!(sl > 1e-6f)) return fail(PARC_ERR_INVALID, "render: sun_dir must be non-zero");
+    const float *cam = p->camera_mode == PARC_CAMERA_TRACK ? p->offset : nullptr;
+    if (cam && !(cam[0] * cam[0] + cam[1] * cam[1] + cam[2] * cam[2] > 1e-12f)) return fail(PARC_ERR_INVALID, "render: the track offset must be non-zero");
+    if (!cam) {
+        const float dx = p->eye[0] - p->target[0], dy = p->eye[1] - p->target[1], dz = p->eye[2] - p->target[2];
+        if (!(dx * dx + dy * dy + dz * dz > 1e-12f)) return fail(PARC_ERR_INVALID, "render: eye and target coincide");
+    }
+    if (!rgba_dev && !depth_dev && !id_dev) return PARC_OK;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    RenderArgs A;
+    memset(&A, 0, sizeof(A));
+    A.W = p->width; A.H = p->height; A.N = e->N; A.B = e->B; A.D = e->D;
+    A.cam_mode = p->camera_mode; A.draw_ref = p->draw_ref ? 1 : 0; A.shadows = p->shadows ? 1 : 0; A.debug = p->debug_visuals ? 1 : 0;
+    for (int c = 0; c < 3; ++c) {
+        A.off[c] = p->offset[c]; A.eye[c] = p->eye[c]; A.tgt[c] = p->target[c]; A.ref_off[c] = p->ref_offset[c]; A.sun[c] = p->sun_dir[c] / sl;
+    }
+    A.tan_half = tanf(0.5f * p->fov_y); A.aspect = (float)p->width / (float)p->height;
+    A.env_ids = env_ids_dev;
+    A.root_pos = b.char_root_pos; A.root_rot = b.char_root_rot; A.dof_pos = b.char_dof_pos; A.contact_forces = b.contact_forces;
+    A.ref_root_pos = b.ref_root_pos; A.ref_root_rot = b.ref_root_rot; A.ref_joint_rot = b.ref_joint_rot; A.ref_contacts = b.ref_contacts;
+    A.env_off = e->d_env_off;
+    A.hf = e->sp.hf; A.X = e->sp.X; A.Y = e->sp.Y; A.min_x = e->sp.min_x; A.min_y = e->sp.min_y; A.dx = e->sp.dx; A.dy = e->sp.dy; A.hmax = e->hf_max;
+    A.tables = e->d_tab; A.geoms = e->d_rgeom;
+    A.rgba = rgba_dev; A.depth = depth_dev; A.id = id_dev;
+    const dim3 grid((unsigned)((p->width + RENDER_TILE - 1) / RENDER_TILE), (unsigned)((p->height + RENDER_TILE - 1) / RENDER_TILE), (unsigned)k);
+    hipLaunchKernelGGL(k_render, grid, dim3(RENDER_TILE * RENDER_TILE), 0, (hipStream_t)stream, A);
+    HIPCHK(hipGetLastError());
+    return PARC_OK;
 }
 
 #ifdef PARC_STAMPS

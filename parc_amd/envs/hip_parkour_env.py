@@ -89,7 +89,7 @@ class HipParkourEnv(base_env.BaseEnv):
 
     def __init__(self, config, num_envs, device, visualize=False, env_id_base=0, total_envs=None, seed=0,
                  mirror_ref_state=True, enable_dynamics=None, dev_options=None, env_offsets=None):
-        super().__init__(visualize=False)
+        super().__init__(visualize=bool(visualize))
         self._start_compute_time = time.time()
         self._lib = L.load()
         if not torch.cuda.is_available():
@@ -170,6 +170,17 @@ class HipParkourEnv(base_env.BaseEnv):
         self._dm_view = _DMView(self)
         self._info = dict()
         self.set_write_agent_states_flag(env_config.get("write_agent_states", False))
+        # viewer (ig_parkour_env.py:417-441, 1046-1064): camera_mode / debug_visuals / ref_char_offset of the env config; with visualize, every
+        # reset / step renders the camera env into the frame sink (set_frame_sink; nothing is allocated or run without visualize)
+        self._camera_mode = env_config.get("camera_mode", "track")
+        self._debug_visuals = bool(env_config.get("debug_visuals", False))
+        self._ref_char_offset = [float(v) for v in (env_config.get("ref_char_offset") or [0.0, 0.0, 0.0])]
+        self._camera_env_id = 0
+        self._frame_sink = None
+        self._render_every = 1
+        self._render_size = (320, 240)
+        self._vis_calls = 0
+        self._vis_bufs = None
         if self._demo_mode:
             print("DEMO MODE ENABLED")
 
@@ -250,6 +261,7 @@ class HipParkourEnv(base_env.BaseEnv):
             if env_ids.numel() > 0:
                 L.check(self._lib.parc_env_reset(self._handle, env_ids.data_ptr(), int(env_ids.numel()), self._stream()))
         self._update_info()
+        self._visual_update()
         return self._obs_buf, self._info
 
     def reset_done(self):
@@ -282,6 +294,7 @@ class HipParkourEnv(base_env.BaseEnv):
             self.check_health()
         self.write_agent_states()  # ig_parkour_env.py:686-696: after update_done, before the agent resets anything
         self._update_info()
+        self._visual_update()
         return self._obs_buf, self._reward_buf, self._done_buf, self._info
 
     def step_and_reset_done(self, action):
@@ -300,6 +313,7 @@ class HipParkourEnv(base_env.BaseEnv):
         if self._health is not None and self._health[0] != 0:
             self.check_health()
         self._update_info()
+        self._visual_update()
         return self._obs_buf, self._reward_buf, self._done_buf, self._info
 
     def _update_info(self):
@@ -568,6 +582,80 @@ class HipParkourEnv(base_env.BaseEnv):
 
     def post_test_update(self):
         return
+
+    # ---- headless viewer (parc_env_render) ----------------------------------------------------------------
+    def render_params(self, width=320, height=240, camera=None, draw_ref=True, shadows=True):
+        """The ``ParcRenderParams`` of one render call.  ``camera=None`` takes ``camera_mode`` / ``debug_visuals`` from the env config; a
+        dict overrides any of ``mode`` ("track" | "still"), ``offset``, ``eye``, ``target``, ``fov_y`` (radians), ``sun_dir``,
+        ``debug_visuals``, ``ref_offset``."""
+        from parc_amd import render as R
+        cam = dict(mode=self._camera_mode, debug_visuals=self._debug_visuals, ref_offset=self._ref_char_offset)
+        cam.update(camera or {})
+        return R.make_params(width, height, cam, draw_ref=draw_ref, shadows=shadows)
+
+    def render(self, env_ids=None, width=320, height=240, camera=None, draw_ref=True, shadows=True, depth=False, ids=False):
+        """Ray-cast the scene of ``env_ids`` (None = every env) into device images: ``uint8 [k, H, W, 4]``; with ``depth`` / ``ids`` a
+        tuple ``(rgba, depth f32 [k, H, W] or None, id u8 [k, H, W] or None)`` (ID encoding: include/parc_env.h).  Enqueued on the current
+        stream after whatever was enqueued before (no host sync); reads the state, writes none of it."""
+        p = self.render_params(width, height, camera, draw_ref, shadows)
+        ids_t = None
+        k = self._num_envs
+        if env_ids is not None:
+            ids_t = torch.as_tensor(env_ids, dtype=torch.long).reshape(-1).to(self._device).contiguous()
+            k = int(ids_t.numel())
+        dev = self._device
+        rgba = torch.empty(k, height, width, 4, dtype=torch.uint8, device=dev)
+        dep = torch.empty(k, height, width, dtype=torch.float32, device=dev) if depth else None
+        idm = torch.empty(k, height, width, dtype=torch.uint8, device=dev) if ids else None
+        self._render_into(p, ids_t, k, rgba, dep, idm)
+        if depth or ids:
+            return rgba, dep, idm
+        return rgba
+
+    def _render_into(self, p, ids_t, k, rgba, dep=None, idm=None):
+        ptr = lambda t: None if t is None else t.data_ptr()
+        L.check(self._lib.parc_env_render(self._handle, C.byref(p), ptr(ids_t), int(k), ptr(rgba), ptr(dep), ptr(idm), self._stream()))
+
+    @property
+    def camera_env_id(self):
+        return self._camera_env_id
+
+    @camera_env_id.setter
+    def camera_env_id(self, env_id):
+        env_id = int(env_id)
+        if not 0 <= env_id < self._num_envs:
+            raise ValueError(f"camera_env_id {env_id} is not an env of this handle (0..{self._num_envs - 1})")
+        self._camera_env_id = env_id
+        if self._vis_bufs is not None:
+            self._vis_bufs["ids"].fill_(env_id)
+
+    def set_frame_sink(self, sink, every=1, size=(320, 240)):
+        """Where the frames of ``visualize`` go: an object with ``submit(rgba_dev [H, W, 4])`` (parc_amd.util.frame_writer.FrameWriter);
+        one frame every ``every`` reset / step calls, ``size`` = (width, height)."""
+        self._frame_sink = sink
+        self._render_every = max(int(every), 1)
+        self._render_size = (int(size[0]), int(size[1]))
+        self._vis_bufs = None
+
+    def _visual_update(self):
+        """With ``visualize``: render the camera env after a reset / step, as a launch of its own on the env's stream (the captured step
+        graph is not touched), and hand the frame to the sink without waiting for it."""
+        if not self._visualize:
+            return
+        self._vis_calls += 1
+        if (self._vis_calls - 1) % self._render_every != 0:
+            return
+        if self._frame_sink is None:
+            from parc_amd.util.frame_writer import FrameWriter
+            self._frame_sink = FrameWriter(os.path.join("output", "frames"))
+        if self._vis_bufs is None:
+            w, h = self._render_size
+            self._vis_bufs = dict(params=self.render_params(w, h, draw_ref=self._mirror_ref_state),
+                                  ids=torch.full((1,), self._camera_env_id, dtype=torch.long, device=self._device),
+                                  rgba=torch.empty(1, h, w, 4, dtype=torch.uint8, device=self._device))
+        vb = self._vis_bufs
+        self._render_into(vb["params"], vb["ids"], 1, vb["rgba"])
+        self._frame_sink.submit(vb["rgba"][0])
 
     # ---- measurement ------------------------------------------------------------------------------------
     def set_kernel_timing(self, enable):

@@ -6,6 +6,9 @@
         --agent_config data/configs/tracker_config/dm_agent_default.yaml \\
         --out_model_file output/model.pt --int_output_dir output/checkpoints --log_file output/log.txt
 
+Headless viewer: ``--visualize true`` writes the camera env's frames as PNG to ``--frame_dir`` (default output/frames), one every
+``--render_every`` steps (default 1), ``--render_size WxH`` (default 320x240).
+
 Multi-GPU (new): launch with ``python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ...``;
 every rank owns ``num_envs`` envs (global env index = rank * num_envs + i) and gradients are all-reduced over RCCL.
 """
@@ -66,8 +69,15 @@ def run(args):
             os.makedirs(d, exist_ok=True)
 
     ws, rk = dist_util.world_size(), dist_util.rank()
+    visualize = visualize and rk == 0  # one viewer: only rank 0 renders
     env = env_builder.build_env(path_loader.resolve_path(args.parse_string("env_config")), num_envs, device, visualize,
                                 env_id_base=rk * num_envs, total_envs=ws * num_envs, seed=seed)
+    frames = None
+    if visualize:  # headless viewer: the camera env as frame_%06d.png under --frame_dir
+        from parc_amd.util.frame_writer import FrameWriter
+        w, h = (int(v) for v in args.parse_string("render_size", "320x240").lower().split("x"))
+        frames = FrameWriter(args.parse_string("frame_dir", "output/frames"))
+        env.set_frame_sink(frames, every=args.parse_int("render_every", 1), size=(w, h))
     agent = agent_builder.build_agent(path_loader.resolve_path(args.parse_string("agent_config")), env, device)
     if model_file != "":
         agent.load(path_loader.resolve_path(model_file))
@@ -89,6 +99,8 @@ def run(args):
         record_dm_motions(agent)
     else:
         raise AssertionError("Unsupported mode: {}".format(mode))
+    if frames is not None:
+        frames.close()
     if hasattr(env, "check_health"):  # hand-off timeouts of the dynamics kernel: raises -> non-zero exit code
         env.check_health()
 
