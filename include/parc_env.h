@@ -402,6 +402,21 @@ typedef struct {
 int parc_env_render(ParcEnv *env, const ParcRenderParams *p, const int64_t *env_ids_dev, int32_t k, uint8_t *rgba_dev, float *depth_dev,
                     uint8_t *id_dev, void *stream);
 
+/* Scene render (the reference's viewer draws every env, ig_parkour_env.py:409-441): ONE W x H image of the terrain and the characters of n
+ * envs, each at its state + env_offsets in the one world (envs that track the same clip overlap).  The camera is p's, relative to
+ * camera_env exactly as parc_env_render places it for that env (TRACK: eye = its root + offset; STILL: eye and target relative to its
+ * origin).  With draw_ref every listed env's reference character is drawn too (+ ref_offset).  Every drawn character casts shadows, also
+ * one outside the view; debug_visuals tints the camera env's characters only (the reference tints _camera_env_id, :1046-1064).
+ * env_ids_dev: int64 [n] device, or NULL for envs 0 .. n-1; ids outside [0, num_envs) are skipped on the device, characters whose root is
+ * not finite are not drawn.  Outputs (caller-owned device buffers, NULL = not written), row-major [H][W]: rgba, depth and id encoded as
+ * for parc_env_render; env_map int32 = env of the character hit, -1 for terrain and sky.  Equal distances go to the smaller env, then
+ * to the simulated character: two calls on the same state give identical bytes.  Errors: PARC_ERR_INVALID for struct_size, sizes,
+ * camera, camera_env outside [0, num_envs) or n outside [1, num_envs]; PARC_ERR_STATE when draw_ref is set without the ref_* mirrors.
+ * Device workspace, allocated on the first call (again when n grows) and freed by parc_env_destroy: 2 x (4 x round_up(7 B, 4) + 36)
+ * bytes per env of n (B = bodies; 936 B for the 15-body humanoid) + 48 KB of bins.  Everything is enqueued on `stream` (no host sync). */
+int parc_env_render_scene(ParcEnv *env, const ParcRenderParams *p, int32_t camera_env, const int64_t *env_ids_dev, int32_t n,
+                          uint8_t *rgba_dev, float *depth_dev, uint8_t *id_dev, int32_t *env_map_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

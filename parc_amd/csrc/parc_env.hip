@@ -1585,6 +1585,7 @@ __global__ __launch_bounds__(1024) void k_build_cdf(const float *fail_rates, con
 }
 
 #include "parc_render.hpp"   // k_render (parc_env_render): reuses joint_dof_to_rot / fk_thread above
+#include "parc_render_scene.hpp"   // parc_env_render_scene: the bins and k_render_scene, on top of parc_render.hpp
 
 // ================================================================================================
 // host side
@@ -1648,6 +1649,9 @@ struct ParcEnv {
     float *d_scratch_jr = nullptr, *d_start_frac = nullptr;
     RenderGeoms *d_rgeom = nullptr;                // parc_env_render: the collision geoms, uploaded at creation
     float hf_max = 0.f;                            // highest column top (parc_env_load_terrain), bounds the renderer's terrain traversal
+    float hf_min = 0.f;                            // lowest column top: the floor of the scene render's shadow-caster cull
+    char *d_scene = nullptr;                       // parc_env_render_scene workspace, allocated on the first call (scene_ws_bytes)
+    int scene_cap = 0;                             // envs the workspace holds
     unsigned long long *d_reset_calls = nullptr;   // device counter of sampling resets (Philox call index)
     const float *action_bound = nullptr;           // parc_env_bind_action
     hipGraphExec_t graph_exec = nullptr;           // parc_env_step_reset_graph
@@ -1674,7 +1678,7 @@ extern "C" int parc_abi_version(void) { return PARC_ABI_VERSION; }
 static void free_dev(ParcEnv *e) {
     void *ptrs[] = {e->d_man_ovf, e->d_root_shadow, e->d_prep, e->d_dyn, e->d_coop, e->d_wave, e->d_tab, e->d_ray, e->d_env_off, e->d_hf, e->d_motion_off, e->d_records, e->d_meta, e->d_weights, e->d_fail,
                     e->d_cdf, e->d_ema, e->d_done_list, e->d_done_key, e->d_chunk_count, e->d_motion_done, e->d_reset_count, e->d_reset_calls,
-                    e->d_scratch_jr, e->d_rgeom};
+                    e->d_scratch_jr, e->d_rgeom, e->d_scene};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (e->h_health) (void)hipHostFree(e->h_health);
     for (auto &ev : e->ev) if (ev) (void)hipEventDestroy(ev);
@@ -2007,6 +2011,8 @@ extern "C" int parc_env_load_terrain(ParcEnv *e, const float *hf, int32_t X, int
     e->T = T;
     e->hf_max = hf[0];
     for (size_t q = 1; q < (size_t)X * Y; ++q) e->hf_max = fmaxf(e->hf_max, hf[q]);
+    e->hf_min = hf[0];
+    for (size_t q = 1; q < (size_t)X * Y; ++q) e->hf_min = fminf(e->hf_min, hf[q]);
     // terrain tile radius: farthest ray sample in cells, +1 for the two independent roundings
     std::vector<float> ray(2 * (size_t)e->R);
     HIPCHK(hipMemcpy(ray.data(), e->d_ray, sizeof(float) * 2 * e->R, hipMemcpyDeviceToHost));
@@ -2777,6 +2783,89 @@ extern "C" int parc_env_render(ParcEnv *e, const ParcRenderParams *p, const int6
     A.rgba = rgba_dev; A.depth = depth_dev; A.id = id_dev;
     const dim3 grid((unsigned)((p->width + RENDER_TILE - 1) / RENDER_TILE), (unsigned)((p->height + RENDER_TILE - 1) / RENDER_TILE), (unsigned)k);
     hipLaunchKernelGGL(k_render, grid, dim3(RENDER_TILE * RENDER_TILE), 0, (hipStream_t)stream, A);
+    HIPCHK(hipGetLastError());
+    return PARC_OK;
+}
+
+// Scene render (parc_render_scene.hpp): one image of the characters of n envs in the one world, camera of camera_env.  Checks like
+// parc_env_render before the device is touched; seven launches on the caller's stream, outside the captured step graph, reading the state
+// buffers without writing any of them.  The workspace is allocated on the first call (and again when a call asks for more envs).
+static int scene_stride(int B) { return (7 * B + 3) & ~3; }   // floats per character record: B rotations, B positions, 16-B aligned
+static size_t scene_ws_bytes(int B, int n) {                  // per env: 2 characters x (record + sphere + key + 4 bin items)
+    const size_t slots = 2 * (size_t)n;
+    return sizeof(SceneHdr) + sizeof(int) * (3 * SCENE_MAX_BINS + 1) + slots * (sizeof(float) * scene_stride(B) + sizeof(float4) + sizeof(int) * (1 + SCENE_BINS_PER_SLOT));
+}
+
+extern "C" int parc_env_render_scene(ParcEnv *e, const ParcRenderParams *p, int32_t camera_env, const int64_t *env_ids_dev, int32_t n,
+                                     uint8_t *rgba_dev, float *depth_dev, uint8_t *id_dev, int32_t *env_map_dev, void *stream) {
+    if (!p) return fail(PARC_ERR_INVALID, "null ParcRenderParams");
+    if (p->struct_size != sizeof(ParcRenderParams)) return fail(PARC_ERR_INVALID, "ParcRenderParams ABI mismatch (struct_size)");
+    if (int rc = check_ready(e)) return rc;
+    if (p->width < 8 || p->width > 4096 || p->height < 8 || p->height > 4096) return fail(PARC_ERR_INVALID, "render_scene: width and height must be in [8, 4096]");
+    if (camera_env < 0 || camera_env >= e->N) return fail(PARC_ERR_INVALID, "render_scene: camera_env must be in [0, num_envs)");
+    if (n < 1 || n > e->N) return fail(PARC_ERR_INVALID, "render_scene: n must be in [1, num_envs]");
+    if (e->N > (1 << 28)) return fail(PARC_ERR_INVALID, "render_scene: at most 2^28 envs");
+    if (p->camera_mode != PARC_CAMERA_TRACK && p->camera_mode != PARC_CAMERA_STILL) return fail(PARC_ERR_INVALID, "render_scene: unknown camera_mode");
+    if (!(p->fov_y > 0.f && p->fov_y < 3.1f)) return fail(PARC_ERR_INVALID, "render_scene: fov_y must be in (0, 3.1) radians");
+    const ParcEnvBuffers &b = e->sp.buf;
+    if (p->draw_ref && (!b.ref_root_pos || !b.ref_root_rot || !b.ref_joint_rot || (p->debug_visuals && !b.ref_contacts)))
+        return fail(PARC_ERR_STATE, "render_scene: the reference characters need the ref_* mirrors bound (ref_root_pos, ref_root_rot, ref_joint_rot, ref_contacts)");
+    const float sl = sqrtf(p->sun_dir[0] * p->sun_dir[0] + p->sun_dir[1] * p->sun_dir[1] + p->sun_dir[2] * p->sun_dir[2]);
+    if (!(sl > 1e-6f)) return fail(PARC_ERR_INVALID, "render_scene: sun_dir must be non-zero");
+    if (p->camera_mode == PARC_CAMERA_TRACK) {
+        const float *o = p->offset;
+        if (!(o[0] * o[0] + o[1] * o[1] + o[2] * o[2] > 1e-12f)) return fail(PARC_ERR_INVALID, "render_scene: the track offset must be non-zero");
+    } else {
+        const float dx = p->eye[0] - p->target[0], dy = p->eye[1] - p->target[1], dz = p->eye[2] - p->target[2];
+        if (!(dx * dx + dy * dy + dz * dz > 1e-12f)) return fail(PARC_ERR_INVALID, "render_scene: eye and target coincide");
+    }
+    if (!rgba_dev && !depth_dev && !id_dev && !env_map_dev) return PARC_OK;
+    HIPCHK(hipSetDevice(e->cfg.device));
+    if (e->scene_cap < n) {
+        if (e->d_scene) { HIPCHK(hipFree(e->d_scene)); e->d_scene = nullptr; e->scene_cap = 0; }
+        HIPCHK(hipMalloc((void **)&e->d_scene, scene_ws_bytes(e->B, n)));
+        e->scene_cap = n;
+    }
+    SceneArgs S;
+    memset(&S, 0, sizeof(S));
+    RenderArgs &A = S.R;
+    A.W = p->width; A.H = p->height; A.N = e->N; A.B = e->B; A.D = e->D;
+    A.cam_mode = p->camera_mode; A.draw_ref = p->draw_ref ? 1 : 0; A.shadows = p->shadows ? 1 : 0; A.debug = p->debug_visuals ? 1 : 0;
+    for (int c = 0; c < 3; ++c) {
+        A.off[c] = p->offset[c]; A.eye[c] = p->eye[c]; A.tgt[c] = p->target[c]; A.ref_off[c] = p->ref_offset[c]; A.sun[c] = p->sun_dir[c] / sl;
+    }
+    A.tan_half = tanf(0.5f * p->fov_y); A.aspect = (float)p->width / (float)p->height;
+    A.env_ids = env_ids_dev;
+    A.root_pos = b.char_root_pos; A.root_rot = b.char_root_rot; A.dof_pos = b.char_dof_pos; A.contact_forces = b.contact_forces;
+    A.ref_root_pos = b.ref_root_pos; A.ref_root_rot = b.ref_root_rot; A.ref_joint_rot = b.ref_joint_rot; A.ref_contacts = b.ref_contacts;
+    A.env_off = e->d_env_off;
+    A.hf = e->sp.hf; A.X = e->sp.X; A.Y = e->sp.Y; A.min_x = e->sp.min_x; A.min_y = e->sp.min_y; A.dx = e->sp.dx; A.dy = e->sp.dy; A.hmax = e->hf_max;
+    A.tables = e->d_tab; A.geoms = e->d_rgeom;
+    A.rgba = rgba_dev; A.depth = depth_dev; A.id = id_dev;
+    S.n = n; S.nk = A.draw_ref ? 2 : 1; S.cam_env = camera_env; S.stride = scene_stride(e->B); S.hmin = e->hf_min;
+    S.env_map = env_map_dev;
+    { // workspace carve-up (every piece 16-B aligned: the header, the bin arrays rounded up, float4 and float records first)
+        const size_t slots = 2 * (size_t)e->scene_cap;
+        char *w = e->d_scene;
+        S.hdr = (SceneHdr *)w; w += sizeof(SceneHdr);
+        S.sph = (float4 *)w; w += sizeof(float4) * slots;
+        S.rec = (float *)w; w += sizeof(float) * S.stride * slots;
+        S.skey = (int *)w; w += sizeof(int) * slots;
+        S.items = (int *)w; w += sizeof(int) * SCENE_BINS_PER_SLOT * slots;
+        S.bin_count = (int *)w; w += sizeof(int) * SCENE_MAX_BINS;
+        S.bin_cursor = (int *)w; w += sizeof(int) * SCENE_MAX_BINS;
+        S.bin_start = (int *)w;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned slots = (unsigned)(n * S.nk);
+    hipLaunchKernelGGL(k_scene_init, dim3(1), dim3(256), 0, st, S);
+    hipLaunchKernelGGL(k_scene_roots, dim3((slots + 255) / 256), dim3(256), 0, st, S);
+    hipLaunchKernelGGL(k_scene_prep, dim3((slots + 63) / 64), dim3(64), 0, st, S);
+    hipLaunchKernelGGL(k_scene_count, dim3((slots + 255) / 256), dim3(256), 0, st, S);
+    hipLaunchKernelGGL(k_scene_scan, dim3(1), dim3(1024), 0, st, S);
+    hipLaunchKernelGGL(k_scene_scatter, dim3((slots + 255) / 256), dim3(256), 0, st, S);
+    const dim3 grid((unsigned)((p->width + RENDER_TILE - 1) / RENDER_TILE), (unsigned)((p->height + RENDER_TILE - 1) / RENDER_TILE));
+    hipLaunchKernelGGL(k_render_scene, grid, dim3(RENDER_TILE * RENDER_TILE), 0, st, S);
     HIPCHK(hipGetLastError());
     return PARC_OK;
 }

@@ -179,6 +179,7 @@ class HipParkourEnv(base_env.BaseEnv):
         self._frame_sink = None
         self._render_every = 1
         self._render_size = (320, 240)
+        self._render_scene_frames = False
         self._vis_calls = 0
         self._vis_bufs = None
         if self._demo_mode:
@@ -612,6 +613,36 @@ class HipParkourEnv(base_env.BaseEnv):
             return rgba, dep, idm
         return rgba
 
+    def render_scene(self, camera_env=None, env_ids=None, width=320, height=240, camera=None, draw_ref=True, shadows=True, depth=False,
+                     ids=False, env_map=False):
+        """Ray-cast ONE image of the characters of ``env_ids`` (None = every env) in the one world (state + env offsets), with the camera
+        of ``render`` placed relative to ``camera_env`` (None = ``camera_env_id``).  Returns ``uint8 [H, W, 4]``; with ``depth`` / ``ids``
+        the tuple ``(rgba, depth f32 [H, W] or None, id u8 [H, W] or None)`` as ``render`` gives it for one env, and with ``env_map`` a
+        fourth item, ``int32 [H, W]``: the env of the character hit, -1 for terrain and sky.  Enqueued on the current stream (no host
+        sync); reads the state, writes none of it."""
+        p = self.render_params(width, height, camera, draw_ref, shadows)
+        cam = self._camera_env_id if camera_env is None else int(camera_env)
+        ids_t, n = None, self._num_envs
+        if env_ids is not None:
+            ids_t = torch.as_tensor(env_ids, dtype=torch.long).reshape(-1).to(self._device).contiguous()
+            n = int(ids_t.numel())
+        dev = self._device
+        rgba = torch.empty(height, width, 4, dtype=torch.uint8, device=dev)
+        dep = torch.empty(height, width, dtype=torch.float32, device=dev) if depth else None
+        idm = torch.empty(height, width, dtype=torch.uint8, device=dev) if ids else None
+        emap = torch.empty(height, width, dtype=torch.int32, device=dev) if env_map else None
+        self._render_scene_into(p, cam, ids_t, n, rgba, dep, idm, emap)
+        if env_map:
+            return rgba, dep, idm, emap
+        if depth or ids:
+            return rgba, dep, idm
+        return rgba
+
+    def _render_scene_into(self, p, camera_env, ids_t, n, rgba, dep=None, idm=None, emap=None):
+        ptr = lambda t: None if t is None else t.data_ptr()
+        L.check(self._lib.parc_env_render_scene(self._handle, C.byref(p), int(camera_env), ptr(ids_t), int(n), ptr(rgba), ptr(dep), ptr(idm),
+                                                ptr(emap), self._stream()))
+
     def _render_into(self, p, ids_t, k, rgba, dep=None, idm=None):
         ptr = lambda t: None if t is None else t.data_ptr()
         L.check(self._lib.parc_env_render(self._handle, C.byref(p), ptr(ids_t), int(k), ptr(rgba), ptr(dep), ptr(idm), self._stream()))
@@ -629,12 +660,14 @@ class HipParkourEnv(base_env.BaseEnv):
         if self._vis_bufs is not None:
             self._vis_bufs["ids"].fill_(env_id)
 
-    def set_frame_sink(self, sink, every=1, size=(320, 240)):
+    def set_frame_sink(self, sink, every=1, size=(320, 240), scene=False):
         """Where the frames of ``visualize`` go: an object with ``submit(rgba_dev [H, W, 4])`` (parc_amd.util.frame_writer.FrameWriter);
-        one frame every ``every`` reset / step calls, ``size`` = (width, height)."""
+        one frame every ``every`` reset / step calls, ``size`` = (width, height).  ``scene``: every env's characters in the frame
+        (``render_scene`` with the camera of ``camera_env_id``); by default the camera env alone (``render``)."""
         self._frame_sink = sink
         self._render_every = max(int(every), 1)
         self._render_size = (int(size[0]), int(size[1]))
+        self._render_scene_frames = bool(scene)
         self._vis_bufs = None
 
     def _visual_update(self):
@@ -654,7 +687,10 @@ class HipParkourEnv(base_env.BaseEnv):
                                   ids=torch.full((1,), self._camera_env_id, dtype=torch.long, device=self._device),
                                   rgba=torch.empty(1, h, w, 4, dtype=torch.uint8, device=self._device))
         vb = self._vis_bufs
-        self._render_into(vb["params"], vb["ids"], 1, vb["rgba"])
+        if self._render_scene_frames:
+            self._render_scene_into(vb["params"], self._camera_env_id, None, self._num_envs, vb["rgba"][0])
+        else:
+            self._render_into(vb["params"], vb["ids"], 1, vb["rgba"])
         self._frame_sink.submit(vb["rgba"][0])
 
     # ---- measurement ------------------------------------------------------------------------------------

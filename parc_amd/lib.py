@@ -170,6 +170,7 @@ def load():
     lib.parc_env_post_kernel.argtypes = [vp]
     lib.parc_env_post_kernel.restype = C.c_char_p
     lib.parc_env_render.argtypes = [vp, C.POINTER(ParcRenderParams), vp, C.c_int32, vp, vp, vp, vp]
+    lib.parc_env_render_scene.argtypes = [vp, C.POINTER(ParcRenderParams), C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -182,7 +183,7 @@ EXPORTED_SYMBOLS = [
     "parc_rot_to_dof", "parc_forward_kinematics", "parc_calc_motion_frame", "parc_env_get_frame_vel_tables",
     "parc_env_profile_step", "parc_env_last_dynamics_ms", "parc_env_dynamics_kernel", "parc_env_set_kernel_timing", "parc_env_get_kernel_timing", "parc_env_record_bind", "parc_env_record_frame", "parc_env_set_episode_length", "parc_td_lambda_return", "parc_normalize_record", "parc_env_bind_action", "parc_env_get_buffers", "parc_env_step_reset_graph",
     "parc_test_quat_op", "parc_build_flags", "parc_env_set_never_done", "parc_env_dynamics_timeouts", "parc_env_dynamics_manifold_drops", "parc_env_describe", "parc_env_get_kernel_timing_samples", "parc_env_health_words", "parc_gather_rows",
-    "parc_env_post_kernel", "parc_env_render",
+    "parc_env_post_kernel", "parc_env_render", "parc_env_render_scene",
 ]
 
 # parc_test_quat_op selectors (include/parc_env.h)

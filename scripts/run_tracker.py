@@ -7,7 +7,8 @@
         --out_model_file output/model.pt --int_output_dir output/checkpoints --log_file output/log.txt
 
 Headless viewer: ``--visualize true`` writes the camera env's frames as PNG to ``--frame_dir`` (default output/frames), one every
-``--render_every`` steps (default 1), ``--render_size WxH`` (default 320x240).
+``--render_every`` steps (default 1), ``--render_size WxH`` (default 320x240); ``--render_scene true`` draws every env's characters
+in those frames (the reference's viewer), seen from the camera env.
 
 Multi-GPU (new): launch with ``python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ...``;
 every rank owns ``num_envs`` envs (global env index = rank * num_envs + i) and gradients are all-reduced over RCCL.
@@ -77,7 +78,7 @@ def run(args):
         from parc_amd.util.frame_writer import FrameWriter
         w, h = (int(v) for v in args.parse_string("render_size", "320x240").lower().split("x"))
         frames = FrameWriter(args.parse_string("frame_dir", "output/frames"))
-        env.set_frame_sink(frames, every=args.parse_int("render_every", 1), size=(w, h))
+        env.set_frame_sink(frames, every=args.parse_int("render_every", 1), size=(w, h), scene=args.parse_bool("render_scene", False))
     agent = agent_builder.build_agent(path_loader.resolve_path(args.parse_string("agent_config")), env, device)
     if model_file != "":
         agent.load(path_loader.resolve_path(model_file))

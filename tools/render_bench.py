@@ -6,6 +6,9 @@
 (1) k_render per call at 1 / 16 / 64 envs x 320x240, shadows on / off: device events around `iters` back-to-back calls (take
     rocprofv3 --kernel-trace --stats of the same run for the kernel-only figure); (2) env steps per second of a step + reset loop of
     `--envs` envs with visualize off, then on (camera env -> FrameWriter -> PNG in --out).  Prints one JSON line.
+(3) --scene: parc_env_render_scene (all seven launches) per call at 320x240 with every env drawn, at 64 / 4096 / 65536 envs
+    (--scene-envs), shadows on / off, with the default track camera of env 0 and with a still camera looking at an empty corner of
+    the world (few characters in view); and the roll-out rate with scene frames after every step next to camera-only frames.
 """
 import argparse
 import json
@@ -37,12 +40,52 @@ def time_render(env, k, shadows, iters, W=320, H=240):
     return a.elapsed_time(b) / iters
 
 
-def rollout(visualize, envs, steps, out_dir):
+def time_scene(env, shadows, iters, camera=None, W=320, H=240):
+    for _ in range(3):
+        env.render_scene(0, None, W, H, camera=camera, shadows=shadows)
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        env.render_scene(0, None, W, H, camera=camera, shadows=shadows)
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def scene_timings(sizes, iters):
+    out = {}
+    for n in sizes:
+        env = env_builder.build_env(CFG, n, "cuda:0", False)
+        env.reset()
+        for _ in range(3):
+            env.step(env._char_dof_pos.clone())
+            env.reset_done()
+        eo = env._scene.env_offsets[0]
+        # still camera over the world's -x, -y corner beyond every env origin: a handful of characters in view at most
+        lo = env._scene.env_offsets.min(axis=0)
+        corner = {"mode": "still", "eye": tuple(float(v) for v in (lo + [-30.0, -30.0, 8.0] - eo)),
+                  "target": tuple(float(v) for v in (lo + [-20.0, -20.0, 0.0] - eo))}
+        _, _, _, em = env.render_scene(0, None, 320, 240, camera=corner, env_map=True)
+        _, _, _, em_t = env.render_scene(0, None, 320, 240, env_map=True)
+        torch.cuda.synchronize()
+        row = {"envs_in_view_track": int(torch.unique(em_t).numel() - 1), "envs_in_view_corner": int(torch.unique(em).numel() - 1)}
+        for sh in (True, False):
+            tag = "shadows" if sh else "noshadows"
+            row["track_" + tag] = round(time_scene(env, sh, iters), 4)
+            row["corner_" + tag] = round(time_scene(env, sh, iters, corner), 4)
+        out["n%d" % n] = row
+        del env
+        torch.cuda.empty_cache()
+    return out
+
+
+def rollout(visualize, envs, steps, out_dir, scene=False):
     env = env_builder.build_env(CFG, envs, "cuda:0", visualize)
     fw = None
     if visualize:
         fw = FrameWriter(out_dir)
-        env.set_frame_sink(fw, every=1, size=(320, 240))
+        env.set_frame_sink(fw, every=1, size=(320, 240), scene=scene)
     env.reset()
     for _ in range(10):
         env.step_and_reset_done(env._char_dof_pos.clone())
@@ -66,7 +109,15 @@ def main():
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--out", default=os.path.join(tempfile.gettempdir(), "parc_render_bench_frames"))
     ap.add_argument("--render-only", action="store_true")
+    ap.add_argument("--scene", action="store_true", help="only the scene render timings and the scene roll-out")
+    ap.add_argument("--scene-envs", default="64,4096,65536")
     a = ap.parse_args()
+    if a.scene:
+        out = {"render_scene_ms_320x240": scene_timings([int(v) for v in a.scene_envs.split(",")], a.iters)}
+        out["rollout_visualize_camera_env"] = rollout(True, a.envs, a.steps, a.out)
+        out["rollout_visualize_scene"] = rollout(True, a.envs, a.steps, a.out, scene=True)
+        print(json.dumps(out))
+        return
     env = env_builder.build_env(CFG, 64, "cuda:0", False)
     env.reset()
     for _ in range(3):
