@@ -417,6 +417,67 @@ int parc_env_render(ParcEnv *env, const ParcRenderParams *p, const int64_t *env_
 int parc_env_render_scene(ParcEnv *env, const ParcRenderParams *p, int32_t camera_env, const int64_t *env_ids_dev, int32_t n,
                           uint8_t *rgba_dev, float *depth_dev, uint8_t *id_dev, int32_t *env_map_dev, void *stream);
 
+/* Kinematic motion optimiser (the reference's motion_optimization.py: motion_contact_optimization with the loss
+ * motion_terrain_contact_loss_localized, :426-656, and compute_approx_body_constraints' point refinement, :124-146) for B clips at once.
+ * Its own handle: nothing is shared with a ParcEnv.  Per frame the parameters are root_pos[3] | root exp map[3] | joint dofs[dof_size]
+ * (PARC_MOPT_NP(dof_size) floats); every array below is row-major over the clips' frames concatenated in clip order.
+ * Every iteration is one host-driven sequence of short launches; results are deterministic and do not depend on
+ * which other clips are in the batch.  Terms follow the reference's LossType order: root pos, root rot, joint rot, smoothness,
+ * penetration, contact, sliding, body constraints, jerk. */
+#define PARC_MOPT_NUM_TERMS 9
+#define PARC_MOPT_MAX_POINTS 512
+#define PARC_MOPT_NP(D) (6 + (D))
+typedef struct ParcMotionOpt ParcMotionOpt;
+typedef struct {
+    uint32_t struct_size;                    /* sizeof(ParcMotionOptParams) */
+    int32_t device;
+    ParcCharModel model;                     /* the tables parc_env_create takes (fk_paths unused) */
+    int32_t num_points;                      /* sample points per frame, [1, PARC_MOPT_MAX_POINTS]; contiguous per body, bodies in order */
+    const float *points_host;                /* [num_points][3] body-local */
+    const int32_t *point_body_host;          /* [num_points] */
+    int32_t geom0_type[PARC_MAX_BODIES];     /* first geom of each body (the body-constraint shape): 0 box, 1 sphere, 2 capsule, -1 none */
+    float geom0_offset[PARC_MAX_BODIES][3];
+    float geom0_radius[PARC_MAX_BODIES];     /* sphere: radius; box: 1.25 |half extents| (motion_optimization.py:589-602) */
+    int32_t contact_body_id[PARC_MAX_BODIES];/* column of the contacts array of each body, -1 when it is not a contact body */
+    float weights[PARC_MOPT_NUM_TERMS];      /* w_root_pos .. w_jerk; w_contact = 0 / w_sliding = 0 switch the term off (reported as 0) */
+    float max_jerk;                          /* scaled by (1/30)^3 on the device, as the reference does */
+    float step_size;                         /* Adam learning rate; betas 0.9 / 0.999, eps 1e-8 (torch.optim.Adam defaults) */
+} ParcMotionOptParams;
+typedef struct {
+    int32_t num_clips;
+    const int64_t *frame_off_host;           /* [num_clips + 1] */
+    const int64_t *hf_off_host;              /* [num_clips + 1] offsets into hf_host */
+    const int64_t *cons_off_host;            /* [num_clips + 1] offsets into the constraint arrays */
+    const int32_t *hf_dims_host;             /* [num_clips][2] */
+    const float *hf_geom_host;               /* [num_clips][4] min_x, min_y, dx, dy */
+    const float *hf_host;                    /* cells, x-major per clip */
+    const float *root_pos_host, *root_rot_host, *joint_rot_host, *contacts_host; /* [F][3], [F][4] xyzw, [F][B-1][4], [F][B] */
+    const int32_t *cons_body_host;           /* [C] */
+    const int32_t *cons_range_host;          /* [C][2] first / last frame */
+    const float *cons_point_host;            /* [C][3] */
+} ParcMotionOptClips;
+int parc_mopt_create(const ParcMotionOptParams *p, ParcMotionOpt **out);
+void parc_mopt_destroy(ParcMotionOpt *h);
+/* Uploads the clips and sets the iterate to the source (root exp map = quat_to_exp_map, dofs = rot_to_dof); resets Adam. */
+int parc_mopt_set_clips(ParcMotionOpt *h, const ParcMotionOptClips *c);
+/* Replaces the constraint points (same count as set_clips gave), e.g. after parc_mopt_build_constraints. */
+int parc_mopt_set_constraint_points(ParcMotionOpt *h, const float *cons_point_host);
+int parc_mopt_set_params(ParcMotionOpt *h, const float *params_host);      /* [F][NP]; resets Adam */
+int parc_mopt_get_params(ParcMotionOpt *h, float *params_host);
+/* Loss terms [num_clips][9] and the gradient of the weighted total [F][NP] at the current iterate (either may be NULL). */
+int parc_mopt_loss_and_grad(ParcMotionOpt *h, float *terms_host, float *grad_host);
+/* n_iters Adam iterations; terms_host (may be NULL) receives [n_iters][num_clips][9], the terms each iteration's gradient came from. */
+int parc_mopt_step(ParcMotionOpt *h, int32_t n_iters, float *terms_host);
+/* The optimised frames: root_pos [F][3], root_rot [F][4] (exp_map_to_quat), joint_rot [F][B-1][4] (dof_to_rot). */
+int parc_mopt_get_frames(ParcMotionOpt *h, float *root_pos_host, float *root_rot_host, float *joint_rot_host);
+/* FK of the SOURCE frames: body_pos [F][B][3], body_rot [F][B][4]. */
+int parc_mopt_get_source_body(ParcMotionOpt *h, float *body_pos_host, float *body_rot_host);
+/* compute_approx_body_constraints' refinement: n points, each on the full terrain of clip clip_host[i], `steps` SGD steps of
+ * lr on sdf^2 (non-inverted, base_z = min(hf) - 10), one lane per point and one launch per step; points updated in place. */
+int parc_mopt_build_constraints(ParcMotionOpt *h, int32_t n, const int32_t *clip_host, float *points_host, int32_t steps, float lr);
+/* Per-kernel device time (hipEvents) of the last parc_mopt_step call, ms per iteration: fk, patch, points, grad, reduce, adam. */
+int parc_mopt_kernel_times(ParcMotionOpt *h, float *ms6);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2965,3 +2965,5 @@ extern "C" int parc_env_profile_step(ParcEnv *e, const float *action_dev, void *
     e->last_dyn_ms = (float)(dyn / iters);
     return PARC_OK;
 }
+
+#include "parc_motion_opt.hpp"   // parc_mopt_*: the batched kinematic motion optimiser (its own handle; uses parc_math.hpp and fail())

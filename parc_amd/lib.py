@@ -79,6 +79,21 @@ class ParcRenderParams(C.Structure):
                 ("draw_ref", C.c_int32), ("shadows", C.c_int32), ("debug_visuals", C.c_int32)]
 
 
+class ParcMotionOptParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("model", ParcCharModel), ("num_points", C.c_int32),
+                ("points_host", f32p), ("point_body_host", i32p), ("geom0_type", C.c_int32 * MAX_BODIES),
+                ("geom0_offset", (C.c_float * 3) * MAX_BODIES), ("geom0_radius", C.c_float * MAX_BODIES),
+                ("contact_body_id", C.c_int32 * MAX_BODIES), ("weights", C.c_float * 9), ("max_jerk", C.c_float),
+                ("step_size", C.c_float)]
+
+
+class ParcMotionOptClips(C.Structure):
+    _fields_ = [("num_clips", C.c_int32), ("frame_off_host", i64p), ("hf_off_host", i64p), ("cons_off_host", i64p),
+                ("hf_dims_host", i32p), ("hf_geom_host", f32p), ("hf_host", f32p), ("root_pos_host", f32p), ("root_rot_host", f32p),
+                ("joint_rot_host", f32p), ("contacts_host", f32p), ("cons_body_host", i32p), ("cons_range_host", i32p),
+                ("cons_point_host", f32p)]
+
+
 BUFFER_FIELDS = [
     ("char_root_pos", "f"), ("char_root_rot", "f"), ("char_root_vel", "f"), ("char_root_ang_vel", "f"),
     ("char_dof_pos", "f"), ("char_dof_vel", "f"), ("char_body_pos", "f"), ("contact_forces", "f"),
@@ -171,6 +186,19 @@ def load():
     lib.parc_env_post_kernel.restype = C.c_char_p
     lib.parc_env_render.argtypes = [vp, C.POINTER(ParcRenderParams), vp, C.c_int32, vp, vp, vp, vp]
     lib.parc_env_render_scene.argtypes = [vp, C.POINTER(ParcRenderParams), C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
+    lib.parc_mopt_create.argtypes = [C.POINTER(ParcMotionOptParams), C.POINTER(vp)]
+    lib.parc_mopt_destroy.argtypes = [vp]
+    lib.parc_mopt_destroy.restype = None
+    lib.parc_mopt_set_clips.argtypes = [vp, C.POINTER(ParcMotionOptClips)]
+    lib.parc_mopt_set_constraint_points.argtypes = [vp, f32p]
+    lib.parc_mopt_set_params.argtypes = [vp, f32p]
+    lib.parc_mopt_get_params.argtypes = [vp, f32p]
+    lib.parc_mopt_loss_and_grad.argtypes = [vp, f32p, f32p]
+    lib.parc_mopt_step.argtypes = [vp, C.c_int32, f32p]
+    lib.parc_mopt_get_frames.argtypes = [vp, f32p, f32p, f32p]
+    lib.parc_mopt_get_source_body.argtypes = [vp, f32p, f32p]
+    lib.parc_mopt_build_constraints.argtypes = [vp, C.c_int32, i32p, f32p, C.c_int32, C.c_float]
+    lib.parc_mopt_kernel_times.argtypes = [vp, f32p]
     _lib = lib
     return lib
 
@@ -184,6 +212,9 @@ EXPORTED_SYMBOLS = [
     "parc_env_profile_step", "parc_env_last_dynamics_ms", "parc_env_dynamics_kernel", "parc_env_set_kernel_timing", "parc_env_get_kernel_timing", "parc_env_record_bind", "parc_env_record_frame", "parc_env_set_episode_length", "parc_td_lambda_return", "parc_normalize_record", "parc_env_bind_action", "parc_env_get_buffers", "parc_env_step_reset_graph",
     "parc_test_quat_op", "parc_build_flags", "parc_env_set_never_done", "parc_env_dynamics_timeouts", "parc_env_dynamics_manifold_drops", "parc_env_describe", "parc_env_get_kernel_timing_samples", "parc_env_health_words", "parc_gather_rows",
     "parc_env_post_kernel", "parc_env_render", "parc_env_render_scene",
+    "parc_mopt_create", "parc_mopt_destroy", "parc_mopt_set_clips", "parc_mopt_set_constraint_points", "parc_mopt_set_params",
+    "parc_mopt_get_params", "parc_mopt_loss_and_grad", "parc_mopt_step", "parc_mopt_get_frames", "parc_mopt_get_source_body",
+    "parc_mopt_build_constraints", "parc_mopt_kernel_times",
 ]
 
 # parc_test_quat_op selectors (include/parc_env.h)

@@ -1,0 +1,435 @@
+"""Batched kinematic motion optimiser (the reference's ``motion_synthesis/motion_opt/motion_optimization.py``).
+
+The reference runs Adam on one clip at a time with autograd.  Here B clips of any lengths, each on its own terrain, are packed into
+flat device arrays and one host-driven launch sequence per iteration evaluates the whole loss of
+``motion_terrain_contact_loss_localized`` with its analytic gradient and applies a fused Adam step
+(``parc_amd/csrc/parc_motion_opt.hpp``).
+
+Host side (this module): the point sampler (``geom_util.get_char_point_samples``), the parameter initialisation
+(``motion_contact_optimization``: root exp map + joint dofs from the source quaternions), the frame stride of
+``run_optimize_motions.py``, the packing with 64-bit per-clip offsets and the contact-run grouping of
+``compute_approx_body_constraints``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import enum
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+
+from parc_amd.char_model import CharModel, GeomType
+
+
+class LossType(enum.Enum):  # motion_optimization.py:15-25 (LOOPING_LOSS is never computed)
+    ROOT_POS_LOSS = 0
+    ROOT_ROT_LOSS = 1
+    JOINT_ROT_LOSS = 2
+    SMOOTHNESS_LOSS = 3
+    PENETRATION_LOSS = 4
+    CONTACT_LOSS = 5
+    SLIDING_LOSS = 6
+    BODY_CONSTRAINT_LOSS = 7
+    JERK_LOSS = 8
+
+
+NUM_TERMS = 9
+# order of ParcMotionOptParams.weights: the LossType order
+WEIGHT_KEYS = ("w_root_pos", "w_root_rot", "w_joint_rot", "w_smoothness", "w_penetration", "w_contact", "w_sliding",
+               "w_body_constraints", "w_jerk")
+SAMPLER_KEYS = ("sphere_num_subdivisions", "box_num_slices", "box_dim_x", "box_dim_y", "capsule_num_circle_points",
+                "capsule_num_sphere_subdivisions", "capsule_num_cylinder_slices")
+MAX_POINTS = 512          # PARC_MOPT_MAX_POINTS
+CONSTRAINT_BODIES = ("left_foot", "right_foot", "left_hand", "right_hand")  # compute_approx_body_constraints order
+CONTACT_THRESHOLD = 0.9
+CONSTRAINT_SGD_STEPS = 1000
+CONSTRAINT_SGD_LR = 0.01
+
+
+def icosahedron_vertices() -> np.ndarray:
+    """The 12 vertices of trimesh's ``icosphere(subdivisions=0)``: the golden-ratio icosahedron, normalised, in its vertex order."""
+    t = (1.0 + 5.0 ** 0.5) / 2.0
+    v = np.array([[-1, t, 0], [1, t, 0], [-1, -t, 0], [1, -t, 0], [0, -1, t], [0, 1, t], [0, -1, -t], [0, 1, -t],
+                  [t, 0, -1], [t, 0, 1], [-t, 0, -1], [-t, 0, 1]], np.float64)
+    return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+def _linspace01(n):
+    return np.linspace(0.0, 1.0, n, dtype=np.float32)
+
+
+def _quat_rotate(q, v):  # torch_util.py:62-67
+    qv, qw = q[..., :3], q[..., 3:]
+    t = 2 * np.cross(qv, v)
+    return v + qw * t + np.cross(qv, t)
+
+
+def char_point_samples(char_model: CharModel, sphere_num_subdivisions=0, box_num_slices=2, box_dim_x=3, box_dim_y=6,
+                       capsule_num_circle_points=4, capsule_num_sphere_subdivisions=0, capsule_num_cylinder_slices=4):
+    """``geom_util.get_char_point_samples`` (geom_util.py:795-874).  Returns (per-body [n_b, 3] arrays, flat [P, 3], body index [P]).
+
+    Boxes: slice-major, the bottom slice first, x-major within a slice.  Capsules: ``capsule_num_circle_points`` around the axis ×
+    ``capsule_num_cylinder_slices`` along it (circle-major, no hemisphere points), rotated by ``acos(dot(axis, fromto))`` about
+    ``cross(z, fromto)`` (the reference's angle: pi/2 for every capsule not along z, ``acos`` of the unnormalised z component for one
+    along z).  Spheres: the 12 icosahedron vertices; other subdivision levels are refused."""
+    if int(sphere_num_subdivisions) != 0 or int(capsule_num_sphere_subdivisions) != 0:
+        raise ValueError("only sphere_num_subdivisions = 0 and capsule_num_sphere_subdivisions = 0 (the icosahedron) are supported")
+    for k, v in (("box_num_slices", box_num_slices), ("box_dim_x", box_dim_x), ("box_dim_y", box_dim_y),
+                 ("capsule_num_circle_points", capsule_num_circle_points), ("capsule_num_cylinder_slices", capsule_num_cylinder_slices)):
+        if int(v) < 1:
+            raise ValueError(f"{k} must be >= 1, got {v}")
+    out = []
+    for b in range(char_model.get_num_bodies()):
+        pts = []
+        for g in char_model._geoms[b]:
+            if g.shape == GeomType.SPHERE:
+                r = np.float32(g.size[0])
+                pts.append((icosahedron_vertices() * r).astype(np.float32) + g.pos.astype(np.float32))
+            elif g.shape == GeomType.BOX:
+                h = g.size.astype(np.float32)
+                z = _linspace01(box_num_slices) * h[2] * np.float32(2) - h[2]
+                x = _linspace01(box_dim_x) * h[0] * np.float32(2) - h[0]
+                y = _linspace01(box_dim_y) * h[1] * np.float32(2) - h[1]
+                xx, yy = np.meshgrid(x, y, indexing="ij")
+                n = box_dim_x * box_dim_y
+                p = np.stack([np.broadcast_to(xx.reshape(-1)[None], (box_num_slices, n)),
+                              np.broadcast_to(yy.reshape(-1)[None], (box_num_slices, n)),
+                              np.broadcast_to(z[:, None], (box_num_slices, n))], axis=-1).reshape(-1, 3)
+                pts.append(p + g.pos.astype(np.float32))
+            elif g.shape == GeomType.CAPSULE:
+                d = (g.pos2 - g.pos).astype(np.float32)
+                offset = g.pos.astype(np.float32) + d / np.float32(2)
+                zax = np.array([0, 0, 1], np.float32)
+                axis = np.cross(zax, d)
+                axis = zax if np.linalg.norm(axis) < 1e-5 else (axis / np.linalg.norm(axis)).astype(np.float32)
+                angle = np.float32(np.arccos(np.float32(np.dot(axis, d))))
+                s, c = np.sin(angle / 2), np.cos(angle / 2)
+                rot = np.concatenate([axis / max(np.linalg.norm(axis), 1e-9) * s, [c]]).astype(np.float32)
+                rot = rot / max(np.linalg.norm(rot), 1e-9)
+                hgt = np.float32(np.linalg.norm(d))
+                r = np.float32(g.size[0])
+                zs = _linspace01(capsule_num_cylinder_slices) * hgt - hgt / np.float32(2)
+                th = np.linspace(0, 2 * np.pi, capsule_num_circle_points + 1, dtype=np.float32)[:-1]
+                nc, ns = capsule_num_circle_points, capsule_num_cylinder_slices
+                p = np.stack([np.broadcast_to((r * np.cos(th))[:, None], (nc, ns)),
+                              np.broadcast_to((r * np.sin(th))[:, None], (nc, ns)),
+                              np.broadcast_to(zs[None, :], (nc, ns))], axis=-1).reshape(-1, 3).astype(np.float32)
+                pts.append(_quat_rotate(rot[None], p).astype(np.float32) + offset)
+        if not pts:   # the reference samples ONE point at the origin of a body without geoms (geom_util.py:864-866)
+            pts.append(np.zeros((1, 3), np.float32))
+        out.append(np.ascontiguousarray(np.concatenate(pts), np.float32))
+    flat = np.ascontiguousarray(np.concatenate(out), np.float32)
+    body = np.concatenate([np.full(p.shape[0], b, np.int32) for b, p in enumerate(out)])
+    if flat.shape[0] > MAX_POINTS:
+        raise ValueError(f"{flat.shape[0]} sample points per frame; at most {MAX_POINTS} are supported")
+    return out, flat, body
+
+
+def contact_runs(flags: np.ndarray, threshold: float = CONTACT_THRESHOLD):
+    """``extract_consecutive_trues`` of ``flags > threshold`` (motion_optimization.py:74-104): runs of consecutive frames, as
+    (first, last) pairs.  Reproduces the reference's quirk: a trailing run of ONE frame is dropped."""
+    idx = np.nonzero(np.asarray(flags).reshape(-1) > threshold)[0]
+    if idx.size == 0:
+        return []
+    breaks = [0] + (np.nonzero(np.diff(idx) > 1)[0] + 1).tolist()
+    runs = [idx[breaks[i]:breaks[i + 1]] for i in range(len(breaks) - 1)]
+    if breaks[-1] < idx.size - 1:
+        runs.append(idx[breaks[-1]:])
+    return [(int(r[0]), int(r[-1])) for r in runs]
+
+
+def stride_constraint_range(start: int, end: int, stride: int):
+    """run_optimize_motions.py: constraints are found at full rate, then ``ceil(start / stride)`` / ``end // stride``."""
+    return int(-(-start // stride)), int(end // stride)
+
+
+@dataclass
+class OptClip:
+    """One source clip on its terrain (quaternions xyzw; ``contacts`` per body)."""
+    root_pos: np.ndarray
+    root_rot: np.ndarray
+    joint_rot: np.ndarray
+    contacts: np.ndarray
+    hf: np.ndarray
+    min_point: np.ndarray
+    dx: float
+    fps: int = 30
+    name: str = ""
+    # body constraints: body index, first / last frame, point (filled by MotionOptimizer.build_constraints or by the caller)
+    cons_body: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    cons_start: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    cons_end: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))
+    cons_point: np.ndarray = field(default_factory=lambda: np.zeros((0, 3), np.float32))
+    # the terrain's per-cell augmentation bounds [X, Y, 2] (ms-file terrain_data.hf_maxmin): not used by the loss, carried to the output
+    hf_maxmin: Optional[np.ndarray] = None
+
+    @property
+    def num_frames(self):
+        return int(self.root_pos.shape[0])
+
+    def strided(self, stride: int) -> "OptClip":
+        """``src_frames[::frame_stride]``, fps ``fps // stride`` and the constraint frame ranges mapped as the reference does."""
+        if stride < 1:
+            raise ValueError("frame_stride must be >= 1")
+        cs, ce = [], []
+        for s, e in zip(self.cons_start, self.cons_end):
+            a, b = stride_constraint_range(int(s), int(e), stride)
+            cs.append(a); ce.append(b)
+        return OptClip(self.root_pos[::stride].copy(), self.root_rot[::stride].copy(), self.joint_rot[::stride].copy(),
+                       self.contacts[::stride].copy(), self.hf, self.min_point, self.dx, self.fps // stride, self.name,
+                       self.cons_body.copy(), np.array(cs, np.int32), np.array(ce, np.int32), self.cons_point.copy(), self.hf_maxmin)
+
+
+def clip_from_ms(path: str) -> OptClip:
+    from parc_amd import ms_file
+    d = ms_file.load_ms_file(path, load_misc=False)
+    m, t = d.motion_data, d.terrain_data
+    if m is None or t is None:
+        raise ValueError(f"{path}: the optimiser needs motion_data and terrain_data")
+    n = m.root_pos.shape[0]
+    ct = np.zeros((n, m.joint_rot.shape[1] + 1), np.float32) if m.body_contacts is None else np.asarray(m.body_contacts, np.float32)
+    import os
+    return OptClip(np.asarray(m.root_pos, np.float32), np.asarray(m.root_rot, np.float32), np.asarray(m.joint_rot, np.float32), ct,
+                   np.asarray(t.hf, np.float32), np.asarray(t.min_point, np.float32), float(t.dx), int(m.fps),
+                   os.path.basename(os.path.splitext(path)[0]), hf_maxmin=np.asarray(t.hf_maxmin, np.float32))
+
+
+def pack_clips(clips: Sequence[OptClip], num_bodies: int, dof_size: int):
+    """Flat arrays + 64-bit per-clip offsets (frames, heightfield cells, constraints) for ``parc_mopt_set_clips``."""
+    if len(clips) == 0:
+        raise ValueError("no clips")
+    J = num_bodies - 1
+    nf = np.array([c.num_frames for c in clips], np.int64)
+    for i, c in enumerate(clips):
+        if c.num_frames < 1:
+            raise ValueError(f"clip {i}: zero frames")
+        if c.root_pos.shape != (c.num_frames, 3) or c.root_rot.shape != (c.num_frames, 4) or \
+                c.joint_rot.shape != (c.num_frames, J, 4) or c.contacts.shape != (c.num_frames, num_bodies):
+            raise ValueError(f"clip {i}: bad shapes root_pos {c.root_pos.shape} root_rot {c.root_rot.shape} "
+                             f"joint_rot {c.joint_rot.shape} contacts {c.contacts.shape} (expected J={J}, B={num_bodies})")
+        if c.hf.ndim != 2 or min(c.hf.shape) < 1:
+            raise ValueError(f"clip {i}: bad heightfield shape {c.hf.shape}")
+        if not (len(c.cons_body) == len(c.cons_start) == len(c.cons_end) == c.cons_point.reshape(-1, 3).shape[0]):
+            raise ValueError(f"clip {i}: constraint arrays differ in length")
+    frame_off = np.zeros(len(clips) + 1, np.int64); frame_off[1:] = np.cumsum(nf)
+    hf_off = np.zeros(len(clips) + 1, np.int64); hf_off[1:] = np.cumsum([c.hf.size for c in clips])
+    ncons = np.array([len(c.cons_body) for c in clips], np.int64)
+    cons_off = np.zeros(len(clips) + 1, np.int64); cons_off[1:] = np.cumsum(ncons)
+    f32 = lambda xs: np.ascontiguousarray(np.concatenate(xs), np.float32)  # noqa: E731
+    return dict(
+        frame_off=frame_off, hf_off=hf_off, cons_off=cons_off,
+        hf_dims=np.ascontiguousarray([[c.hf.shape[0], c.hf.shape[1]] for c in clips], np.int32),
+        hf_geom=np.ascontiguousarray([[c.min_point[0], c.min_point[1], c.dx, c.dx] for c in clips], np.float32),
+        root_pos=f32([c.root_pos for c in clips]), root_rot=f32([c.root_rot for c in clips]),
+        joint_rot=f32([c.joint_rot.reshape(-1, J * 4) for c in clips]), contacts=f32([c.contacts for c in clips]),
+        hf=f32([c.hf.reshape(-1) for c in clips]),
+        cons_body=np.ascontiguousarray(np.concatenate([c.cons_body for c in clips]).astype(np.int32)),
+        cons_range=np.ascontiguousarray(np.stack([np.concatenate([c.cons_start for c in clips]),
+                                                  np.concatenate([c.cons_end for c in clips])], -1).astype(np.int32).reshape(-1, 2)),
+        cons_point=f32([c.cons_point.reshape(-1, 3) for c in clips]).reshape(-1, 3))
+
+
+def optimizer_params(char_model: CharModel, flat_points, point_body, weights: Dict[str, float], max_jerk: float, step_size: float,
+                     device: int = 0):
+    """``ParcMotionOptParams`` for the character, the sample points and the loss weights (keys ``WEIGHT_KEYS``)."""
+    from parc_amd import lib as L
+    p = L.ParcMotionOptParams()
+    p.struct_size = C.sizeof(L.ParcMotionOptParams)
+    p.device = int(device)
+    p.model = L.make_char_model(char_model)
+    pts = np.ascontiguousarray(flat_points, np.float32)
+    body = np.ascontiguousarray(point_body, np.int32)
+    p.num_points = int(pts.shape[0])
+    p.points_host = L.np_f32p(pts)
+    p.point_body_host = L.np_i32p(body)
+    p._keep = (pts, body)
+    for b in range(char_model.get_num_bodies()):
+        geoms = char_model._geoms[b]
+        p.geom0_type[b] = -1
+        if geoms:
+            g = geoms[0]
+            p.geom0_type[b] = int(g.shape)
+            for k in range(3):
+                p.geom0_offset[b][k] = float(g.pos[k])
+            if g.shape == GeomType.SPHERE:
+                p.geom0_radius[b] = float(np.float32(g.size[0]))
+            elif g.shape == GeomType.BOX:   # torch.norm(dims) * 1.25 in fp32
+                p.geom0_radius[b] = float(np.float32(np.linalg.norm(g.size.astype(np.float32))) * np.float32(1.25))
+        name = char_model.get_body_name(b)
+        p.contact_body_id[b] = char_model._contact_body_names.index(name) if name in char_model._contact_body_names else -1
+    missing = [k for k in WEIGHT_KEYS if k not in weights]
+    if missing:
+        raise ValueError(f"missing loss weights: {missing}")
+    for t, k in enumerate(WEIGHT_KEYS):
+        p.weights[t] = float(weights[k])
+    p.max_jerk = float(max_jerk)
+    p.step_size = float(step_size)
+    return p
+
+
+class MotionOptimizer:
+    """``MotionOptimizer(char_file, device, cfg).optimize(clips, iters, log_every)``: the reference's ``motion_contact_optimization``
+    for a whole batch of clips.  ``cfg`` holds the loss weights (``WEIGHT_KEYS``), ``max_jerk``, ``step_size`` and optionally
+    ``char_point_samples`` (``SAMPLER_KEYS``; the stage-2 sampler when absent)."""
+
+    def __init__(self, char_file: str, device="cuda:0", cfg: Optional[dict] = None):
+        import torch  # noqa: F401  (one HIP runtime: torch's, loaded before the library)
+        from parc_amd import lib as L
+        cfg = dict(cfg or {})
+        self._L = L
+        self._lib = L.load()
+        self.char_model = CharModel(char_file)
+        sampler = dict(sphere_num_subdivisions=0, box_num_slices=2, box_dim_x=3, box_dim_y=6, capsule_num_circle_points=4,
+                       capsule_num_sphere_subdivisions=0, capsule_num_cylinder_slices=4)
+        sampler.update(cfg.get("char_point_samples") or {})
+        unknown = set(sampler) - set(SAMPLER_KEYS)
+        if unknown:
+            raise ValueError(f"unknown char_point_samples keys: {sorted(unknown)}")
+        self.body_points, self.points, self.point_body = char_point_samples(self.char_model, **sampler)
+        self.cfg = cfg
+        dev = str(device)
+        self.device_index = int(dev.split(":")[1]) if ":" in dev else 0
+        params = optimizer_params(self.char_model, self.points, self.point_body, cfg, float(cfg.get("max_jerk", 1000.0)),
+                                  float(cfg.get("step_size", 1e-3)), self.device_index)
+        h = C.c_void_p()
+        L.check(self._lib.parc_mopt_create(C.byref(params), C.byref(h)))
+        self._h = h
+        self.B = self.char_model.get_num_bodies()
+        self.D = self.char_model.get_dof_size()
+        self.NP = 6 + self.D
+        self._clips: List[OptClip] = []
+        self._packed = None
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            self._lib.parc_mopt_destroy(h)
+            self._h = None
+
+    # ------------------------------------------------------------------ batch
+    def set_clips(self, clips: Sequence[OptClip]):
+        L = self._L
+        pk = pack_clips(clips, self.B, self.D)
+        st = L.ParcMotionOptClips()
+        st.num_clips = len(clips)
+        i64 = lambda a: a.ctypes.data_as(L.i64p)  # noqa: E731
+        st.frame_off_host, st.hf_off_host, st.cons_off_host = i64(pk["frame_off"]), i64(pk["hf_off"]), i64(pk["cons_off"])
+        st.hf_dims_host, st.hf_geom_host, st.hf_host = L.np_i32p(pk["hf_dims"]), L.np_f32p(pk["hf_geom"]), L.np_f32p(pk["hf"])
+        st.root_pos_host, st.root_rot_host = L.np_f32p(pk["root_pos"]), L.np_f32p(pk["root_rot"])
+        st.joint_rot_host, st.contacts_host = L.np_f32p(pk["joint_rot"]), L.np_f32p(pk["contacts"])
+        st.cons_body_host, st.cons_range_host = L.np_i32p(pk["cons_body"]), L.np_i32p(pk["cons_range"])
+        st.cons_point_host = L.np_f32p(pk["cons_point"])
+        L.check(self._lib.parc_mopt_set_clips(self._h, C.byref(st)))
+        self._clips = list(clips)
+        self._packed = pk
+        return pk
+
+    @property
+    def num_frames_total(self):
+        return 0 if self._packed is None else int(self._packed["frame_off"][-1])
+
+    def _split(self, a):
+        off = self._packed["frame_off"]
+        return [a[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+
+    def get_params(self) -> np.ndarray:
+        out = np.zeros((self.num_frames_total, self.NP), np.float32)
+        self._L.check(self._lib.parc_mopt_get_params(self._h, self._L.np_f32p(out)))
+        return out
+
+    def set_params(self, params: np.ndarray):
+        p = np.ascontiguousarray(params, np.float32)
+        if p.shape != (self.num_frames_total, self.NP):
+            raise ValueError(f"params must be [{self.num_frames_total}, {self.NP}], got {p.shape}")
+        self._L.check(self._lib.parc_mopt_set_params(self._h, self._L.np_f32p(p)))
+
+    def loss_and_grad(self):
+        """(terms [num_clips, 9], gradient of the weighted total [F, NP]) at the current iterate."""
+        terms = np.zeros((len(self._clips), NUM_TERMS), np.float32)
+        grad = np.zeros((self.num_frames_total, self.NP), np.float32)
+        self._L.check(self._lib.parc_mopt_loss_and_grad(self._h, self._L.np_f32p(terms), self._L.np_f32p(grad)))
+        return terms, grad
+
+    def step(self, n_iters: int):
+        """n Adam iterations; returns the terms [n, num_clips, 9] each iteration's gradient came from."""
+        terms = np.zeros((max(int(n_iters), 0), len(self._clips), NUM_TERMS), np.float32)
+        self._L.check(self._lib.parc_mopt_step(self._h, int(n_iters), self._L.np_f32p(terms) if n_iters > 0 else None))
+        return terms
+
+    def kernel_times(self):
+        out = np.zeros(6, np.float32)
+        self._L.check(self._lib.parc_mopt_kernel_times(self._h, self._L.np_f32p(out)))
+        return dict(zip(("fk", "patch", "points", "grad", "reduce", "adam"), out.tolist()))
+
+    def get_frames(self):
+        F, J = self.num_frames_total, self.B - 1
+        rp, rr, jr = np.zeros((F, 3), np.float32), np.zeros((F, 4), np.float32), np.zeros((F, J, 4), np.float32)
+        self._L.check(self._lib.parc_mopt_get_frames(self._h, self._L.np_f32p(rp), self._L.np_f32p(rr), self._L.np_f32p(jr)))
+        return rp, rr, jr
+
+    # ------------------------------------------------------------------ constraints
+    def build_constraints(self, clips: Sequence[OptClip]) -> List[OptClip]:
+        """``compute_approx_body_constraints`` for every clip at its full rate: contact runs (flag > 0.9) of both feet (box centre)
+        and both hands, the mean position over each run, then the SGD refinement on the device.  Returns copies with constraints."""
+        cm = self.char_model
+        self.set_clips(clips)
+        F = self.num_frames_total
+        bp = np.zeros((F, self.B, 3), np.float32)
+        br = np.zeros((F, self.B, 4), np.float32)
+        self._L.check(self._lib.parc_mopt_get_source_body(self._h, self._L.np_f32p(bp), self._L.np_f32p(br)))
+        off = self._packed["frame_off"]
+        out, all_clip, all_pts = [], [], []
+        for ci, c in enumerate(clips):
+            pos, rot = bp[off[ci]:off[ci + 1]], br[off[ci]:off[ci + 1]]
+            cb, cs, ce, cp = [], [], [], []
+            for name in CONSTRAINT_BODIES:
+                b = cm.get_body_id(name)
+                p = pos[:, b]
+                g = cm._geoms[b][0]
+                if name.endswith("foot"):
+                    p = p + _quat_rotate(rot[:, b], np.broadcast_to(g.pos.astype(np.float32), p.shape)).astype(np.float32)
+                for s, e in contact_runs(c.contacts[:, b]):
+                    cb.append(b); cs.append(s); ce.append(e)
+                    cp.append(np.mean(p[s:e + 1], axis=0, dtype=np.float32))
+            order = sorted(range(len(cb)), key=lambda i: (cb[i], cs[i]))   # body-major, as the reference's per-body lists
+            cb, cs, ce, cp = [cb[i] for i in order], [cs[i] for i in order], [ce[i] for i in order], [cp[i] for i in order]
+            nc = OptClip(**{**c.__dict__})
+            nc.cons_body, nc.cons_start, nc.cons_end = np.array(cb, np.int32), np.array(cs, np.int32), np.array(ce, np.int32)
+            nc.cons_point = np.array(cp, np.float32).reshape(-1, 3)
+            out.append(nc)
+            all_clip += [ci] * len(cb); all_pts += cp
+        if all_pts:
+            pts = np.ascontiguousarray(np.array(all_pts, np.float32).reshape(-1, 3))
+            cl = np.array(all_clip, np.int32)
+            self._L.check(self._lib.parc_mopt_build_constraints(self._h, len(cl), self._L.np_i32p(cl), self._L.np_f32p(pts),
+                                                                 CONSTRAINT_SGD_STEPS, CONSTRAINT_SGD_LR))
+            k = 0
+            for nc in out:
+                n = len(nc.cons_body)
+                nc.cons_point = pts[k:k + n].copy(); k += n
+        return out
+
+    # ------------------------------------------------------------------ driver
+    def optimize(self, clips: Sequence[OptClip], iters: int, log_every: int = 0, log=None):
+        """Optimise every clip in one batch.  Returns (frames, history): per clip a dict root_pos / root_rot / joint_rot / contacts
+        (contacts unchanged), and per clip a list of (iteration, {LossType name: value}) every ``log_every`` iterations and at the end."""
+        self.set_clips(clips)
+        hist = [[] for _ in clips]
+        done = 0
+        every = int(log_every) if log_every and log_every > 0 else max(int(iters), 1)
+        while done < iters:
+            n = min(every, iters - done)
+            terms = self.step(n)
+            done += n
+            for ci in range(len(clips)):
+                hist[ci].append((done - n, {LossType(k).name: float(terms[0, ci, k]) for k in range(NUM_TERMS)}))
+            if log is not None:
+                log(done - n, terms[0])
+        terms, _ = self.loss_and_grad()
+        for ci in range(len(clips)):
+            hist[ci].append((int(iters), {LossType(k).name: float(terms[ci, k]) for k in range(NUM_TERMS)}))
+        rp, rr, jr = self.get_frames()
+        frames = [dict(root_pos=a, root_rot=b, joint_rot=c_, contacts=cl.contacts.copy())
+                  for a, b, c_, cl in zip(self._split(rp), self._split(rr), self._split(jr), clips)]
+        return frames, hist

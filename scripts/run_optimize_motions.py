@@ -1,0 +1,106 @@
+#!/usr/bin/env python3
+"""Kinematic motion optimiser driver: every clip of ``motions_yaml_path`` (one ms file or a dataset YAML) in ONE batched run.
+
+    python scripts/run_optimize_motions.py --config data/configs/motion_opt/motion_opt_default.yaml
+
+Semantics of PARC's ``parc_2_kin_gen.py`` optimisation stage: optional body constraints from the source clip at full rate
+(``auto_compute_body_constraints``), the frame stride of ``run_optimize_motions.py`` (constraint ranges ``ceil(s / stride)`` /
+``e // stride``, fps ``fps // stride``), then ``num_iters`` Adam iterations.  Writes ``<name>_opt.pkl`` (loop mode CLAMP, the
+clip's terrain, constraints in ``misc_data`` as plain arrays) and ``log/log_<name>_opt.txt`` with the loss terms every
+``log_every`` iterations.
+"""
+import argparse
+import os
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+import numpy as np  # noqa: E402
+
+from parc_amd import motion_opt as mo  # noqa: E402
+
+REQUIRED = ("motions_yaml_path", "output_folder_path", "char_model", "num_iters", "step_size", "max_jerk") + mo.WEIGHT_KEYS
+
+
+def load_config(path):
+    from parc_amd.util import path_loader
+    cfg = path_loader.load_config(path)
+    if not isinstance(cfg, dict):
+        raise ValueError(f"{path}: not a mapping")
+    missing = [k for k in REQUIRED if k not in cfg]
+    if missing:
+        raise ValueError(f"{path}: missing keys {missing}")
+    cfg.setdefault("device", "cuda:0")
+    cfg.setdefault("frame_stride", 1)
+    cfg.setdefault("auto_compute_body_constraints", False)
+    cfg.setdefault("log_every", 100)
+    if int(cfg["frame_stride"]) < 1 or int(cfg["num_iters"]) < 0:
+        raise ValueError("frame_stride must be >= 1 and num_iters >= 0")
+    return cfg
+
+
+def resolve(p):
+    return p if os.path.isabs(p) else os.path.join(REPO, p)
+
+
+def write_clip(path, frames, clip: mo.OptClip, constraints: mo.OptClip):
+    from parc_amd import ms_file
+    misc = None
+    if len(constraints.cons_body):
+        misc = {"opt:body_constraints": {"body": constraints.cons_body.astype(np.int64), "start_frame": constraints.cons_start.astype(np.int64),
+                                          "end_frame": constraints.cons_end.astype(np.int64), "point": constraints.cons_point.astype(np.float32)}}
+    md = ms_file.MSMotionData(root_pos=frames["root_pos"], root_rot=frames["root_rot"], joint_rot=frames["joint_rot"],
+                              body_contacts=frames["contacts"], fps=int(clip.fps), loop_mode="CLAMP")
+    maxmin = clip.hf_maxmin
+    if maxmin is None:   # a clip built in memory: SubTerrain's defaults (max 1, min -1 in every cell)
+        maxmin = np.stack([np.ones_like(clip.hf), -np.ones_like(clip.hf)], -1)
+    td = ms_file.MSTerrainData(hf=clip.hf, hf_maxmin=maxmin, min_point=clip.min_point, dx=float(clip.dx))
+    ms_file.save_ms_file(ms_file.MSFileData(motion_data=md, terrain_data=td, misc_data=misc), path)
+
+
+def run(cfg):
+    from parc_amd.motion_lib import fetch_motion_files
+    files, _ = fetch_motion_files(resolve(cfg["motions_yaml_path"]))
+    clips = [mo.clip_from_ms(f) for f in files]
+    opt = mo.MotionOptimizer(resolve(cfg["char_model"]), cfg["device"], cfg)
+    if cfg["auto_compute_body_constraints"]:
+        clips = opt.build_constraints(clips)
+    stride = int(cfg["frame_stride"])
+    clips = [c.strided(stride) for c in clips]
+    out_dir = resolve(cfg["output_folder_path"])
+    log_dir = os.path.join(out_dir, "log")
+    os.makedirs(log_dir, exist_ok=True)
+    logs = [open(os.path.join(log_dir, f"log_{c.name}_opt.txt"), "w") for c in clips]
+    for f in logs:
+        f.write("iteration\t" + "\t".join(t.name for t in mo.LossType) + "\n")
+
+    def log(it, terms):
+        for f, t in zip(logs, terms):
+            f.write(f"{it}\t" + "\t".join(f"{v:.6g}" for v in t) + "\n")
+
+    t0 = time.time()
+    frames, hist = opt.optimize(clips, int(cfg["num_iters"]), int(cfg["log_every"]), log=log)
+    for f, c, h in zip(logs, clips, hist):
+        f.write(f"{h[-1][0]}\t" + "\t".join(f"{h[-1][1][t.name]:.6g}" for t in mo.LossType) + "\n")
+        f.close()
+    paths = []
+    for c, fr in zip(clips, frames):
+        p = os.path.join(out_dir, c.name + "_opt.pkl")
+        write_clip(p, fr, c, c)
+        paths.append(p)
+    print(f"optimised {len(clips)} clips x {cfg['num_iters']} iterations in {time.time() - t0:.2f} s")
+    return paths
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--config", required=True)
+    args = ap.parse_args(argv)
+    return run(load_config(args.config))
+
+
+if __name__ == "__main__":
+    main()

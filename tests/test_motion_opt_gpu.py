@@ -1,0 +1,269 @@
+"""Kinematic motion optimiser on the GPU (parc_mopt_*) against the reference fixtures (tests/golden/make_golden_motion_opt.py)."""
+import os
+
+import numpy as np
+import pytest
+
+from parc_amd import motion_opt as mo
+
+pytestmark = pytest.mark.gpu
+
+REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+CHAR = os.path.join(REPO, "data/assets/humanoid.xml")
+FIXTURES = ["motion_opt_dec2024_teaser_717_1_modified_opt_s1", "motion_opt_civilization_s4"]
+
+
+def fixture(name):
+    return dict(np.load(os.path.join(REPO, "tests/golden", name + ".npz")))
+
+
+def cfg_of(z, **over):
+    c = {k: float(v) for k, v in zip(mo.WEIGHT_KEYS, z["weights"])}
+    c.update(max_jerk=float(z["max_jerk"]), step_size=float(z["step_size"]))
+    c.update(over)
+    return c
+
+
+def clip_of(z, constraints=True):
+    c = mo.OptClip(z["root_pos"], z["root_rot"], z["joint_rot"], z["contacts"], z["hf"], z["min_point"], float(z["dx"]), int(z["fps"]))
+    if constraints:
+        c.cons_body, c.cons_start, c.cons_end, c.cons_point = z["cons_body"], z["cons_start"], z["cons_end"], z["cons_point"]
+    return c
+
+
+def params_of(z, tag):
+    return np.concatenate([z[f"state_{tag}_root_pos"], z[f"state_{tag}_root_rot"], z[f"state_{tag}_dof"]], axis=1).astype(np.float32)
+
+
+def grad_of(z, key):
+    return np.concatenate([z[f"grad_{key}_root_pos"], z[f"grad_{key}_root_rot"], z[f"grad_{key}_dof"]], axis=1)
+
+
+def check_terms(got, ref, rtol=2e-5, atol=1e-6):
+    err = np.abs(got.astype(np.float64) - ref)
+    assert (err <= rtol * np.abs(ref) + atol).all(), (got, ref, err / np.maximum(np.abs(ref), 1e-30))
+
+
+def check_grad(got, ref, what):
+    tol = 1e-4 * np.abs(ref).max() + 1e-6
+    bad = np.abs(got - ref) > tol
+    frac = bad.mean()
+    print(f"{what}: {bad.sum()} of {bad.size} entries outside {tol:.3g} (max err {np.abs(got - ref).max():.3g})")
+    assert frac <= 1e-3, (what, np.argwhere(bad)[:20])
+
+
+@pytest.fixture(scope="module", params=FIXTURES)
+def case(request):
+    z = fixture(request.param)
+    opt = mo.MotionOptimizer(CHAR, "cuda:0", cfg_of(z))
+    opt.set_clips([clip_of(z)])
+    return z, opt
+
+
+def test_initial_iterate_is_the_source_parameterisation(case):
+    z, opt = case
+    p = opt.get_params()
+    np.testing.assert_allclose(p, params_of(z, "a"), atol=2e-6)
+
+
+@pytest.mark.parametrize("tag", ["a", "b", "c"])
+def test_loss_and_grad_against_reference(case, tag):
+    z, opt = case
+    opt.set_params(params_of(z, tag))
+    terms, grad = opt.loss_and_grad()
+    check_terms(terms[0], z[f"terms_{tag}"])
+    check_grad(grad, grad_of(z, tag), f"{z['clip']} state {tag}")
+    assert np.isfinite(grad).all()
+
+
+def test_masked_rotation_gradients_are_zero_at_the_source(case):
+    z, _ = case
+    # only the rotation terms on: at target = source every rotation difference is below the 1e-5 mask of quat_to_axis_angle, where
+    # autograd's gradient is exactly 0 (torch.where) -- the kernel's must be exactly 0 as well
+    w = {k: 0.0 for k in mo.WEIGHT_KEYS}
+    w.update(w_root_rot=float(z["weights"][1]), w_joint_rot=float(z["weights"][2]))
+    opt = mo.MotionOptimizer(CHAR, "cuda:0", dict(cfg_of(z), **w))
+    opt.set_clips([clip_of(z)])
+    terms, grad = opt.loss_and_grad()
+    assert terms[0, 1] == 0 and terms[0, 2] == 0
+    assert (grad == 0).all(), np.argwhere(grad != 0)[:10]
+
+
+def test_one_adam_step_is_torch_adam_on_the_kernel_gradient(case):
+    import torch
+    z, opt = case
+    p0 = params_of(z, "b")
+    opt.set_params(p0)
+    _, g = opt.loss_and_grad()
+    opt.step(1)
+    p1 = opt.get_params()
+    t = torch.tensor(p0, requires_grad=True)
+    a = torch.optim.Adam([t], lr=float(z["step_size"]))
+    t.grad = torch.tensor(g)
+    a.step()
+    np.testing.assert_allclose(p1, t.detach().numpy(), rtol=0, atol=1e-7)
+
+
+def test_twenty_step_trajectory(case):
+    z, opt = case
+    opt.set_params(params_of(z, "b"))
+    hist = opt.step(20)[:, 0].astype(np.float64)
+    ref = z["hist20"]
+    rel = np.abs(hist - ref) / np.maximum(np.abs(ref), 1e-6)
+    assert (rel <= 1e-3).all(), rel.max(axis=0)
+    p = opt.get_params()
+    close = np.abs(p - params_of(z, "c")) <= 1e-4
+    assert close.mean() >= 0.99, close.mean()
+
+
+def test_long_run_within_five_percent():
+    z = fixture(FIXTURES[0])
+    opt = mo.MotionOptimizer(CHAR, "cuda:0", cfg_of(z))
+    opt.set_clips([clip_of(z)])
+    opt.set_params(params_of(z, "b"))
+    n = int(z["long_iters"])
+    last = opt.step(n)[-1, 0].astype(np.float64)
+    ref = z["hist_long"][-1]
+    assert (np.abs(last - ref) <= 0.05 * np.abs(ref) + 1e-6).all(), (last, ref)
+
+
+@pytest.mark.parametrize("switch", ["no_contact", "no_sliding", "no_constraints"])
+def test_switching_terms_off(switch):
+    for name in FIXTURES:
+        z = fixture(name)
+        over = {"no_contact": dict(w_contact=0.0), "no_sliding": dict(w_sliding=0.0)}.get(switch, {})
+        opt = mo.MotionOptimizer(CHAR, "cuda:0", cfg_of(z, **over))
+        opt.set_clips([clip_of(z, constraints=switch != "no_constraints")])
+        opt.set_params(params_of(z, "b"))
+        terms, grad = opt.loss_and_grad()
+        check_terms(terms[0], z[f"terms_b_{switch}"])
+        if switch == "no_contact":
+            assert terms[0, mo.LossType.CONTACT_LOSS.value] == 0
+        if switch == "no_sliding":
+            assert terms[0, mo.LossType.SLIDING_LOSS.value] == 0
+        check_grad(grad, grad_of(z, f"b_{switch}"), f"{name} {switch}")
+
+
+def test_device_constraint_builder_matches_reference():
+    """Both terrains: the builder runs on the full-rate source frames the reference computed its constraints from."""
+    for name in FIXTURES:
+        z = fixture(name)
+        opt = mo.MotionOptimizer(CHAR, "cuda:0", cfg_of(z))
+        full = mo.OptClip(z["full_root_pos"], z["full_root_rot"], z["full_joint_rot"], z["full_contacts"], z["hf"], z["min_point"],
+                          float(z["dx"]))
+        out = opt.build_constraints([full])[0]
+        np.testing.assert_array_equal(out.cons_body, z["cons_body"])
+        np.testing.assert_array_equal(out.cons_start, z["cons_start_full"])
+        np.testing.assert_array_equal(out.cons_end, z["cons_end_full"])
+        np.testing.assert_allclose(out.cons_point, z["cons_point"], atol=1e-4)
+        strided = out.strided(int(z["stride"]))
+        np.testing.assert_array_equal(strided.cons_start, z["cons_start"])
+        np.testing.assert_array_equal(strided.cons_end, z["cons_end"])
+
+
+def _synthetic_clips(n, seed=0):
+    rng = np.random.default_rng(seed)
+    zs = [fixture(f) for f in FIXTURES]
+    out = []
+    for i in range(n):
+        z = zs[i % 2]
+        base = clip_of(z)
+        F = base.num_frames
+        L = [3, 4, 7, 400][i] if i < 4 else int(rng.integers(4, 401))
+        idx = np.arange(L) % F
+        c = mo.OptClip(base.root_pos[idx].copy(), base.root_rot[idx].copy(), base.joint_rot[idx].copy(), base.contacts[idx].copy(),
+                       base.hf, base.min_point, base.dx, base.fps)
+        c.root_pos[:, :2] += rng.normal(0, 0.05, 2).astype(np.float32)
+        c.root_pos[:, 2] -= np.float32(0.05)
+        if i == 5:   # points off the terrain edge
+            c.root_pos[:, 0] += np.float32(z["hf"].shape[0] * z["dx"])
+        keep = (base.cons_end < L)
+        c.cons_body, c.cons_start, c.cons_end, c.cons_point = base.cons_body[keep], base.cons_start[keep], base.cons_end[keep], \
+            base.cons_point[keep]
+        out.append(c)
+    return out
+
+
+def test_batching_is_bit_identical_to_single_runs():
+    z = fixture(FIXTURES[0])
+    clips = _synthetic_clips(64)
+    opt = mo.MotionOptimizer(CHAR, "cuda:0", cfg_of(z))
+    frames, hist = opt.optimize(clips, 50)
+    single = mo.MotionOptimizer(CHAR, "cuda:0", cfg_of(z))
+    for i in range(len(clips)):   # every clip alone (set_clips resets the iterate and Adam)
+        f1, h1 = single.optimize([clips[i]], 50)
+        for k in ("root_pos", "root_rot", "joint_rot"):
+            assert np.array_equal(frames[i][k], f1[0][k]), (i, k)
+        assert hist[i] == h1[0]
+    assert hist[0][-1][1]["JERK_LOSS"] == 0.0   # 3 frames: no jerk window
+
+
+def test_large_batch_finite_and_nan_clip_isolated():
+    z = fixture(FIXTURES[0])
+    clips = _synthetic_clips(1024, seed=1)
+    clips[7].root_pos[2, 0] = np.nan
+    opt = mo.MotionOptimizer(CHAR, "cuda:0", cfg_of(z))
+    opt.set_clips(clips)
+    terms = opt.step(100)
+    bad = ~np.isfinite(terms).all(axis=(0, 2))
+    assert bad[7] and bad.sum() == 1, np.nonzero(bad)[0]
+    p = opt.get_params()
+    off = opt._packed["frame_off"]
+    for i in [0, 100, 333, 512, 777, 900, 1000, 1023]:
+        s = mo.MotionOptimizer(CHAR, "cuda:0", cfg_of(z))
+        s.set_clips([clips[i]])
+        s.step(100)
+        assert np.array_equal(s.get_params(), p[off[i]:off[i + 1]]), i
+
+
+def test_argument_errors():
+    z = fixture(FIXTURES[0])
+    opt = mo.MotionOptimizer(CHAR, "cuda:0", cfg_of(z))
+    c = clip_of(z)
+    with pytest.raises(ValueError):
+        opt.set_clips([mo.OptClip(c.root_pos[:0], c.root_rot[:0], c.joint_rot[:0], c.contacts[:0], c.hf, c.min_point, c.dx)])
+    with pytest.raises(ValueError):
+        opt.set_clips([mo.OptClip(c.root_pos, c.root_rot[:-1], c.joint_rot, c.contacts, c.hf, c.min_point, c.dx)])
+    with pytest.raises(ValueError):
+        mo.MotionOptimizer(CHAR, "cuda:0", dict(cfg_of(z), char_point_samples=dict(sphere_num_subdivisions=1)))
+    from parc_amd import lib as L
+    with pytest.raises(L.ParcError):
+        opt.loss_and_grad()   # no clips yet
+
+
+def test_driver_end_to_end_files_load_in_the_env(tmp_path):
+    import sys
+    import torch
+    import yaml
+    sys.path.insert(0, os.path.join(REPO, "scripts"))
+    import run_optimize_motions as drv
+    from gpu_helpers import default_config
+    from parc_amd import ms_file
+    from parc_amd.envs.hip_parkour_env import HipParkourEnv
+    cfg = yaml.safe_load(open(os.path.join(REPO, "data/configs/motion_opt/motion_opt_default.yaml")))
+    ds = tmp_path / "ds.yaml"
+    ds.write_text(yaml.safe_dump({"motions": [{"file": os.path.join(REPO, "data/motion_terrains", f), "weight": 1.0}
+                                              for f in ("dec2024_teaser_717_1_modified_opt.pkl", "civilization.pkl", "sfu.pkl")]}))
+    cfg.update(motions_yaml_path=str(ds), output_folder_path=str(tmp_path / "out"), num_iters=30, log_every=10, frame_stride=2)
+    c = tmp_path / "c.yaml"
+    c.write_text(yaml.safe_dump(cfg))
+    paths = drv.main(["--config", str(c)])
+    assert len(paths) == 3
+    for p in paths:
+        d = ms_file.load_ms_file(p)
+        assert d.motion_data.loop_mode == "CLAMP" and d.motion_data.fps == 15
+        assert np.isfinite(d.motion_data.root_pos).all()
+        assert "opt:body_constraints" in d.misc_data
+        src_td = ms_file.load_ms_file(os.path.join(REPO, "data/motion_terrains", os.path.basename(p)[:-8] + ".pkl"),
+                                      load_misc=False).terrain_data
+        np.testing.assert_array_equal(d.terrain_data.hf_maxmin, src_td.hf_maxmin)
+        log = open(os.path.join(tmp_path, "out", "log", "log_" + os.path.basename(p)[:-4] + ".txt")).read().splitlines()
+        assert len(log) == 1 + 3 + 1
+        env_cfg = default_config()
+        env_cfg["env"]["dm"]["motion_file"] = p
+        env = HipParkourEnv(env_cfg, 8, "cuda:0", False)
+        obs, _ = env.reset()
+        obs, rew, done, _ = env.step(env._char_dof_pos.clone())
+        torch.cuda.synchronize()
+        assert torch.isfinite(obs).all() and torch.isfinite(rew).all()
+        del env
