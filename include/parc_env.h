@@ -478,6 +478,47 @@ int parc_mopt_build_constraints(ParcMotionOpt *h, int32_t n, const int32_t *clip
 /* Per-kernel device time (hipEvents) of the last parc_mopt_step call, ms per iteration: fk, patch, points, grad, reduce, adam. */
 int parc_mopt_kernel_times(ParcMotionOpt *h, float *ms6);
 
+/* Motion-terrain analysis for B clips at once, each on its own terrain: the reference's
+ * terrain_util.compute_hf_extra_vals (per-frame heightfield cell masks, lowest body point per cell, augmentation bounds hf_maxmin,
+ * terrain_util.py:1851-1947), mdm_path.compute_motion_loss with unit weights (penetration and contact against the exact column-box
+ * SDF of the whole terrain, mdm_path.py:31-127) and the jerk statistics of scripts/motion_tests/compute_losses.py:163-174.
+ * Its own handle.  The clips use the optimiser's layout (ParcMotionOptClips; the constraint fields are ignored).  A frame whose inputs
+ * or sample points are not finite contributes no cells and no heights and makes its clip's scores and max root z NaN; other clips are
+ * unaffected.  Results do not depend on which other clips are in the batch. */
+#define PARC_MTERR_SDF_PRUNED 0                  /* exact ring-pruned search of the whole terrain (default) */
+#define PARC_MTERR_SDF_BRUTE 1                   /* every cell for every point (bit-identical to the pruned search; for tests) */
+#define PARC_MTERR_CLIP_OUTPUTS 6                /* pen_loss, contact_loss, mean_jerk, jerk_frac, max_root_z, min_hf */
+typedef struct ParcMotionTerrain ParcMotionTerrain;
+typedef struct {
+    uint32_t struct_size;                    /* sizeof(ParcMotionTerrainParams) */
+    int32_t device;
+    ParcCharModel model;                     /* the tables parc_env_create takes (fk_paths unused) */
+    int32_t num_points;                      /* sample points per frame, [1, PARC_MOPT_MAX_POINTS]; contiguous per body, bodies in order */
+    const float *points_host;                /* [num_points][3] body-local */
+    const int32_t *point_body_host;          /* [num_points] */
+    int32_t contact_body_id[PARC_MAX_BODIES];/* column of the contacts array of each body, -1 = not scored (compute_motion_loss: b -> b) */
+    double z_buf;                            /* hf_maxmin default bounds: max root z + z_buf, min hf - z_buf (reference default 3.0) */
+    double jump_buf;                         /* jump cells: lowest point - hf >= jump_buf (fp32), bound lowest point - jump_buf (0.8) */
+    double max_jerk;                         /* jerk_frac threshold, compared in fp32 (compute_losses.py: 11666.3906) */
+    int32_t sdf_mode;                        /* PARC_MTERR_SDF_* */
+} ParcMotionTerrainParams;
+int parc_mterr_create(const ParcMotionTerrainParams *p, ParcMotionTerrain **out);
+void parc_mterr_destroy(ParcMotionTerrain *h);
+/* Uploads the clips (num_clips >= 1, every clip >= 1 frame, dims >= 1 with at most 2^31 - 1 cells, dx > 0). */
+int parc_mterr_set_clips(ParcMotionTerrain *h, const ParcMotionOptClips *c);
+/* One analysis of the uploaded clips.  Outputs (NULL = not copied): clip_out [num_clips][PARC_MTERR_CLIP_OUTPUTS]; mask_counts [F], the
+ * number of distinct cells of each frame; hf_maxmin [cells][2] (max, min), cells in hf_host's order; total_inds = sum of mask_counts.
+ * mean_jerk / jerk_frac are NaN for clips of fewer than 4 frames; jerk_frac divides by frames - 3, not by samples (the reference's). */
+int parc_mterr_run(ParcMotionTerrain *h, float *clip_out_host, int32_t *mask_counts_host, float *hf_maxmin_host, int64_t *total_inds);
+/* The cells of the last run: int32 [total_inds][2] (i, j), frames in order, each frame's cells in lexicographic order without repeats. */
+int parc_mterr_get_mask_inds(ParcMotionTerrain *h, int32_t *inds_host);
+/* TEST entry: the lowest body point per cell of the last run ([cells], 99999.9999f where untouched) and the touched flags ([cells]). */
+int parc_mterr_get_min_heights(ParcMotionTerrain *h, float *min_heights_host, int32_t *touched_host);
+/* TEST entry: the raw ground / air SDF minima [num_frames][num_points] of frames [frame0, frame0 + num_frames) (after a run). */
+int parc_mterr_point_sdf(ParcMotionTerrain *h, int64_t frame0, int32_t num_frames, float *ground_host, float *air_host);
+/* Device time (hipEvents) of the last run, ms: fk, init, points, reduce, cells, and gather (the last parc_mterr_get_mask_inds). */
+int parc_mterr_kernel_times(ParcMotionTerrain *h, float *ms6);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,16 @@ class ParcMotionOptParams(C.Structure):
                 ("step_size", C.c_float)]
 
 
+MTERR_SDF_PRUNED, MTERR_SDF_BRUTE = 0, 1   # PARC_MTERR_SDF_*
+MTERR_CLIP_OUTPUTS = 6
+
+
+class ParcMotionTerrainParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("model", ParcCharModel), ("num_points", C.c_int32),
+                ("points_host", f32p), ("point_body_host", i32p), ("contact_body_id", C.c_int32 * MAX_BODIES),
+                ("z_buf", C.c_double), ("jump_buf", C.c_double), ("max_jerk", C.c_double), ("sdf_mode", C.c_int32)]
+
+
 class ParcMotionOptClips(C.Structure):
     _fields_ = [("num_clips", C.c_int32), ("frame_off_host", i64p), ("hf_off_host", i64p), ("cons_off_host", i64p),
                 ("hf_dims_host", i32p), ("hf_geom_host", f32p), ("hf_host", f32p), ("root_pos_host", f32p), ("root_rot_host", f32p),
@@ -199,6 +209,15 @@ def load():
     lib.parc_mopt_get_source_body.argtypes = [vp, f32p, f32p]
     lib.parc_mopt_build_constraints.argtypes = [vp, C.c_int32, i32p, f32p, C.c_int32, C.c_float]
     lib.parc_mopt_kernel_times.argtypes = [vp, f32p]
+    lib.parc_mterr_create.argtypes = [C.POINTER(ParcMotionTerrainParams), C.POINTER(vp)]
+    lib.parc_mterr_destroy.argtypes = [vp]
+    lib.parc_mterr_destroy.restype = None
+    lib.parc_mterr_set_clips.argtypes = [vp, C.POINTER(ParcMotionOptClips)]
+    lib.parc_mterr_run.argtypes = [vp, f32p, i32p, f32p, C.POINTER(C.c_int64)]
+    lib.parc_mterr_get_mask_inds.argtypes = [vp, i32p]
+    lib.parc_mterr_get_min_heights.argtypes = [vp, f32p, i32p]
+    lib.parc_mterr_point_sdf.argtypes = [vp, C.c_int64, C.c_int32, f32p, f32p]
+    lib.parc_mterr_kernel_times.argtypes = [vp, f32p]
     _lib = lib
     return lib
 
@@ -215,6 +234,8 @@ EXPORTED_SYMBOLS = [
     "parc_mopt_create", "parc_mopt_destroy", "parc_mopt_set_clips", "parc_mopt_set_constraint_points", "parc_mopt_set_params",
     "parc_mopt_get_params", "parc_mopt_loss_and_grad", "parc_mopt_step", "parc_mopt_get_frames", "parc_mopt_get_source_body",
     "parc_mopt_build_constraints", "parc_mopt_kernel_times",
+    "parc_mterr_create", "parc_mterr_destroy", "parc_mterr_set_clips", "parc_mterr_run", "parc_mterr_get_mask_inds",
+    "parc_mterr_get_min_heights", "parc_mterr_point_sdf", "parc_mterr_kernel_times",
 ]
 
 # parc_test_quat_op selectors (include/parc_env.h)

@@ -1,0 +1,160 @@
+"""Batched motion-terrain analysis: the reference's ``terrain_util.compute_hf_extra_vals`` (dataset preprocessing and stage 2),
+``mdm_path.compute_motion_loss`` with unit weights and the jerk statistics of ``scripts/motion_tests/compute_losses.py``.
+
+B clips of any lengths, each on its own terrain, are packed as for the motion optimiser (``motion_opt.pack_clips``, no constraints)
+and analysed in one launch sequence (``parc_amd/csrc/parc_motion_terrain.hpp``).  Per clip: the cells each
+frame covers (``hf_mask_inds``, int64 ``[K, 2]`` per frame as the reference stores them), the augmentation bounds ``hf_maxmin``,
+``pen_loss`` / ``contact_loss`` against the exact SDF of the whole terrain, ``mean_jerk`` / ``jerk_frac``.  The sample points are
+``get_char_point_samples``' defaults, which the reference uses for both passes.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, Sequence
+
+import numpy as np
+
+from parc_amd.char_model import CharModel
+from parc_amd.motion_opt import OptClip, char_point_samples, clip_from_ms, pack_clips  # noqa: F401  (re-exported for callers)
+
+SDF_PRUNED, SDF_BRUTE = 0, 1
+Z_BUF, JUMP_BUF, MAX_JERK = 3.0, 0.8, 11666.3906
+CLIP_OUTPUTS = ("pen_loss", "contact_loss", "mean_jerk", "jerk_frac", "max_root_z", "min_hf")
+KERNELS = ("fk", "init", "points", "reduce", "cells", "gather")
+MISSING_POINT_VALUE = 99999.9999   # compute_hf_mask_inds' initial lowest point
+
+
+def analyzer_params(char_model: CharModel, flat_points, point_body, z_buf=Z_BUF, jump_buf=JUMP_BUF, max_jerk=MAX_JERK,
+                    sdf_mode=SDF_PRUNED, device: int = 0):
+    """``ParcMotionTerrainParams``: every body scored with its own contact column (``compute_motion_loss``' ``contacts[..., b]``)."""
+    from parc_amd import lib as L
+    p = L.ParcMotionTerrainParams()
+    p.struct_size = C.sizeof(L.ParcMotionTerrainParams)
+    p.device = int(device)
+    p.model = L.make_char_model(char_model)
+    pts = np.ascontiguousarray(flat_points, np.float32)
+    body = np.ascontiguousarray(point_body, np.int32)
+    p.num_points = int(pts.shape[0])
+    p.points_host = L.np_f32p(pts)
+    p.point_body_host = L.np_i32p(body)
+    p._keep = (pts, body)
+    for b in range(char_model.get_num_bodies()):
+        p.contact_body_id[b] = b
+    p.z_buf, p.jump_buf, p.max_jerk = float(z_buf), float(jump_buf), float(max_jerk)
+    p.sdf_mode = int(sdf_mode)
+    return p
+
+
+def clip_struct(pk, num_clips):
+    """``ParcMotionOptClips`` over the arrays of ``pack_clips`` (the caller keeps ``pk`` alive)."""
+    from parc_amd import lib as L
+    st = L.ParcMotionOptClips()
+    st.num_clips = int(num_clips)
+    i64 = lambda a: a.ctypes.data_as(L.i64p)  # noqa: E731
+    st.frame_off_host, st.hf_off_host, st.cons_off_host = i64(pk["frame_off"]), i64(pk["hf_off"]), i64(pk["cons_off"])
+    st.hf_dims_host, st.hf_geom_host, st.hf_host = L.np_i32p(pk["hf_dims"]), L.np_f32p(pk["hf_geom"]), L.np_f32p(pk["hf"])
+    st.root_pos_host, st.root_rot_host = L.np_f32p(pk["root_pos"]), L.np_f32p(pk["root_rot"])
+    st.joint_rot_host, st.contacts_host = L.np_f32p(pk["joint_rot"]), L.np_f32p(pk["contacts"])
+    return st
+
+
+class MotionTerrainAnalyzer:
+    """``MotionTerrainAnalyzer(char_file, device).analyze(clips)``: ``compute_hf_extra_vals`` + ``compute_motion_loss`` + jerk
+    statistics for a whole batch of clips on the GPU.  ``sdf_mode = SDF_BRUTE`` scans every cell for every point (for tests: the
+    default ring-pruned search returns the same bits); ``points`` replaces the sampler's points."""
+
+    def __init__(self, char_file: str, device="cuda:0", sdf_mode: int = SDF_PRUNED, points=None):
+        import torch  # noqa: F401  (one HIP runtime: torch's, loaded before the library)
+        from parc_amd import lib as L
+        self._L = L
+        self._lib = L.load()
+        self.char_model = CharModel(char_file)
+        if points is None:   # get_char_point_samples' defaults
+            _, self.points, self.point_body = char_point_samples(self.char_model)
+        else:                # (flat [P, 3], body index [P]), e.g. the reference's own samples
+            self.points = np.ascontiguousarray(points[0], np.float32)
+            self.point_body = np.ascontiguousarray(points[1], np.int32)
+        dev = str(device)
+        self.device_index = int(dev.split(":")[1]) if ":" in dev else 0
+        self.sdf_mode = int(sdf_mode)
+        self.B = self.char_model.get_num_bodies()
+        self.D = self.char_model.get_dof_size()
+        self._h = None
+        self._key = None
+        self._packed = None
+
+    def __del__(self):
+        self._destroy()
+
+    def _destroy(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            self._lib.parc_mterr_destroy(h)
+        self._h = None
+
+    def _handle(self, z_buf, jump_buf, max_jerk):
+        key = (float(z_buf), float(jump_buf), float(max_jerk))
+        if self._h is None or self._key != key:
+            self._destroy()
+            p = analyzer_params(self.char_model, self.points, self.point_body, *key, sdf_mode=self.sdf_mode, device=self.device_index)
+            h = C.c_void_p()
+            self._L.check(self._lib.parc_mterr_create(C.byref(p), C.byref(h)))
+            self._h, self._key = h, key
+        return self._h
+
+    def run(self, clips: Sequence[OptClip], z_buf=Z_BUF, jump_buf=JUMP_BUF, max_jerk=MAX_JERK):
+        """The flat outputs of one batched run: ``clip_out`` [C, 6] (``CLIP_OUTPUTS``), ``counts`` [F], ``inds`` int32 [K, 2] in
+        frame order, ``hf_maxmin`` [cells, 2] and the packing (``frame_off``, ``hf_off``, ...)."""
+        L = self._L
+        h = self._handle(z_buf, jump_buf, max_jerk)
+        pk = pack_clips(clips, self.B, self.D)
+        st = clip_struct(pk, len(clips))
+        L.check(self._lib.parc_mterr_set_clips(h, C.byref(st)))
+        F, ncell = int(pk["frame_off"][-1]), int(pk["hf_off"][-1])
+        out = np.zeros((len(clips), len(CLIP_OUTPUTS)), np.float32)
+        counts = np.zeros(F, np.int32)
+        maxmin = np.zeros((ncell, 2), np.float32)
+        total = C.c_int64()
+        L.check(self._lib.parc_mterr_run(h, L.np_f32p(out), L.np_i32p(counts), L.np_f32p(maxmin), C.byref(total)))
+        inds = np.zeros((int(total.value), 2), np.int32)
+        L.check(self._lib.parc_mterr_get_mask_inds(h, L.np_i32p(inds) if inds.size else None))
+        self._packed = pk
+        return dict(packed=pk, clip_out=out, counts=counts, inds=inds, hf_maxmin=maxmin)
+
+    def analyze(self, clips: Sequence[OptClip], z_buf=Z_BUF, jump_buf=JUMP_BUF, max_jerk=MAX_JERK) -> List[dict]:
+        """Per clip a dict: the ``CLIP_OUTPUTS`` scores (floats), ``num_frames``, ``hf_mask_inds`` (list of int64 [K, 2], one per
+        frame) and ``hf_maxmin`` [X, Y, 2] float32."""
+        r = self.run(clips, z_buf, jump_buf, max_jerk)
+        pk, counts = r["packed"], r["counts"]
+        ind_off = np.zeros(counts.size + 1, np.int64)
+        np.cumsum(counts, out=ind_off[1:])
+        inds64 = r["inds"].astype(np.int64)
+        res = []
+        for i, c in enumerate(clips):
+            f0, f1 = int(pk["frame_off"][i]), int(pk["frame_off"][i + 1])
+            per_frame = [inds64[ind_off[f]:ind_off[f + 1]] for f in range(f0, f1)]
+            mm = r["hf_maxmin"][pk["hf_off"][i]:pk["hf_off"][i + 1]].reshape(c.hf.shape[0], c.hf.shape[1], 2).copy()
+            d = {k: float(v) for k, v in zip(CLIP_OUTPUTS, r["clip_out"][i])}
+            d.update(num_frames=f1 - f0, hf_mask_inds=per_frame, hf_maxmin=mm)
+            res.append(d)
+        return res
+
+    # ------------------------------------------------------------------ test entries (after run / analyze)
+    def min_heights(self):
+        """(lowest body point per cell [cells], touched flags [cells]) of the last run, cells in packing order."""
+        n = int(self._packed["hf_off"][-1])
+        mh, tc = np.zeros(n, np.float32), np.zeros(n, np.int32)
+        self._L.check(self._lib.parc_mterr_get_min_heights(self._h, self._L.np_f32p(mh), self._L.np_i32p(tc)))
+        return mh, tc
+
+    def point_sdf(self, frame0: int, num_frames: int):
+        """Raw (ground, air) SDF minima [num_frames, P] of the batch's frames [frame0, frame0 + num_frames)."""
+        P = self.points.shape[0]
+        g, a = np.zeros((num_frames, P), np.float32), np.zeros((num_frames, P), np.float32)
+        self._L.check(self._lib.parc_mterr_point_sdf(self._h, int(frame0), int(num_frames), self._L.np_f32p(g), self._L.np_f32p(a)))
+        return g, a
+
+    def kernel_times(self):
+        out = np.zeros(6, np.float32)
+        self._L.check(self._lib.parc_mterr_kernel_times(self._h, self._L.np_f32p(out)))
+        return dict(zip(KERNELS, out.tolist()))

@@ -7,7 +7,9 @@ Semantics of PARC's ``parc_2_kin_gen.py`` optimisation stage: optional body cons
 (``auto_compute_body_constraints``), the frame stride of ``run_optimize_motions.py`` (constraint ranges ``ceil(s / stride)`` /
 ``e // stride``, fps ``fps // stride``), then ``num_iters`` Adam iterations.  Writes ``<name>_opt.pkl`` (loop mode CLAMP, the
 clip's terrain, constraints in ``misc_data`` as plain arrays) and ``log/log_<name>_opt.txt`` with the loss terms every
-``log_every`` iterations.
+``log_every`` iterations.  With ``hf_extras: true`` (or ``--hf_extras``) the files also carry stage 2's
+``compute_hf_extra_vals`` of the optimised frames: ``misc_data["hf_mask_inds"]`` and the recomputed ``hf_maxmin`` (default off: the
+source bounds are kept).
 """
 import argparse
 import os
@@ -37,6 +39,7 @@ def load_config(path):
     cfg.setdefault("frame_stride", 1)
     cfg.setdefault("auto_compute_body_constraints", False)
     cfg.setdefault("log_every", 100)
+    cfg.setdefault("hf_extras", False)
     if int(cfg["frame_stride"]) < 1 or int(cfg["num_iters"]) < 0:
         raise ValueError("frame_stride must be >= 1 and num_iters >= 0")
     return cfg
@@ -46,15 +49,18 @@ def resolve(p):
     return p if os.path.isabs(p) else os.path.join(REPO, p)
 
 
-def write_clip(path, frames, clip: mo.OptClip, constraints: mo.OptClip):
+def write_clip(path, frames, clip: mo.OptClip, constraints: mo.OptClip, hf_extras=None):
     from parc_amd import ms_file
     misc = None
     if len(constraints.cons_body):
         misc = {"opt:body_constraints": {"body": constraints.cons_body.astype(np.int64), "start_frame": constraints.cons_start.astype(np.int64),
                                           "end_frame": constraints.cons_end.astype(np.int64), "point": constraints.cons_point.astype(np.float32)}}
+    if hf_extras is not None:   # parc_2_kin_gen.py:472-484: the optimised frames' mask inds and bounds
+        misc = dict(misc or {})
+        misc["hf_mask_inds"] = [np.ascontiguousarray(a, np.int64) for a in hf_extras["hf_mask_inds"]]
     md = ms_file.MSMotionData(root_pos=frames["root_pos"], root_rot=frames["root_rot"], joint_rot=frames["joint_rot"],
                               body_contacts=frames["contacts"], fps=int(clip.fps), loop_mode="CLAMP")
-    maxmin = clip.hf_maxmin
+    maxmin = clip.hf_maxmin if hf_extras is None else hf_extras["hf_maxmin"]
     if maxmin is None:   # a clip built in memory: SubTerrain's defaults (max 1, min -1 in every cell)
         maxmin = np.stack([np.ones_like(clip.hf), -np.ones_like(clip.hf)], -1)
     td = ms_file.MSTerrainData(hf=clip.hf, hf_maxmin=maxmin, min_point=clip.min_point, dx=float(clip.dx))
@@ -86,10 +92,16 @@ def run(cfg):
     for f, c, h in zip(logs, clips, hist):
         f.write(f"{h[-1][0]}\t" + "\t".join(f"{h[-1][1][t.name]:.6g}" for t in mo.LossType) + "\n")
         f.close()
+    extras = [None] * len(clips)
+    if cfg["hf_extras"]:
+        from parc_amd.motion_terrain import MotionTerrainAnalyzer
+        opt_clips = [mo.OptClip(fr["root_pos"], fr["root_rot"], fr["joint_rot"], fr["contacts"], c.hf, c.min_point, c.dx, c.fps, c.name)
+                     for c, fr in zip(clips, frames)]
+        extras = MotionTerrainAnalyzer(resolve(cfg["char_model"]), cfg["device"]).analyze(opt_clips)
     paths = []
-    for c, fr in zip(clips, frames):
+    for c, fr, ex in zip(clips, frames, extras):
         p = os.path.join(out_dir, c.name + "_opt.pkl")
-        write_clip(p, fr, c, c)
+        write_clip(p, fr, c, c, ex)
         paths.append(p)
     print(f"optimised {len(clips)} clips x {cfg['num_iters']} iterations in {time.time() - t0:.2f} s")
     return paths
@@ -98,8 +110,12 @@ def run(cfg):
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--config", required=True)
+    ap.add_argument("--hf_extras", action="store_true", help="write hf_mask_inds and recomputed hf_maxmin (config key hf_extras)")
     args = ap.parse_args(argv)
-    return run(load_config(args.config))
+    cfg = load_config(args.config)
+    if args.hf_extras:
+        cfg["hf_extras"] = True
+    return run(cfg)
 
 
 if __name__ == "__main__":
