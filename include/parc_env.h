@@ -519,6 +519,107 @@ int parc_mterr_point_sdf(ParcMotionTerrain *h, int64_t frame0, int32_t num_frame
 /* Device time (hipEvents) of the last run, ms: fk, init, points, reduce, cells, and gather (the last parc_mterr_get_mask_inds). */
 int parc_mterr_kernel_times(ParcMotionTerrain *h, float *ms6);
 
+/* Motion-window sampler for generator training: the reference's MDMHeightfieldContactMotionSampler
+ * (mdm_heightfield_contact_motion_sampler.py) for a whole batch.  Its own handle.  Per sample: a window of T frames at t0 + times[k]
+ * (calc_motion_frame), canonicalised to the heading frame of frame ref_frame and run through FK; the target (root at t_future, in that
+ * frame); the local Gx x Gy heightfield around the reference root with the per-window augmentation bounds (the clip's hf_maxmin where the
+ * window's hf_mask_inds touch a cell, (2 max_h, -2 max_h) elsewhere) and the terrain augmentation.  Every random value comes from a plan
+ * (device arrays of derived values); parc_msamp_draw_plan fills one from a seed with the counter-based generator.  A sample's outputs
+ * do not depend on the batch it is in or on its position.  Limits: T <= PARC_MSAMP_MAX_FRAMES, patch sides <= PARC_MSAMP_MAX_GRID,
+ * a clip's terrain <= PARC_MSAMP_MAX_TERRAIN_CELLS cells (the window mask is a bitset in LDS), max_num_boxes <= PARC_MSAMP_MAX_BOXES. */
+#define PARC_MSAMP_MAX_FRAMES 64
+#define PARC_MSAMP_MAX_GRID 32
+#define PARC_MSAMP_MAX_TERRAIN_CELLS (512 * 512)
+#define PARC_MSAMP_MAX_BOXES 64
+#define PARC_MSAMP_BOX_FLOATS 6                  /* center x, y (patch index units), len x, y, angle, height */
+#define PARC_MSAMP_RELATIVE_TO_ROOT 0            /* RelativeZStyle */
+#define PARC_MSAMP_RELATIVE_TO_ROOT_FLOOR 1
+#define PARC_MSAMP_AUG_NOISE 0                   /* HFAugmentationMode */
+#define PARC_MSAMP_AUG_MAXPOOL_AND_BOXES 1
+#define PARC_MSAMP_AUG_NONE 2
+#define PARC_MSAMP_POOL_NONE 0                   /* plan pool_kind: maxpool_hf, maxpool_hf_1d_x, maxpool_hf_1d_y */
+#define PARC_MSAMP_POOL_2D 1
+#define PARC_MSAMP_POOL_1D_X 2
+#define PARC_MSAMP_POOL_1D_Y 3
+#define PARC_MSAMP_STATUS_BAD_MOTION 1           /* plan status bits (parc_msamp_plan_status) */
+#define PARC_MSAMP_STATUS_BAD_BOXES 2
+#define PARC_MSAMP_STATUS_BAD_POOL 4
+typedef struct ParcMotionSampler ParcMotionSampler;
+typedef struct {
+    uint32_t struct_size;                    /* sizeof(ParcMotionSamplerParams) */
+    int32_t device;
+    ParcCharModel model;                     /* the tables parc_env_create takes (fk_paths unused) */
+    int32_t num_frames;                      /* T = len(arange(0, sequence_duration, 1 / sequence_fps)) */
+    const float *times_host;                 /* [T] that arange, fp32 */
+    float timestep;                          /* fp32(1 / sequence_fps): the frame index of a window is round(t0 / timestep) */
+    float sequence_duration;
+    int32_t ref_frame;                       /* num_prev_states - 1 */
+    int32_t autoregressive;                  /* 0: drawn start times are 0 */
+    int32_t relative_z_style;                /* PARC_MSAMP_RELATIVE_* */
+    int32_t aug_mode;                        /* PARC_MSAMP_AUG_* (use_hf_augmentation = false is AUG_NONE) */
+    int32_t grid_dim_x, grid_dim_y;          /* Gx = num_x_neg + 1 + num_x_pos, Gy likewise */
+    int32_t num_x_neg, num_y_neg;
+    const float *grid_x_host, *grid_y_host;  /* [Gx], [Gy]: get_xy_grid_points' linspace values around 0 */
+    float grid_min_x, grid_min_y;            /* fp32(-num_neg) * fp32(dx) (floor heights) */
+    float dx;                                /* heightmap.horizontal_scale */
+    float max_h;
+    int32_t max_num_boxes;
+    float box_min_len, box_max_len;
+    float hf_maxpool_chance;
+    int32_t hf_max_maxpool_size;
+    float hf_change_height_chance;
+    float future_pos_noise_scale, future_window_min, future_window_max;
+} ParcMotionSamplerParams;
+typedef struct {                             /* with ParcMotionOptClips (constraint fields ignored) */
+    const float *hf_maxmin_host;             /* [cells][2] (max, min), cells in hf_host's order */
+    const int64_t *mask_off_host;            /* [F + 1] CSR offsets of the frames' hf_mask_inds, frames in clip order */
+    const int32_t *mask_cells_host;          /* [mask_off[F]] cell i * Y + j */
+    const int32_t *fps_host;                 /* [num_clips] */
+    const int32_t *loop_modes_host;          /* [num_clips] PARC_LOOP_* */
+    const double *weights_host;              /* [num_clips] sampling weights (normalised on load) */
+} ParcMotionSamplerClipInfo;
+typedef struct {                             /* device arrays of n samples; derived values, not uniforms */
+    int32_t n;
+    const int32_t *motion_id;                /* [n] */
+    const float *t0, *t_future;              /* [n] */
+    const float *future_pos_noise;           /* [n][3] already scaled */
+    const int32_t *change_height;            /* [n] */
+    const float *height_value;               /* [n] */
+    const int32_t *pool_kind, *pool_size;    /* [n][3] PARC_MSAMP_POOL_* in application order; half widths >= 0 */
+    const int32_t *num_boxes;                /* [n] in [0, max_num_boxes] */
+    const float *boxes;                      /* [n][max_num_boxes][PARC_MSAMP_BOX_FLOATS] */
+    const float *noise;                      /* [n][Gx][Gy] the noisy heightfield of AUG_NOISE (NULL in the other modes) */
+} ParcMotionSamplerPlan;
+typedef struct {                             /* caller-owned device buffers; NULL = not written */
+    float *root_pos, *root_rot;              /* [n][T][3], [n][T][4] */
+    float *joint_pos, *joint_rot;            /* [n][T][B-1][3] body positions without the root, [n][T][B-1][4] */
+    float *contacts;                         /* [n][T][B] */
+    float *floor_heights;                    /* [n][T] (needs root_pos and hfs) */
+    float *hfs;                              /* [n][Gx][Gy] */
+    float *target_pos, *target_rot;          /* [n][3], [n][4] */
+    float *hf_bounds;                        /* [n][Gx][Gy][2] the per-window (max, min) after the relative-z shift (tests) */
+} ParcMotionSamplerOutputs;
+int parc_msamp_create(const ParcMotionSamplerParams *p, ParcMotionSampler **out);
+void parc_msamp_destroy(ParcMotionSampler *h);
+/* Uploads the library.  PARC_ERR_INVALID names the clip (by index) that has no full window (num_frames - T <= 0) or whose terrain has
+ * more than PARC_MSAMP_MAX_TERRAIN_CELLS cells. */
+int parc_msamp_set_clips(ParcMotionSampler *h, const ParcMotionOptClips *c, const ParcMotionSamplerClipInfo *info);
+/* The deterministic path: everything is enqueued on `stream`, no host sync. */
+int parc_msamp_sample_with(ParcMotionSampler *h, const ParcMotionSamplerPlan *plan, const ParcMotionSamplerOutputs *out, void *stream);
+/* Fills the (writable, caller-owned) arrays of `plan` for plan->n samples from `seed` (Philox4x32-10, counter = sample index). */
+int parc_msamp_draw_plan(ParcMotionSampler *h, uint64_t seed, const ParcMotionSamplerPlan *plan, void *stream);
+/* draw_plan + sample_with. */
+int parc_msamp_sample(ParcMotionSampler *h, uint64_t seed, const ParcMotionSamplerPlan *plan, const ParcMotionSamplerOutputs *out, void *stream);
+/* get_motion_sequences_for_id: the num_frames - T windows of clip `clip` starting at frames 0, 1, ... (t0 = frame * fp32(1/fps)); motion
+ * outputs only (hfs, floor_heights, targets and bounds must be NULL). */
+int parc_msamp_enumerate(ParcMotionSampler *h, int32_t clip, const ParcMotionSamplerOutputs *out, void *stream);
+/* Synchronises `stream` and returns the OR of the PARC_MSAMP_STATUS_* bits the kernels raised since the last call (then cleared).
+ * A sample with a bad plan entry is still computed memory-safely (ids and counts clamped) but its values are not meaningful. */
+int parc_msamp_plan_status(ParcMotionSampler *h, void *stream, int32_t *status);
+/* Device time (hipEvents; waits for the last event) of the last sample_with / sample call, ms: draw (0 for sample_with), window,
+ * heightfield. */
+int parc_msamp_kernel_times(ParcMotionSampler *h, float *ms3);
+
 #ifdef __cplusplus
 }
 #endif

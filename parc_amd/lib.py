@@ -104,6 +104,43 @@ class ParcMotionOptClips(C.Structure):
                 ("cons_point_host", f32p)]
 
 
+MSAMP_MAX_FRAMES, MSAMP_MAX_GRID, MSAMP_MAX_TERRAIN_CELLS, MSAMP_MAX_BOXES, MSAMP_BOX_FLOATS = 64, 32, 512 * 512, 64, 6   # PARC_MSAMP_*
+MSAMP_STATUS = {1: "motion_id outside the library", 2: "num_boxes outside [0, max_num_boxes]", 4: "pool kind or size out of range"}
+
+
+class ParcMotionSamplerParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("model", ParcCharModel), ("num_frames", C.c_int32),
+                ("times_host", f32p), ("timestep", C.c_float), ("sequence_duration", C.c_float), ("ref_frame", C.c_int32),
+                ("autoregressive", C.c_int32), ("relative_z_style", C.c_int32), ("aug_mode", C.c_int32),
+                ("grid_dim_x", C.c_int32), ("grid_dim_y", C.c_int32), ("num_x_neg", C.c_int32), ("num_y_neg", C.c_int32),
+                ("grid_x_host", f32p), ("grid_y_host", f32p), ("grid_min_x", C.c_float), ("grid_min_y", C.c_float),
+                ("dx", C.c_float), ("max_h", C.c_float), ("max_num_boxes", C.c_int32), ("box_min_len", C.c_float),
+                ("box_max_len", C.c_float), ("hf_maxpool_chance", C.c_float), ("hf_max_maxpool_size", C.c_int32),
+                ("hf_change_height_chance", C.c_float), ("future_pos_noise_scale", C.c_float),
+                ("future_window_min", C.c_float), ("future_window_max", C.c_float)]
+
+
+class ParcMotionSamplerClipInfo(C.Structure):
+    _fields_ = [("hf_maxmin_host", f32p), ("mask_off_host", i64p), ("mask_cells_host", i32p), ("fps_host", i32p),
+                ("loop_modes_host", i32p), ("weights_host", f64p)]
+
+
+# (field, dtype, per-sample shape in terms of max_num_boxes mb / grid gx, gy): the plan's device arrays, in struct order
+MSAMP_PLAN_FIELDS = [("motion_id", "i", ()), ("t0", "f", ()), ("t_future", "f", ()), ("future_pos_noise", "f", (3,)),
+                     ("change_height", "i", ()), ("height_value", "f", ()), ("pool_kind", "i", (3,)), ("pool_size", "i", (3,)),
+                     ("num_boxes", "i", ()), ("boxes", "f", ("mb", MSAMP_BOX_FLOATS)), ("noise", "f", ("gx", "gy"))]
+MSAMP_OUTPUT_FIELDS = ["root_pos", "root_rot", "joint_pos", "joint_rot", "contacts", "floor_heights", "hfs", "target_pos", "target_rot",
+                       "hf_bounds"]
+
+
+class ParcMotionSamplerPlan(C.Structure):
+    _fields_ = [("n", C.c_int32)] + [(n, C.c_void_p) for n, _, _ in MSAMP_PLAN_FIELDS]
+
+
+class ParcMotionSamplerOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in MSAMP_OUTPUT_FIELDS]
+
+
 BUFFER_FIELDS = [
     ("char_root_pos", "f"), ("char_root_rot", "f"), ("char_root_vel", "f"), ("char_root_ang_vel", "f"),
     ("char_dof_pos", "f"), ("char_dof_vel", "f"), ("char_body_pos", "f"), ("contact_forces", "f"),
@@ -218,6 +255,16 @@ def load():
     lib.parc_mterr_get_min_heights.argtypes = [vp, f32p, i32p]
     lib.parc_mterr_point_sdf.argtypes = [vp, C.c_int64, C.c_int32, f32p, f32p]
     lib.parc_mterr_kernel_times.argtypes = [vp, f32p]
+    lib.parc_msamp_create.argtypes = [C.POINTER(ParcMotionSamplerParams), C.POINTER(vp)]
+    lib.parc_msamp_destroy.argtypes = [vp]
+    lib.parc_msamp_destroy.restype = None
+    lib.parc_msamp_set_clips.argtypes = [vp, C.POINTER(ParcMotionOptClips), C.POINTER(ParcMotionSamplerClipInfo)]
+    lib.parc_msamp_sample_with.argtypes = [vp, C.POINTER(ParcMotionSamplerPlan), C.POINTER(ParcMotionSamplerOutputs), vp]
+    lib.parc_msamp_draw_plan.argtypes = [vp, C.c_uint64, C.POINTER(ParcMotionSamplerPlan), vp]
+    lib.parc_msamp_sample.argtypes = [vp, C.c_uint64, C.POINTER(ParcMotionSamplerPlan), C.POINTER(ParcMotionSamplerOutputs), vp]
+    lib.parc_msamp_enumerate.argtypes = [vp, C.c_int32, C.POINTER(ParcMotionSamplerOutputs), vp]
+    lib.parc_msamp_plan_status.argtypes = [vp, vp, i32p]
+    lib.parc_msamp_kernel_times.argtypes = [vp, f32p]
     _lib = lib
     return lib
 
@@ -236,6 +283,8 @@ EXPORTED_SYMBOLS = [
     "parc_mopt_build_constraints", "parc_mopt_kernel_times",
     "parc_mterr_create", "parc_mterr_destroy", "parc_mterr_set_clips", "parc_mterr_run", "parc_mterr_get_mask_inds",
     "parc_mterr_get_min_heights", "parc_mterr_point_sdf", "parc_mterr_kernel_times",
+    "parc_msamp_create", "parc_msamp_destroy", "parc_msamp_set_clips", "parc_msamp_sample_with", "parc_msamp_draw_plan",
+    "parc_msamp_sample", "parc_msamp_enumerate", "parc_msamp_plan_status", "parc_msamp_kernel_times",
 ]
 
 # parc_test_quat_op selectors (include/parc_env.h)

@@ -1,0 +1,375 @@
+#!/usr/bin/env python3
+"""Generate the motion-window sampler fixtures (``motion_sampler_*.npz``) from the REAL reference.
+
+Run where the reference checkout is available (the tests only read the fixtures it writes):
+
+    python tests/golden/make_golden_motion_sampler.py
+
+The reference's ``MDMHeightfieldContactMotionSampler`` is driven as ``make_golden_motion_terrain.py`` drives ``terrain_util`` (a ``parc``
+package alias, empty module stubs, our data-only ms-file decoder) on a two-clip library, ``civilization`` and
+``dec2024_teaser_717_1_modified_opt``; ``hf_mask_inds`` / ``hf_maxmin`` come from the reference's own ``compute_hf_extra_vals`` (they
+equal ``motion_terrain_<clip>.npz``, asserted here, so the tests take them from there).  Every random source the sampler touches is
+wrapped with a recorder (``random.random / randint / shuffle``, ``torch.rand``, ``rand_like``, ``randn_like``); the recorded draws are
+converted to the plan's derived values with the reference's own fp32 expressions.  ``sample_motion_data`` is called with explicit
+``motion_ids`` / ``motion_start_times``.
+
+Per case: the config (JSON), the inputs, the plan, every output, the raw per-window bounds, and ``skip`` [n, Gx, Gy]: the patch
+cells fp32 rounding may move -- (a) the patch point's terrain cell coordinate lies within 1e-4 cells of a half-integer, (b) the
+cell's rotated index coordinate lies within 1e-4 cells of an edge of one of the sample's boxes.  At most 1 % of a case's cells may be
+skipped (asserted).  ``motion_sampler_stats.npz`` holds ``get_motion_sequences_for_id`` of the shorter clip (every ninth window) and the feature statistics
+of the library in ``MDM._compute_stats``' arithmetic (mdm.py:467-495).
+"""
+import json
+import os
+import random
+import sys
+import tempfile
+import types
+
+REF = "/root/reference"
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.abspath(os.path.join(HERE, "..", ".."))
+sys.path.insert(0, REPO)
+sys.dont_write_bytecode = True
+
+for _name in ["trimesh", "trimesh.creation", "wandb", "gym", "gym.spaces", "isaacgym", "isaacgym.gymapi", "isaacgym.gymtorch",
+              "isaacgym.gymutil"]:
+    sys.modules[_name] = types.ModuleType(_name)
+sys.modules["wandb"].run = None
+sys.modules["trimesh"].creation = sys.modules["trimesh.creation"]
+_parc = types.ModuleType("parc")
+_parc.__path__ = [os.path.join(REF, "PARC")]
+sys.modules["parc"] = _parc
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import yaml  # noqa: E402
+
+import parc.util.file_io as ref_file_io  # noqa: E402
+from parc_amd import motion_opt as mo  # noqa: E402
+from parc_amd import ms_file  # noqa: E402
+
+
+def _icosphere(subdivisions=0, radius=1.0):
+    assert subdivisions == 0
+    return types.SimpleNamespace(vertices=mo.icosahedron_vertices() * radius)
+
+
+sys.modules["trimesh.creation"].icosphere = _icosphere
+
+
+def _safe_load(filepath):
+    d = ms_file.load_ms_file(filepath, load_misc=False)
+    md = None if d.motion_data is None else ref_file_io.MSMotionData(**vars(d.motion_data))
+    td = None if d.terrain_data is None else ref_file_io.MSTerrainData(**vars(d.terrain_data))
+    return ref_file_io.MSFileData(motion_data=md, terrain_data=td, misc_data=None)
+
+
+ref_file_io.load_ms_file = _safe_load
+import parc.util.path_loader as ref_path_loader  # noqa: E402
+
+ref_path_loader.resolve_path = lambda p: p                                   # no $DATA_DIR here: the paths below are absolute
+ref_path_loader.load_config = lambda p: yaml.safe_load(open(p).read())
+
+import parc.motion_generator.mdm_heightfield_contact_motion_sampler as ref_sampler  # noqa: E402
+import parc.util.geom_util as geom_util  # noqa: E402
+import parc.util.motion_util as motion_util  # noqa: E402
+import parc.util.terrain_util as terrain_util  # noqa: E402
+import parc.util.torch_util as torch_util  # noqa: E402
+from parc.motion_generator.diffusion_util import MDMFrameType  # noqa: E402
+
+torch.set_num_threads(4)
+CLIPS = ["civilization", "dec2024_teaser_717_1_modified_opt"]
+NUM_SAMPLES = 12
+EDGE = 1e-4
+MAX_SKIP_SHARE = 0.01
+DEFAULT_COMPONENTS = ["ROOT_POS", "ROOT_ROT", "JOINT_POS", "JOINT_ROT", "CONTACTS"]
+BASE_CFG = dict(
+    device="cpu", char_file=os.path.join(REPO, "data/assets/humanoid.xml"),
+    features=dict(frame_components=DEFAULT_COMPONENTS, rot_type="DEFAULT", canonicalize_samples=True),
+    autoregressive=True, sequence_duration=0.5, sequence_fps=30, num_prev_states=2, use_hf_augmentation=True,
+    relative_z_style="RELATIVE_TO_ROOT", hf_augmentation_mode="MAXPOOL_AND_BOXES", max_num_boxes=4, box_min_len=2, box_max_len=12,
+    hf_maxpool_chance=0.6, hf_max_maxpool_size=10, hf_change_height_chance=0.3,   # raised from 0.15 / 0.1: every branch in 12 samples
+    angle_noise_scale=0.01, pos_noise_scale=0.01, future_pos_noise_scale=0.05,
+    heightmap=dict(horizontal_scale=0.2, local_grid=dict(num_x_neg=10, num_x_pos=20, num_y_neg=15, num_y_pos=15), max_h=3.0),
+    future_window_min=0.4, future_window_max=1.5)
+# (name, overrides)
+CASES = [("root_boxes", {}),
+         ("floor_boxes", dict(relative_z_style="RELATIVE_TO_ROOT_FLOOR",
+                              features=dict(frame_components=DEFAULT_COMPONENTS + ["FLOOR_HEIGHTS"], rot_type="DEFAULT",
+                                            canonicalize_samples=True))),
+         ("noise", dict(hf_augmentation_mode="NOISE")),
+         ("none", dict(hf_augmentation_mode="NONE"))]
+POOL_KIND = {"maxpool_hf": 1, "maxpool_hf_1d_x": 2, "maxpool_hf_1d_y": 3}
+
+
+class Recorder:
+    """Wraps the random sources; ``events`` is the list the current augmentation call appends to."""
+
+    def __init__(self):
+        self.events = None
+        self.randn = []
+        self._orig = (random.random, random.randint, random.shuffle, torch.rand, torch.rand_like, torch.randn_like)
+        r = self
+
+        def rnd():
+            v = r._orig[0]()
+            r.events.append(("random", v))
+            return v
+
+        def rint(a, b):
+            v = r._orig[1](a, b)
+            r.events.append(("randint", v))
+            return v
+
+        def shuf(x):
+            r._orig[2](x)
+            r.events.append(("shuffle", [f.__name__ for f in x]))
+
+        def rand(*a, **k):
+            v = r._orig[3](*a, **k)
+            if r.events is not None:
+                r.events.append(("rand", v.clone()))
+            return v
+
+        def rand_like(*a, **k):
+            v = r._orig[4](*a, **k)
+            if r.events is not None:
+                r.events.append(("rand_like", v.clone()))
+            return v
+
+        def randn_like(*a, **k):
+            v = r._orig[5](*a, **k)
+            r.randn.append(v.clone())
+            return v
+
+        random.random, random.randint, random.shuffle = rnd, rint, shuf
+        torch.rand, torch.rand_like, torch.randn_like = rand, rand_like, randn_like
+
+
+def build_sampler(cfg, lib_yaml, extra):
+    c = dict(cfg)
+    c["motion_lib_file"] = lib_yaml
+    s = ref_sampler.MDMHeightfieldContactMotionSampler(c)
+    for i, (inds, maxmin) in enumerate(extra):
+        s._mlib._hf_mask_inds[i] = inds
+        s._mlib._terrains[i].hf_maxmin = maxmin.clone()
+    return s
+
+
+def plan_from_events(s, events, n, gx, gy):
+    """The recorded draws of one sample's ``_box_hf_augmentation`` -> the plan's derived values (the reference's fp32 expressions)."""
+    mb = s._max_num_boxes
+    out = dict(change_height=0, height_value=np.float32(0), pool_kind=np.zeros(3, np.int32), pool_size=np.zeros(3, np.int32), num_boxes=0,
+               boxes=np.zeros((mb, 6), np.float32))
+    ev = list(events)
+
+    def pop(kind):
+        e = ev.pop(0)
+        assert e[0] == kind, (e, kind)
+        return e[1]
+
+    if pop("random") < s._hf_change_height_chance:
+        out["change_height"] = 1
+        out["height_value"] = np.float32(pop("random") * (s._max_h - s._min_h) + s._min_h)   # assigned into the fp32 patch
+    use = [pop("random") < s._hf_maxpool_chance for _ in range(3)]
+    order = pop("shuffle")
+    for k in range(3):
+        if use[k]:
+            out["pool_kind"][k] = POOL_KIND[order[k]]
+            out["pool_size"][k] = pop("randint")
+    nb = pop("randint")
+    out["num_boxes"] = nb
+    shape = torch.tensor([gx, gy], dtype=torch.float32)
+    for b in range(nb):
+        center = pop("rand") * shape
+        length = pop("rand") * (s._box_max_len - s._box_min_len) + s._box_min_len
+        angle = pop("rand") * (2.0 * torch.pi - 0.0) + 0.0
+        h = pop("rand") * (s._max_h - s._min_h) + s._min_h
+        out["boxes"][b] = torch.cat([center, length, angle, h]).numpy()
+    assert not ev, ev
+    return out
+
+
+def skip_cells(s, ids, canon_pos, canon_rot, plan, terrains):
+    """(a) + (b) of the module docstring, evaluated in float64 on the reference's fp32 patch points."""
+    n = len(ids)
+    gx, gy = s._grid_dim_x, s._grid_dim_y
+    pts = s._generic_heightmap.clone().unsqueeze(0).expand(n, -1, -1, -1)
+    heading = torch_util.calc_heading(canon_rot).unsqueeze(-1).unsqueeze(-1).expand(-1, gx, gy)
+    pts = torch_util.rotate_2d_vec(pts, heading) + canon_pos[:, 0:2].unsqueeze(1).unsqueeze(1)
+    skip = np.zeros((n, gx, gy), bool)
+    ii, jj = np.meshgrid(np.arange(gx, dtype=np.float64), np.arange(gy, dtype=np.float64), indexing="ij")
+    for i in range(n):
+        t = terrains[int(ids[i])]
+        u = (pts[i].double().numpy() - t.min_point.double().numpy()) / t.dxdy.double().numpy()
+        skip[i] |= (np.abs(u - np.floor(u) - 0.5) < EDGE).any(-1)
+        for b in range(int(plan["num_boxes"][i])):
+            cx, cy, lx, ly, ang, _ = plan["boxes"][i, b].astype(np.float64)
+            ux, uy = ii - cx, jj - cy
+            rx, ry = ux * np.cos(ang) - uy * np.sin(ang), ux * np.sin(ang) + uy * np.cos(ang)
+            skip[i] |= (np.abs(np.abs(rx) - lx / 2) < EDGE) | (np.abs(np.abs(ry) - ly / 2) < EDGE)
+    return skip
+
+
+def main():
+    rec = Recorder()
+    import parc.anim.kin_char_model as kcm
+    char = kcm.KinCharModel("cpu")
+    char.load_char_file(BASE_CFG["char_file"])
+    pts = geom_util.get_char_point_samples(char)
+    tmp = tempfile.mkdtemp()
+    lib_yaml = os.path.join(tmp, "motions.yaml")
+    with open(lib_yaml, "w") as f:
+        yaml.safe_dump({"motions": [{"file": os.path.join(REPO, "data/motion_terrains", c + ".pkl"), "weight": 1.0} for c in CLIPS]}, f)
+    # hf_mask_inds / hf_maxmin from the reference's compute_hf_extra_vals (= the motion_terrain_<clip>.npz fixtures)
+    extra = []
+    for c in CLIPS:
+        d = ms_file.load_ms_file(os.path.join(REPO, "data/motion_terrains", c + ".pkl"), load_misc=False)
+        m, td = d.motion_data, d.terrain_data
+        terrain = terrain_util.SubTerrain(x_dim=td.hf.shape[0], y_dim=td.hf.shape[1], dx=td.dx, dy=td.dx, min_x=float(td.min_point[0]),
+                                          min_y=float(td.min_point[1]), device="cpu")
+        terrain.hf = torch.tensor(np.asarray(td.hf), dtype=torch.float32)
+        mf = motion_util.MotionFrames(root_pos=torch.tensor(np.asarray(m.root_pos), dtype=torch.float32),
+                                      root_rot=torch.tensor(np.asarray(m.root_rot), dtype=torch.float32),
+                                      joint_rot=torch.tensor(np.asarray(m.joint_rot), dtype=torch.float32),
+                                      contacts=torch.tensor(np.asarray(m.body_contacts), dtype=torch.float32))
+        inds, ret = terrain_util.compute_hf_extra_vals(mf, terrain, char, pts)
+        z = np.load(os.path.join(HERE, f"motion_terrain_{c}.npz"))
+        assert np.array_equal(torch.cat(inds).numpy().astype(np.int32), z["mask_inds"]) and np.array_equal(ret.hf_maxmin.numpy(), z["hf_maxmin"])
+        extra.append((inds, ret.hf_maxmin))
+
+    for case, over in CASES:
+        cfg = dict(BASE_CFG)
+        cfg.update(over)
+        rec.events = None
+        s = build_sampler(cfg, lib_yaml, extra)
+        mlib = s._mlib
+        gx, gy, T = s._grid_dim_x, s._grid_dim_y, s._seq_len
+        rng = np.random.RandomState(1234)
+        ids = np.array([0, 0, 1, 1] + list(rng.randint(0, 2, NUM_SAMPLES - 4)), np.int64)
+        lengths = mlib._motion_lengths.numpy()
+        t0 = (rng.rand(NUM_SAMPLES).astype(np.float32) * (lengths[ids] - np.float32(cfg["sequence_duration"]))).astype(np.float32)
+        t0[0] = t0[2] = 0.0                                                        # the first possible start time of each clip
+        t0[1], t0[3] = lengths[0] - np.float32(0.5), lengths[1] - np.float32(0.5)  # and the last (length - sequence_duration)
+        ids_t, t0_t = torch.tensor(ids), torch.tensor(t0)
+
+        per_sample, captured = [], {}
+        orig_box, orig_noise = s._box_hf_augmentation, s._noise_hf_augmentation
+        orig_future, orig_helper = s._sample_motion_future_times, s.get_hfs_from_data_helper
+
+        def box(hf, mm):
+            rec.events = []
+            orig_box(hf, mm)
+            per_sample.append(rec.events)
+            rec.events = None
+
+        def noise(hf, mm):
+            rec.events = []
+            orig_noise(hf, mm)
+            per_sample.append(rec.events)
+            rec.events = None
+
+        def future(*a, **k):
+            captured["t_future"] = orig_future(*a, **k).clone()
+            return captured["t_future"]
+
+        def helper(*a, **k):
+            hfs, mms = orig_helper(*a, **k)
+            captured["bounds_raw"] = torch.stack(mms).clone()
+            captured["hf_raw"] = torch.stack(hfs).clone()
+            return hfs, mms
+
+        s._box_hf_augmentation, s._noise_hf_augmentation = box, noise
+        s._sample_motion_future_times, s.get_hfs_from_data_helper = future, helper
+        random.seed(7)
+        torch.manual_seed(7)
+        rec.randn = []
+        motion, hfs, target = s.sample_motion_data(motion_ids=ids_t, motion_start_times=t0_t)
+        assert len(rec.randn) == 1
+        plan = dict(motion_id=ids.astype(np.int32), t0=t0, t_future=captured["t_future"].numpy(),
+                    future_pos_noise=(s._future_pos_noise_scale * rec.randn[0]).numpy(),
+                    change_height=np.zeros(NUM_SAMPLES, np.int32), height_value=np.zeros(NUM_SAMPLES, np.float32),
+                    pool_kind=np.zeros((NUM_SAMPLES, 3), np.int32), pool_size=np.zeros((NUM_SAMPLES, 3), np.int32),
+                    num_boxes=np.zeros(NUM_SAMPLES, np.int32), boxes=np.zeros((NUM_SAMPLES, s._max_num_boxes, 6), np.float32))
+        mode = cfg["hf_augmentation_mode"]
+        if mode == "MAXPOOL_AND_BOXES":
+            for i, ev in enumerate(per_sample):
+                for k, v in plan_from_events(s, ev, NUM_SAMPLES, gx, gy).items():
+                    plan[k][i] = v
+        elif mode == "NOISE":
+            plan["noise"] = np.stack([(ev[0][1] * (s._max_h - s._min_h) + s._min_h).numpy() for ev in per_sample])
+        # the canonicalisation inputs, for the skip cells
+        times = (t0_t.unsqueeze(-1) + s._motion_times)[:, s._ref_frame_idx]
+        cp, cr = s._extract_root_pos_and_rot(ids_t, times)
+        skip = skip_cells(s, ids, cp, cr, plan, mlib._terrains)
+        share = skip.mean()
+        assert share <= MAX_SKIP_SHARE, (case, share)
+        out = dict(config=np.array(json.dumps({k: v for k, v in cfg.items() if k not in ("device", "char_file")})), clips=np.array(CLIPS),
+                   skip=skip, bounds_raw=captured["bounds_raw"].numpy(), hf_raw=captured["hf_raw"].numpy(),
+                   root_pos=motion[MDMFrameType.ROOT_POS].numpy(), root_rot=motion[MDMFrameType.ROOT_ROT].numpy(),
+                   joint_pos=motion[MDMFrameType.JOINT_POS].numpy(), joint_rot=motion[MDMFrameType.JOINT_ROT].numpy(),
+                   contacts=motion[MDMFrameType.CONTACTS].numpy(), hfs=hfs.numpy(), target_pos=target.future_pos.numpy(),
+                   target_rot=target.future_rot.numpy())
+        if MDMFrameType.FLOOR_HEIGHTS in motion:   # the reference stacks hf i under EVERY sample's roots: [n, n, T, 1]; the diagonal is sample i's own
+            fh = motion[MDMFrameType.FLOOR_HEIGHTS].numpy()
+            out["floor_heights"] = np.stack([fh[i, i, :, 0] for i in range(NUM_SAMPLES)])
+        out.update({"plan_" + k: v for k, v in plan.items()})
+        path = os.path.join(HERE, f"motion_sampler_{case}.npz")
+        np.savez_compressed(path, **{k: (v.astype(np.float32) if isinstance(v, np.ndarray) and v.dtype == np.float64 else v) for k, v in out.items()})
+        print("wrote", path, os.path.getsize(path), "bytes; skipped share %.5f" % share, "pools", plan["pool_kind"].tolist(), "boxes",
+              plan["num_boxes"].tolist(), "height", plan["change_height"].tolist())
+        assert os.path.getsize(path) <= 235 * 1024
+
+    # get_motion_sequences_for_id of the shorter clip and the feature statistics (mdm.py:467-495, rot_type DEFAULT = quaternions)
+    rec.events = None
+    s = build_sampler(dict(BASE_CFG), lib_yaml, extra)
+
+    def features(md):
+        parts = []
+        for c in DEFAULT_COMPONENTS:
+            v = md[MDMFrameType[c]]
+            parts.append(v.reshape(v.shape[0], v.shape[1], -1))
+        return torch.cat(parts, dim=-1)
+
+    def sequences(i):
+        """get_motion_sequences_for_id (:117-131) as it is meant: every start frame 0 .. num_frames - T - 1 of clip i.  The reference
+        passes the start times positionally, where they land in ``num_samples``, so it really draws that many RANDOM start times;
+        here they go to ``motion_start_times``, which makes the statistics a deterministic function of the library."""
+        nf = s._mlib._motion_num_frames[i].item()
+        starts = torch.arange(start=0, end=nf - s._seq_len, dtype=torch.float32) * (1.0 / s._fps)
+        ids = torch.ones_like(starts, dtype=torch.int64)
+        ids[:] = i
+        return s.sample_motion_data(motion_ids=ids, motion_start_times=starts, ret_hf_obs=False, ret_target_info=False)
+
+    seqs = sequences(1)
+    D = features(seqs).shape[-1]
+    mean = torch.zeros(s._seq_len, D, dtype=torch.float32)
+    std = torch.zeros_like(mean)
+    num = 0
+    for i in range(len(CLIPS)):
+        f = features(sequences(i))
+        num += f.shape[0]
+        mean += f.sum(dim=0)
+    mean /= num
+    for i in range(len(CLIPS)):
+        f = features(sequences(i))
+        std += torch.square(f - mean.unsqueeze(0)).sum(dim=0)
+    std /= (num - 1)
+    std = torch.sqrt(std)
+    c0 = D - 15
+    mean[:, c0:] = 0.0
+    std[:, c0:] = 1.0
+    std = torch.clamp(std, min=1e-5)
+    path = os.path.join(HERE, "motion_sampler_stats.npz")
+    nwin = seqs[MDMFrameType.ROOT_POS].shape[0]
+    sel = np.array(sorted(set(range(0, nwin, 9)) | {nwin - 1}), np.int64)     # every ninth start frame and the last (the size limit)
+    np.savez_compressed(path, clips=np.array(CLIPS), seq_clip=np.int32(1), seq_windows=np.int64(nwin), seq_starts=sel, mean=mean.numpy(),
+                        std=std.numpy(), num_sequences=np.int64(num),
+                        **{"seq_" + c.lower(): seqs[MDMFrameType[c]].numpy()[sel] for c in DEFAULT_COMPONENTS})
+    print("wrote", path, os.path.getsize(path), "bytes;", num, "sequences")
+    assert os.path.getsize(path) <= 235 * 1024
+
+
+if __name__ == "__main__":
+    main()
