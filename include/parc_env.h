@@ -620,6 +620,71 @@ int parc_msamp_plan_status(ParcMotionSampler *h, void *stream, int32_t *status);
  * heightfield. */
 int parc_msamp_kernel_times(ParcMotionSampler *h, float *ms3);
 
+/* Batched terrain path planner: stage 2's A* search (motion_synthesis/procgen/astar.py, driven as
+ * scripts/parc_2_kin_gen.py:310-337) for Q queries at once, each its own dim_x x dim_y heightfield, start cell and goal cell.  Its own
+ * handle.  Per query: the optional terrain simplification (flat_maxpool_2x2, then flatten_4x4_near_edge around the start and around the
+ * goal), the navigation graph (8 neighbours within max_z_diff; jump edges between cliff cells with a Bresenham line of sight), the
+ * search, the node list and the 3-D polyline of run_a_star_on_start_end_nodes.  All of it fp32 in the reference's association.
+ * The pop order is the contract (the metre heuristic is not admissible against squared-metre step costs): the open cell with the smallest
+ * (f, g) is popped; a tie on (f, g) between different cells goes to the LOWEST CELL INDEX i * dim_y + j (the reference's comparison of
+ * tied nodes is not a total order).  Two stated differences from the reference:
+ *   - step-cost noise: not a global stream consumed in expansion order but a pure function of (seed, query index, from cell, to cell):
+ *     Philox4x32-10 keyed by the seed, counter (hi = query index, lo = from << 16 | to), u = the first word's top 24 bits / 2^24,
+ *     noise = fp32(u * fp32(uniform_cost_max - uniform_cost_min) + fp32(uniform_cost_min)), added last;
+ *   - max_compute_time (wall clock) becomes max_expansions: a query that would pop more cells ends with PARC_PATHPLAN_BUDGET and
+ *     counts as a failure (the reference returns the path to whatever node it was at).
+ * Start / goal cells are injected by the caller or drawn on the device: both uniform over pick_random_start_end_nodes_on_edges'
+ * candidate list (i in {1, 2, X-3, X-2} or j in {1, 2, Y-3, Y-2}), redrawn until their xy distance is >= min_start_end_xy_dist - 1e-4;
+ * draw t of query q uses counter (hi = 1 << 62 | q, lo = t), words 0 and 1, index = min(int(u * n), n - 1); after 1000 draws the query
+ * ends with PARC_PATHPLAN_NO_DRAW (the reference asserts).  The query index is first_query + the position in the batch, so a query
+ * computes the same bits alone or in any batch.  Limits: sides of 4 .. PARC_PATHPLAN_MAX_DIM cells (a query's search state lives in LDS:
+ * 14 B per cell, 57.9 KB at 64 x 64), jump window radius ceil(max_jump_xy_dist / dx) <= PARC_PATHPLAN_MAX_JUMP_RADIUS. */
+#define PARC_PATHPLAN_MAX_DIM 64
+#define PARC_PATHPLAN_MAX_JUMP_RADIUS 8
+#define PARC_PATHPLAN_JUMP_WORDS 8               /* (2 * PARC_PATHPLAN_MAX_JUMP_RADIUS)^2 window candidates / 32 */
+#define PARC_PATHPLAN_FOUND 0
+#define PARC_PATHPLAN_NO_PATH 1                  /* the open set ran empty */
+#define PARC_PATHPLAN_OVER_MAX_COST 2            /* a path exists (cost and nodes are returned) but cost > max_cost */
+#define PARC_PATHPLAN_BUDGET 3                   /* more than max_expansions pops */
+#define PARC_PATHPLAN_NO_DRAW 4                  /* no start / goal pair far enough apart in 1000 draws */
+typedef struct ParcPathPlanner ParcPathPlanner;
+typedef struct {
+    uint32_t struct_size;                    /* sizeof(ParcPathPlanParams) */
+    int32_t device;
+    int32_t dim_x, dim_y;                    /* one grid shape per handle */
+    float dx, dy;                            /* SubTerrain.dxdy */
+    float min_point[2];                      /* SubTerrain.min_point (stage 2: 0, 0) */
+    /* AStarSettings (astar.py:12-24), Python floats */
+    double max_z_diff, max_jump_xy_dist, max_jump_z_diff, min_jump_z_diff, w_z, w_xy, w_bumpy, max_bumpy;
+    double uniform_cost_max, uniform_cost_min, min_start_end_xy_dist, max_cost;
+    int32_t simplify_terrain;                /* parc_2_kin_gen's simplify_terrain */
+    int32_t max_expansions;                  /* pops per query before PARC_PATHPLAN_BUDGET */
+    int32_t max_nodes, max_points;           /* row lengths of the node and polyline outputs */
+} ParcPathPlanParams;
+typedef struct {                             /* host arrays of Q entries; NULL = not copied */
+    int32_t *status;                         /* [Q] PARC_PATHPLAN_* */
+    float *cost;                             /* [Q] g of the goal (NaN unless FOUND / OVER_MAX_COST) */
+    int32_t *num_nodes;                      /* [Q] cells of the path, start and goal included (may exceed max_nodes: then cut) */
+    int32_t *nodes;                          /* [Q][max_nodes] cell index i * dim_y + j */
+    int32_t *num_points;                     /* [Q] polyline points of a FOUND query (may exceed max_points: then cut) */
+    float *points;                           /* [Q][max_points][3] */
+    int32_t *start, *goal;                   /* [Q][2] the cells used */
+    float *hf;                               /* [Q][dim_x][dim_y] the heightfield searched (simplified when simplify_terrain) */
+    int32_t *pops;                           /* [Q] */
+} ParcPathPlanOutputs;
+int parc_pathplan_create(const ParcPathPlanParams *p, ParcPathPlanner **out);
+void parc_pathplan_destroy(ParcPathPlanner *h);
+/* Plans Q queries: hf_host [Q][dim_x][dim_y]; start_host / goal_host [Q][2] cells, or both NULL to draw them from (seed, query index).
+ * Synchronous (the outputs are host arrays). */
+int parc_pathplan_run(ParcPathPlanner *h, int32_t Q, const float *hf_host, const int32_t *start_host, const int32_t *goal_host, uint64_t seed,
+                      uint64_t first_query, const ParcPathPlanOutputs *out);
+/* The navigation graph of queries [q0, q0 + n) of the last run, from the predicates the search uses: nbr [n][cells] bit d = the edge to
+ * neighbour d of (-1,0) (1,0) (0,-1) (0,1) (-1,-1) (-1,1) (1,-1) (1,1); cliff [n][cells]; jump [n][cells][PARC_PATHPLAN_JUMP_WORDS],
+ * bit k = the jump edge from (i, j) to (i - R + k / 2R, j - R + k % 2R), R the jump window radius. */
+int parc_pathplan_get_graph(ParcPathPlanner *h, int32_t q0, int32_t n, uint8_t *nbr_host, uint8_t *cliff_host, uint32_t *jump_host);
+/* Device time (hipEvents) of the last run, ms: prepare (draw + simplification), search, and the last parc_pathplan_get_graph. */
+int parc_pathplan_kernel_times(ParcPathPlanner *h, float *ms3);
+
 #ifdef __cplusplus
 }
 #endif

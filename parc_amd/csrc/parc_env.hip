@@ -2969,3 +2969,4 @@ extern "C" int parc_env_profile_step(ParcEnv *e, const float *action_dev, void *
 #include "parc_motion_opt.hpp"   // parc_mopt_*: the batched kinematic motion optimiser (its own handle; uses parc_math.hpp and fail())
 #include "parc_motion_terrain.hpp"   // parc_mterr_*: motion-terrain analysis (its own handle; reuses the motion optimiser FK, sdBox and clip layout)
 #include "parc_motion_sampler.hpp"   // parc_msamp_*: the generator's motion-window sampler (its own handle; reuses frame_blend, philox4, the optimiser FK and grid_index)
+#include "parc_path_planner.hpp"     // parc_pathplan_*: stage 2's batched A* terrain path planner (its own handle; reuses philox4)

@@ -141,6 +141,24 @@ class ParcMotionSamplerOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in MSAMP_OUTPUT_FIELDS]
 
 
+PATHPLAN_MAX_DIM, PATHPLAN_MAX_JUMP_RADIUS, PATHPLAN_JUMP_WORDS = 64, 8, 8   # PARC_PATHPLAN_*
+PATHPLAN_STATUS = ("FOUND", "NO_PATH", "OVER_MAX_COST", "BUDGET", "NO_DRAW")
+PATHPLAN_SETTINGS = ("max_z_diff", "max_jump_xy_dist", "max_jump_z_diff", "min_jump_z_diff", "w_z", "w_xy", "w_bumpy", "max_bumpy",
+                     "uniform_cost_max", "uniform_cost_min", "min_start_end_xy_dist", "max_cost")   # AStarSettings, in struct order
+PATHPLAN_OUTPUT_FIELDS = [("status", "i"), ("cost", "f"), ("num_nodes", "i"), ("nodes", "i"), ("num_points", "i"), ("points", "f"),
+                          ("start", "i"), ("goal", "i"), ("hf", "f"), ("pops", "i")]
+
+
+class ParcPathPlanParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("dim_x", C.c_int32), ("dim_y", C.c_int32), ("dx", C.c_float),
+                ("dy", C.c_float), ("min_point", C.c_float * 2)] + [(n, C.c_double) for n in PATHPLAN_SETTINGS] + \
+               [("simplify_terrain", C.c_int32), ("max_expansions", C.c_int32), ("max_nodes", C.c_int32), ("max_points", C.c_int32)]
+
+
+class ParcPathPlanOutputs(C.Structure):
+    _fields_ = [(n, {"f": f32p, "i": i32p}[t]) for n, t in PATHPLAN_OUTPUT_FIELDS]
+
+
 BUFFER_FIELDS = [
     ("char_root_pos", "f"), ("char_root_rot", "f"), ("char_root_vel", "f"), ("char_root_ang_vel", "f"),
     ("char_dof_pos", "f"), ("char_dof_vel", "f"), ("char_body_pos", "f"), ("contact_forces", "f"),
@@ -265,6 +283,12 @@ def load():
     lib.parc_msamp_enumerate.argtypes = [vp, C.c_int32, C.POINTER(ParcMotionSamplerOutputs), vp]
     lib.parc_msamp_plan_status.argtypes = [vp, vp, i32p]
     lib.parc_msamp_kernel_times.argtypes = [vp, f32p]
+    lib.parc_pathplan_create.argtypes = [C.POINTER(ParcPathPlanParams), C.POINTER(vp)]
+    lib.parc_pathplan_destroy.argtypes = [vp]
+    lib.parc_pathplan_destroy.restype = None
+    lib.parc_pathplan_run.argtypes = [vp, C.c_int32, f32p, i32p, i32p, C.c_uint64, C.c_uint64, C.POINTER(ParcPathPlanOutputs)]
+    lib.parc_pathplan_get_graph.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)]
+    lib.parc_pathplan_kernel_times.argtypes = [vp, f32p]
     _lib = lib
     return lib
 
@@ -285,6 +309,7 @@ EXPORTED_SYMBOLS = [
     "parc_mterr_get_min_heights", "parc_mterr_point_sdf", "parc_mterr_kernel_times",
     "parc_msamp_create", "parc_msamp_destroy", "parc_msamp_set_clips", "parc_msamp_sample_with", "parc_msamp_draw_plan",
     "parc_msamp_sample", "parc_msamp_enumerate", "parc_msamp_plan_status", "parc_msamp_kernel_times",
+    "parc_pathplan_create", "parc_pathplan_destroy", "parc_pathplan_run", "parc_pathplan_get_graph", "parc_pathplan_kernel_times",
 ]
 
 # parc_test_quat_op selectors (include/parc_env.h)
