@@ -2966,7 +2966,8 @@ extern "C" int parc_env_profile_step(ParcEnv *e, const float *action_dev, void *
     return PARC_OK;
 }
 
-#include "parc_motion_opt.hpp"   // parc_mopt_*: the batched kinematic motion optimiser (its own handle; uses parc_math.hpp and fail())
-#include "parc_motion_terrain.hpp"   // parc_mterr_*: motion-terrain analysis (its own handle; reuses the motion optimiser FK, sdBox and clip layout)
-#include "parc_motion_sampler.hpp"   // parc_msamp_*: the generator's motion-window sampler (its own handle; reuses frame_blend, philox4, the optimiser FK and grid_index)
-#include "parc_path_planner.hpp"     // parc_pathplan_*: stage 2's batched A* terrain path planner (its own handle; reuses philox4)
+#include "parc_clip_batch.hpp"   // host code the four handles below share: the device arena, mopt::Model setup, clip-batch validation and upload (uses fail(), HIPCHK)
+#include "parc_motion_opt.hpp"   // parc_mopt_*: the batched kinematic motion optimiser (its own handle; uses parc_math.hpp; defines mopt::Model / mopt::Clips)
+#include "parc_motion_terrain.hpp"   // parc_mterr_*: motion-terrain analysis (its own handle; reuses the motion optimiser FK, sdBox, model and clip layout)
+#include "parc_motion_sampler.hpp"   // parc_msamp_*: the generator's motion-window sampler (its own handle; reuses frame_blend, philox4, the optimiser FK, model and clip layout, grid_index)
+#include "parc_path_planner.hpp"     // parc_pathplan_*: stage 2's batched A* terrain path planner (its own handle; reuses philox4 and the device arena)

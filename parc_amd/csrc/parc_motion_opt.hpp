@@ -553,7 +553,7 @@ struct ParcMotionOpt {
     mopt::Model *d_model = nullptr;
     mopt::Clips K{};
     mopt::Work W{};
-    std::vector<void *> allocs;           // everything of the current batch
+    DeviceArena batch;                    // everything of the current batch
     long long F = 0, adam_t = 0, ncons = 0;
     float step_size = 1e-3f;
     hipEvent_t ev[7] = {};
@@ -561,23 +561,11 @@ struct ParcMotionOpt {
 };
 
 static void mopt_free_batch(ParcMotionOpt *h) {
-    for (void *p : h->allocs) (void)hipFree(p);
-    h->allocs.clear();
+    h->batch.release();
     h->K = mopt::Clips{};
     h->W = mopt::Work{};
     h->F = 0;
 }
-
-template <typename T> static int mopt_alloc(ParcMotionOpt *h, T *&p, long long count, const void *src = nullptr) {
-    void *d = nullptr;
-    const size_t bytes = count > 0 ? (size_t)count * sizeof(T) : 16;
-    HIPCHK(hipMalloc(&d, bytes));
-    h->allocs.push_back(d);
-    if (src && count > 0) HIPCHK(hipMemcpy(d, src, (size_t)count * sizeof(T), hipMemcpyHostToDevice));
-    p = (T *)d;
-    return PARC_OK;
-}
-#define MOPT_ALLOC(...) do { if (int _rc = mopt_alloc(__VA_ARGS__)) return _rc; } while (0)
 
 extern "C" void parc_mopt_destroy(ParcMotionOpt *h) {
     if (!h) return;
@@ -597,71 +585,39 @@ extern "C" int parc_mopt_create(const ParcMotionOptParams *p, ParcMotionOpt **ou
     if (p->num_points < 1 || p->num_points > PARC_MOPT_MAX_POINTS || !p->points_host || !p->point_body_host)
         return fail(PARC_ERR_INVALID, "mopt: num_points must be in [1, 512] with points and point bodies given");
     mopt::Model M;
-    memset(&M, 0, sizeof(M));
-    M.B = cm.num_bodies; M.D = cm.dof_size; M.NP = PARC_MOPT_NP(cm.dof_size); M.P = p->num_points;
+    PARC_TRY(model_tree("mopt", cm, M));
+    M.NP = PARC_MOPT_NP(cm.dof_size);
     for (int b = 0; b < M.B; ++b) {
-        M.parent[b] = cm.parent[b]; M.jtype[b] = cm.joint_type[b]; M.dof_idx[b] = cm.dof_idx[b];
-        if (b > 0 && (cm.parent[b] < 0 || cm.parent[b] >= b)) return fail(PARC_ERR_INVALID, "mopt: parents must precede their children");
         const int dd = cm.joint_type[b] == PARC_JOINT_HINGE ? 1 : (cm.joint_type[b] == PARC_JOINT_SPHERICAL ? 3 : 0);
         if (b > 0 && dd && (cm.dof_idx[b] < 0 || cm.dof_idx[b] + dd > cm.dof_size)) return fail(PARC_ERR_INVALID, "mopt: dof_idx out of range");
-        for (int k = 0; k < 3; ++k) { M.lt[b][k] = cm.local_translation[b][k]; M.axis[b][k] = cm.joint_axis[b][k]; M.g0off[b][k] = p->geom0_offset[b][k]; }
-        for (int k = 0; k < 4; ++k) M.lr[b][k] = cm.local_rotation[b][k];
+        for (int k = 0; k < 3; ++k) M.g0off[b][k] = p->geom0_offset[b][k];
         M.g0type[b] = p->geom0_type[b]; M.g0rad[b] = p->geom0_radius[b];
-        M.contact_id[b] = p->contact_body_id[b];
-        if (M.contact_id[b] >= M.B) return fail(PARC_ERR_INVALID, "mopt: contact_body_id out of range");
     }
-    int prev = -1;
-    for (int k = 0; k < M.P; ++k) {
-        const int b = p->point_body_host[k];
-        if (b < 0 || b >= M.B || b < prev) return fail(PARC_ERR_INVALID, "mopt: point bodies must be in [0, B) and non-decreasing");
-        if (b != prev) M.pt_start[b] = k;
-        M.pt_count[b]++;
-        prev = b;
-        M.pt_body[k] = b;
-        for (int d = 0; d < 3; ++d) M.pts[k][d] = p->points_host[3 * k + d];
-    }
+    PARC_TRY(model_points("mopt", M, p->num_points, p->points_host, p->point_body_host, p->contact_body_id));
     for (int t = 0; t < mopt::NT; ++t) M.w[t] = p->weights[t];
     const double dt = 1.0 / 30.0;
     M.max_jerk = (float)((double)p->max_jerk * (dt * dt * dt));
     ParcMotionOpt *h = new (std::nothrow) ParcMotionOpt();
     if (!h) return fail(PARC_ERR_INVALID, "mopt: out of host memory");
     h->device = p->device; h->host_model = M; h->step_size = p->step_size;
-    hipError_t e = hipSetDevice(p->device);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_model, sizeof(M));
-    if (e == hipSuccess) e = hipMemcpy(h->d_model, &M, sizeof(M), hipMemcpyHostToDevice);
+    hipError_t e = model_upload(p->device, M, &h->d_model);
     for (int i = 0; i < 7 && e == hipSuccess; ++i) e = hipEventCreate(&h->ev[i]);
     if (e != hipSuccess) { parc_mopt_destroy(h); return fail(PARC_ERR_HIP, std::string("mopt create: ") + hipGetErrorString(e)); }
     *out = h;
     return PARC_OK;
 }
 
-static unsigned mopt_blocks(long long n, int t) { return (unsigned)((n + t - 1) / t); }
-
 extern "C" int parc_mopt_set_clips(ParcMotionOpt *h, const ParcMotionOptClips *c) {
     if (!h || !c) return fail(PARC_ERR_INVALID, "mopt: null argument");
-    const int C = c->num_clips;
-    if (C < 1) return fail(PARC_ERR_INVALID, "mopt: num_clips must be >= 1");
-    if (!c->frame_off_host || !c->hf_off_host || !c->cons_off_host || !c->hf_dims_host || !c->hf_geom_host || !c->hf_host ||
-        !c->root_pos_host || !c->root_rot_host || !c->joint_rot_host || !c->contacts_host)
-        return fail(PARC_ERR_INVALID, "mopt: null clip array");
-    const int B = h->host_model.B, NP = h->host_model.NP;
-    if (c->frame_off_host[0] != 0 || c->hf_off_host[0] != 0 || c->cons_off_host[0] != 0) return fail(PARC_ERR_INVALID, "mopt: offsets must start at 0");
-    std::vector<int> frame_clip;
-    std::vector<float> hf_min(C);
-    for (int i = 0; i < C; ++i) {
-        const long long nf = c->frame_off_host[i + 1] - c->frame_off_host[i];
-        const long long X = c->hf_dims_host[2 * i], Y = c->hf_dims_host[2 * i + 1];
-        if (nf < 1) return fail(PARC_ERR_INVALID, "mopt: clip " + std::to_string(i) + " has no frames");
-        if (X < 1 || Y < 1 || c->hf_off_host[i + 1] - c->hf_off_host[i] != X * Y) return fail(PARC_ERR_INVALID, "mopt: heightfield dims / offsets disagree");
-        if (!(c->hf_geom_host[4 * i + 2] > 0.f) || !(c->hf_geom_host[4 * i + 3] > 0.f)) return fail(PARC_ERR_INVALID, "mopt: dx must be > 0");
+    PARC_TRY(clip_batch_arrays("mopt", c));
+    if (!c->cons_off_host) return fail(PARC_ERR_INVALID, "mopt: null clip array");
+    if (c->cons_off_host[0] != 0) return fail(PARC_ERR_INVALID, "mopt: offsets must start at 0");
+    ClipBatch cb;
+    PARC_TRY(clip_batch_clips("mopt", c, cb));
+    const int C = cb.C, B = h->host_model.B, NP = h->host_model.NP;
+    for (int i = 0; i < C; ++i)
         if (c->cons_off_host[i + 1] < c->cons_off_host[i]) return fail(PARC_ERR_INVALID, "mopt: constraint offsets decrease");
-        float mn = INFINITY;
-        for (long long k = c->hf_off_host[i]; k < c->hf_off_host[i + 1]; ++k) mn = fminf(mn, c->hf_host[k]);
-        hf_min[i] = mn;
-        frame_clip.insert(frame_clip.end(), (size_t)nf, i);
-    }
-    const long long F = c->frame_off_host[C], ncons = c->cons_off_host[C], ncell = c->hf_off_host[C];
-    if (F > 0x7fffffffLL) return fail(PARC_ERR_INVALID, "mopt: at most 2^31 - 1 frames per batch");
+    const long long F = cb.F, ncons = c->cons_off_host[C];
     if (ncons > 0 && (!c->cons_body_host || !c->cons_range_host || !c->cons_point_host)) return fail(PARC_ERR_INVALID, "mopt: null constraint array");
     for (long long q = 0; q < ncons; ++q)
         if (c->cons_body_host[q] < 0 || c->cons_body_host[q] >= B) return fail(PARC_ERR_INVALID, "mopt: constraint body out of range");
@@ -669,39 +625,31 @@ extern "C" int parc_mopt_set_clips(ParcMotionOpt *h, const ParcMotionOptClips *c
     mopt_free_batch(h);
     mopt::Clips &K = h->K;
     mopt::Work &W = h->W;
-    K.C = C; K.F = F;
-    MOPT_ALLOC(h, K.frame_off, C + 1, c->frame_off_host);
-    MOPT_ALLOC(h, K.hf_off, C + 1, c->hf_off_host);
-    MOPT_ALLOC(h, K.cons_off, C + 1, c->cons_off_host);
-    MOPT_ALLOC(h, K.frame_clip, F, frame_clip.data());
-    MOPT_ALLOC(h, K.hf_dims, 2 * C, c->hf_dims_host);
-    MOPT_ALLOC(h, K.hf_geom, 4 * C, c->hf_geom_host);
-    MOPT_ALLOC(h, K.hf, ncell, c->hf_host);
-    MOPT_ALLOC(h, K.hf_min, C, hf_min.data());
-    MOPT_ALLOC(h, K.src_root_pos, 3 * F, c->root_pos_host);
-    MOPT_ALLOC(h, K.src_root_rot, 4 * F, c->root_rot_host);
-    MOPT_ALLOC(h, K.src_jrot, 4 * F * (B - 1), c->joint_rot_host);
-    MOPT_ALLOC(h, K.contacts, F * B, c->contacts_host);
-    MOPT_ALLOC(h, K.src_pos, 3 * F * B);
-    MOPT_ALLOC(h, K.src_rot, 4 * F * B);
-    MOPT_ALLOC(h, K.cons_body, ncons, c->cons_body_host);
-    MOPT_ALLOC(h, K.cons_range, 2 * ncons, c->cons_range_host);
-    MOPT_ALLOC(h, K.cons_point, 3 * ncons, c->cons_point_host);
-    MOPT_ALLOC(h, W.params, F * NP);
-    MOPT_ALLOC(h, W.grad, F * NP);
-    MOPT_ALLOC(h, W.m, F * NP);
-    MOPT_ALLOC(h, W.v, F * NP);
-    MOPT_ALLOC(h, W.pos, 3 * F * B);
-    MOPT_ALLOC(h, W.rot, 4 * F * B);
-    MOPT_ALLOC(h, W.jrot, 4 * F * B);
-    MOPT_ALLOC(h, W.gpos, 3 * F * B);
-    MOPT_ALLOC(h, W.grot, 4 * F * B);
-    MOPT_ALLOC(h, W.gbox, 4 * F);
-    MOPT_ALLOC(h, W.patch, 2 * C);
-    MOPT_ALLOC(h, W.fterms, F * mopt::NT);
-    MOPT_ALLOC(h, W.terms, (long long)C * mopt::NT);
+    DeviceArena &mem = h->batch;
+    PARC_TRY(clip_batch_upload(mem, K, c, cb, B));
+    PARC_TRY(mem.alloc(K.cons_off, C + 1, c->cons_off_host));
+    PARC_TRY(mem.alloc(K.frame_clip, F, cb.frame_clip.data()));
+    PARC_TRY(mem.alloc(K.hf_min, C, cb.hf_min.data()));
+    PARC_TRY(mem.alloc(K.src_pos, 3 * F * B));
+    PARC_TRY(mem.alloc(K.src_rot, 4 * F * B));
+    PARC_TRY(mem.alloc(K.cons_body, ncons, c->cons_body_host));
+    PARC_TRY(mem.alloc(K.cons_range, 2 * ncons, c->cons_range_host));
+    PARC_TRY(mem.alloc(K.cons_point, 3 * ncons, c->cons_point_host));
+    PARC_TRY(mem.alloc(W.params, F * NP));
+    PARC_TRY(mem.alloc(W.grad, F * NP));
+    PARC_TRY(mem.alloc(W.m, F * NP));
+    PARC_TRY(mem.alloc(W.v, F * NP));
+    PARC_TRY(mem.alloc(W.pos, 3 * F * B));
+    PARC_TRY(mem.alloc(W.rot, 4 * F * B));
+    PARC_TRY(mem.alloc(W.jrot, 4 * F * B));
+    PARC_TRY(mem.alloc(W.gpos, 3 * F * B));
+    PARC_TRY(mem.alloc(W.grot, 4 * F * B));
+    PARC_TRY(mem.alloc(W.gbox, 4 * F));
+    PARC_TRY(mem.alloc(W.patch, 2 * C));
+    PARC_TRY(mem.alloc(W.fterms, F * mopt::NT));
+    PARC_TRY(mem.alloc(W.terms, (long long)C * mopt::NT));
     h->F = F; h->ncons = ncons; h->adam_t = 0;
-    hipLaunchKernelGGL(mopt::k_mopt_source, dim3(mopt_blocks(F, 64)), dim3(64), 0, 0, h->d_model, K, W);
+    hipLaunchKernelGGL(mopt::k_mopt_source, dim3(blocks(F, 64)), dim3(64), 0, 0, h->d_model, K, W);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     return PARC_OK;
@@ -746,19 +694,19 @@ static int mopt_eval(ParcMotionOpt *h, bool timed) {
     const long long F = h->F;
     const int C = h->K.C;
     if (timed) HIPCHK(hipEventRecord(h->ev[0], 0));
-    hipLaunchKernelGGL(mopt::k_mopt_fk, dim3(mopt_blocks(F, 64)), dim3(64), 0, 0, h->d_model, h->K, h->W);
+    hipLaunchKernelGGL(mopt::k_mopt_fk, dim3(blocks(F, 64)), dim3(64), 0, 0, h->d_model, h->K, h->W);
     HIPCHK(hipGetLastError());
     if (timed) HIPCHK(hipEventRecord(h->ev[1], 0));
-    hipLaunchKernelGGL(mopt::k_mopt_patch, dim3(mopt_blocks(C, 64)), dim3(64), 0, 0, h->K, h->W);
+    hipLaunchKernelGGL(mopt::k_mopt_patch, dim3(blocks(C, 64)), dim3(64), 0, 0, h->K, h->W);
     HIPCHK(hipGetLastError());
     if (timed) HIPCHK(hipEventRecord(h->ev[2], 0));
     hipLaunchKernelGGL(mopt::k_mopt_points, dim3((unsigned)F), dim3(mopt::PT_THREADS), 0, 0, h->d_model, h->K, h->W);
     HIPCHK(hipGetLastError());
     if (timed) HIPCHK(hipEventRecord(h->ev[3], 0));
-    hipLaunchKernelGGL(mopt::k_mopt_grad, dim3(mopt_blocks(F, 64)), dim3(64), 0, 0, h->d_model, h->K, h->W);
+    hipLaunchKernelGGL(mopt::k_mopt_grad, dim3(blocks(F, 64)), dim3(64), 0, 0, h->d_model, h->K, h->W);
     HIPCHK(hipGetLastError());
     if (timed) HIPCHK(hipEventRecord(h->ev[4], 0));
-    hipLaunchKernelGGL(mopt::k_mopt_reduce, dim3(mopt_blocks((long long)C * mopt::NT, 64)), dim3(64), 0, 0, h->K, h->W);
+    hipLaunchKernelGGL(mopt::k_mopt_reduce, dim3(blocks((long long)C * mopt::NT, 64)), dim3(64), 0, 0, h->K, h->W);
     HIPCHK(hipGetLastError());
     if (timed) HIPCHK(hipEventRecord(h->ev[5], 0));
     return PARC_OK;
@@ -784,7 +732,7 @@ extern "C" int parc_mopt_step(ParcMotionOpt *h, int32_t n_iters, float *terms) {
         if (int rc = mopt_eval(h, true)) return rc;
         h->adam_t++;
         const double bc1 = 1.0 - pow(0.9, (double)h->adam_t), bc2 = 1.0 - pow(0.999, (double)h->adam_t);
-        hipLaunchKernelGGL(mopt::k_mopt_adam, dim3(mopt_blocks(n, 256)), dim3(256), 0, 0, h->W, n, (float)((double)h->step_size / bc1),
+        hipLaunchKernelGGL(mopt::k_mopt_adam, dim3(blocks(n, 256)), dim3(256), 0, 0, h->W, n, (float)((double)h->step_size / bc1),
                            (float)sqrt(bc2));
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(h->ev[6], 0));
@@ -810,7 +758,7 @@ extern "C" int parc_mopt_kernel_times(ParcMotionOpt *h, float *ms6) {
 extern "C" int parc_mopt_get_frames(ParcMotionOpt *h, float *root_pos, float *root_rot, float *joint_rot) {
     if (int rc = mopt_check(h)) return rc;
     HIPCHK(hipSetDevice(h->device));
-    hipLaunchKernelGGL(mopt::k_mopt_fk, dim3(mopt_blocks(h->F, 64)), dim3(64), 0, 0, h->d_model, h->K, h->W);
+    hipLaunchKernelGGL(mopt::k_mopt_fk, dim3(blocks(h->F, 64)), dim3(64), 0, 0, h->d_model, h->K, h->W);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     const int B = h->host_model.B, NP = h->host_model.NP;
@@ -847,7 +795,7 @@ extern "C" int parc_mopt_build_constraints(ParcMotionOpt *h, int32_t n, const in
     if (e == hipSuccess) e = hipMemcpy(d_clip, clip, n * sizeof(int), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_pts, pts, 3 * (size_t)n * sizeof(float), hipMemcpyHostToDevice);
     for (int s = 0; s < steps && e == hipSuccess; ++s) {
-        hipLaunchKernelGGL(mopt::k_mopt_cons_sgd, dim3(mopt_blocks(n, 64)), dim3(64), 0, 0, h->K, d_clip, d_pts, n, lr);
+        hipLaunchKernelGGL(mopt::k_mopt_cons_sgd, dim3(blocks(n, 64)), dim3(64), 0, 0, h->K, d_clip, d_pts, n, lr);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(pts, d_pts, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost);

@@ -343,8 +343,8 @@ struct ParcMotionSampler {
     msamp::Cfg cfg{};
     mopt::Clips K{};
     msamp::Lib L{};
-    std::vector<void *> allocs;           // the library
-    std::vector<void *> tables;           // times / grid tables (create)
+    DeviceArena lib;                      // the library (set_clips)
+    DeviceArena tables;                   // times / grid tables (create)
     std::vector<int> clip_windows;        // num_frames - T per clip
     int bit_words = 0;                    // words of the largest terrain's cell bitset
     int *d_status = nullptr;
@@ -352,20 +352,8 @@ struct ParcMotionSampler {
     bool timed = false, drew = false;
 };
 
-template <typename T> static int msamp_alloc(std::vector<void *> &keep, T *&p, long long count, const void *src = nullptr) {
-    void *d = nullptr;
-    const size_t bytes = count > 0 ? (size_t)count * sizeof(T) : 16;
-    HIPCHK(hipMalloc(&d, bytes));
-    keep.push_back(d);
-    if (src && count > 0) HIPCHK(hipMemcpy(d, src, (size_t)count * sizeof(T), hipMemcpyHostToDevice));
-    p = (T *)d;
-    return PARC_OK;
-}
-#define MSAMP_ALLOC(...) do { if (int _rc = msamp_alloc(__VA_ARGS__)) return _rc; } while (0)
-
 static void msamp_free_lib(ParcMotionSampler *h) {
-    for (void *p : h->allocs) (void)hipFree(p);
-    h->allocs.clear();
+    h->lib.release();
     h->K = mopt::Clips{};
     h->L = msamp::Lib{};
     h->clip_windows.clear();
@@ -376,7 +364,7 @@ extern "C" void parc_msamp_destroy(ParcMotionSampler *h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     msamp_free_lib(h);
-    for (void *p : h->tables) (void)hipFree(p);
+    h->tables.release();
     if (h->d_model) (void)hipFree(h->d_model);
     if (h->d_status) (void)hipFree(h->d_status);
     for (int i = 0; i < 4; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
@@ -384,14 +372,12 @@ extern "C" void parc_msamp_destroy(ParcMotionSampler *h) {
 }
 
 static int msamp_create_device(ParcMotionSampler *h, const ParcMotionSamplerParams *p) {
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipMalloc((void **)&h->d_model, sizeof(mopt::Model)));
-    HIPCHK(hipMemcpy(h->d_model, &h->host_model, sizeof(mopt::Model), hipMemcpyHostToDevice));
+    HIPCHK(model_upload(p->device, h->host_model, &h->d_model));
     HIPCHK(hipMalloc((void **)&h->d_status, sizeof(int)));
     HIPCHK(hipMemset(h->d_status, 0, sizeof(int)));
-    MSAMP_ALLOC(h->tables, h->cfg.times, p->num_frames, p->times_host);
-    MSAMP_ALLOC(h->tables, h->cfg.gridx, p->grid_dim_x, p->grid_x_host);
-    MSAMP_ALLOC(h->tables, h->cfg.gridy, p->grid_dim_y, p->grid_y_host);
+    PARC_TRY(h->tables.alloc(h->cfg.times, p->num_frames, p->times_host));
+    PARC_TRY(h->tables.alloc(h->cfg.gridx, p->grid_dim_x, p->grid_x_host));
+    PARC_TRY(h->tables.alloc(h->cfg.gridy, p->grid_dim_y, p->grid_y_host));
     for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreate(&h->ev[i]));
     return PARC_OK;
 }
@@ -414,14 +400,7 @@ extern "C" int parc_msamp_create(const ParcMotionSamplerParams *p, ParcMotionSam
         return fail(PARC_ERR_INVALID, "msamp: max_num_boxes must be in [0, " + std::to_string(PARC_MSAMP_MAX_BOXES) + "], hf_max_maxpool_size >= 0");
     if (!(p->timestep > 0.f) || !(p->dx > 0.f)) return fail(PARC_ERR_INVALID, "msamp: sequence_fps and horizontal_scale must be > 0");
     mopt::Model M;
-    memset(&M, 0, sizeof(M));
-    M.B = cm.num_bodies; M.D = cm.dof_size;
-    for (int b = 0; b < M.B; ++b) {
-        M.parent[b] = cm.parent[b]; M.jtype[b] = cm.joint_type[b]; M.dof_idx[b] = cm.dof_idx[b];
-        if (b > 0 && (cm.parent[b] < 0 || cm.parent[b] >= b)) return fail(PARC_ERR_INVALID, "msamp: parents must precede their children");
-        for (int k = 0; k < 3; ++k) { M.lt[b][k] = cm.local_translation[b][k]; M.axis[b][k] = cm.joint_axis[b][k]; }
-        for (int k = 0; k < 4; ++k) M.lr[b][k] = cm.local_rotation[b][k];
-    }
+    PARC_TRY(model_tree("msamp", cm, M));
     ParcMotionSampler *h = new (std::nothrow) ParcMotionSampler();
     if (!h) return fail(PARC_ERR_INVALID, "msamp: out of host memory");
     h->device = p->device; h->host_model = M;
@@ -440,16 +419,12 @@ extern "C" int parc_msamp_create(const ParcMotionSamplerParams *p, ParcMotionSam
 
 extern "C" int parc_msamp_set_clips(ParcMotionSampler *h, const ParcMotionOptClips *c, const ParcMotionSamplerClipInfo *info) {
     if (!h || !c || !info) return fail(PARC_ERR_INVALID, "msamp: null argument");
-    const int C = c->num_clips;
-    if (C < 1) return fail(PARC_ERR_INVALID, "msamp: num_clips must be >= 1");
-    if (!c->frame_off_host || !c->hf_off_host || !c->hf_dims_host || !c->hf_geom_host || !c->hf_host || !c->root_pos_host ||
-        !c->root_rot_host || !c->joint_rot_host || !c->contacts_host || !info->hf_maxmin_host || !info->mask_off_host ||
-        !info->fps_host || !info->loop_modes_host || !info->weights_host)
+    PARC_TRY(clip_batch_arrays("msamp", c));
+    if (!info->hf_maxmin_host || !info->mask_off_host || !info->fps_host || !info->loop_modes_host || !info->weights_host)
         return fail(PARC_ERR_INVALID, "msamp: null clip array");
-    if (c->frame_off_host[0] != 0 || c->hf_off_host[0] != 0 || info->mask_off_host[0] != 0) return fail(PARC_ERR_INVALID, "msamp: offsets must start at 0");
-    const int B = h->host_model.B, T = h->cfg.T;
-    const long long F = c->frame_off_host[C], ncell = c->hf_off_host[C];
-    if (F > 0x7fffffffLL) return fail(PARC_ERR_INVALID, "msamp: at most 2^31 - 1 frames");
+    if (info->mask_off_host[0] != 0) return fail(PARC_ERR_INVALID, "msamp: offsets must start at 0");
+    const int C = c->num_clips, B = h->host_model.B, T = h->cfg.T;
+    if (c->frame_off_host[C] > 0x7fffffffLL) return fail(PARC_ERR_INVALID, "msamp: at most 2^31 - 1 frames");
     std::vector<MotionMeta> meta((size_t)C);
     std::vector<float> cdf((size_t)C);
     std::vector<int> windows((size_t)C);
@@ -460,18 +435,22 @@ extern "C" int parc_msamp_set_clips(ParcMotionSampler *h, const ParcMotionOptCli
         wsum += info->weights_host[i];
     }
     if (!(wsum > 0.0)) return fail(PARC_ERR_INVALID, "msamp: the weights sum to 0");
+    for (int i = 0; i < C; ++i) {   // before the shared per-clip checks: a clip without frames is refused as too short as well
+        const long long nf = c->frame_off_host[i + 1] - c->frame_off_host[i];
+        if (nf - T <= 0)   // get_motion_sequences_for_id asserts; _sample_motion_start_times would draw a negative start time
+            return fail(PARC_ERR_INVALID, "msamp: clip " + std::to_string(i) + " is too short: " + std::to_string(nf) + " frames for windows of " +
+                                              std::to_string(T));
+    }
+    ClipBatch cb;
+    PARC_TRY(clip_batch_clips("msamp", c, cb));
+    const long long F = cb.F, ncell = cb.ncell;
     float run = 0.f;
     for (int i = 0; i < C; ++i) {
         const long long f0 = c->frame_off_host[i], nf = c->frame_off_host[i + 1] - f0;
         const long long X = c->hf_dims_host[2 * i], Y = c->hf_dims_host[2 * i + 1];
-        if (nf - T <= 0)   // get_motion_sequences_for_id asserts; _sample_motion_start_times would draw a negative start time
-            return fail(PARC_ERR_INVALID, "msamp: clip " + std::to_string(i) + " is too short: " + std::to_string(nf) + " frames for windows of " +
-                                              std::to_string(T));
-        if (X < 1 || Y < 1 || c->hf_off_host[i + 1] - c->hf_off_host[i] != X * Y) return fail(PARC_ERR_INVALID, "msamp: heightfield dims / offsets disagree");
         if (X * Y > PARC_MSAMP_MAX_TERRAIN_CELLS)
             return fail(PARC_ERR_INVALID, "msamp: the terrain of clip " + std::to_string(i) + " has " + std::to_string(X * Y) + " cells, above the limit of " +
                                               std::to_string(PARC_MSAMP_MAX_TERRAIN_CELLS) + " (the window mask is a bitset in LDS)");
-        if (!(c->hf_geom_host[4 * i + 2] > 0.f) || !(c->hf_geom_host[4 * i + 3] > 0.f)) return fail(PARC_ERR_INVALID, "msamp: dx must be > 0");
         if (info->fps_host[i] < 1) return fail(PARC_ERR_INVALID, "msamp: fps must be >= 1");
         for (long long f = f0; f < f0 + nf; ++f) {
             if (info->mask_off_host[f + 1] < info->mask_off_host[f]) return fail(PARC_ERR_INVALID, "msamp: mask offsets must not decrease");
@@ -493,21 +472,13 @@ extern "C" int parc_msamp_set_clips(ParcMotionSampler *h, const ParcMotionOptCli
     msamp_free_lib(h);
     mopt::Clips &K = h->K;
     msamp::Lib &L = h->L;
-    K.C = C; K.F = F;
-    MSAMP_ALLOC(h->allocs, K.frame_off, C + 1, c->frame_off_host);
-    MSAMP_ALLOC(h->allocs, K.hf_off, C + 1, c->hf_off_host);
-    MSAMP_ALLOC(h->allocs, K.hf_dims, 2 * C, c->hf_dims_host);
-    MSAMP_ALLOC(h->allocs, K.hf_geom, 4 * C, c->hf_geom_host);
-    MSAMP_ALLOC(h->allocs, K.hf, ncell, c->hf_host);
-    MSAMP_ALLOC(h->allocs, K.src_root_pos, 3 * F, c->root_pos_host);
-    MSAMP_ALLOC(h->allocs, K.src_root_rot, 4 * F, c->root_rot_host);
-    MSAMP_ALLOC(h->allocs, K.src_jrot, 4 * F * (B - 1), c->joint_rot_host);
-    MSAMP_ALLOC(h->allocs, K.contacts, F * B, c->contacts_host);
-    MSAMP_ALLOC(h->allocs, L.meta, C, meta.data());
-    MSAMP_ALLOC(h->allocs, L.maxmin, 2 * ncell, info->hf_maxmin_host);
-    MSAMP_ALLOC(h->allocs, L.mask_off, F + 1, info->mask_off_host);
-    MSAMP_ALLOC(h->allocs, L.mask_cells, info->mask_off_host[F], info->mask_cells_host);
-    MSAMP_ALLOC(h->allocs, L.cdf, C, cdf.data());
+    DeviceArena &mem = h->lib;
+    PARC_TRY(clip_batch_upload(mem, K, c, cb, B));
+    PARC_TRY(mem.alloc(L.meta, C, meta.data()));
+    PARC_TRY(mem.alloc(L.maxmin, 2 * ncell, info->hf_maxmin_host));
+    PARC_TRY(mem.alloc(L.mask_off, F + 1, info->mask_off_host));
+    PARC_TRY(mem.alloc(L.mask_cells, info->mask_off_host[F], info->mask_cells_host));
+    PARC_TRY(mem.alloc(L.cdf, C, cdf.data()));
     h->clip_windows = windows;
     h->bit_words = bit_words;
     return PARC_OK;

@@ -370,7 +370,7 @@ struct ParcMotionTerrain {
     mterr::Cfg cfg{};
     mopt::Clips K{};
     mterr::Work W{};
-    std::vector<void *> allocs;           // everything of the current batch
+    DeviceArena batch;                    // everything of the current batch
     std::vector<int> counts;              // per-frame mask counts of the last run
     std::vector<long long> offsets;
     long long F = 0, ncell = 0, total = 0;
@@ -382,24 +382,12 @@ struct ParcMotionTerrain {
 };
 
 static void mterr_free_batch(ParcMotionTerrain *h) {
-    for (void *p : h->allocs) (void)hipFree(p);
-    h->allocs.clear();
+    h->batch.release();
     h->K = mopt::Clips{};
     h->W = mterr::Work{};
     h->F = h->ncell = h->total = 0;
     h->ran = false;
 }
-
-template <typename T> static int mterr_alloc(ParcMotionTerrain *h, T *&p, long long count, const void *src = nullptr) {
-    void *d = nullptr;
-    const size_t bytes = count > 0 ? (size_t)count * sizeof(T) : 16;
-    HIPCHK(hipMalloc(&d, bytes));
-    h->allocs.push_back(d);
-    if (src && count > 0) HIPCHK(hipMemcpy(d, src, (size_t)count * sizeof(T), hipMemcpyHostToDevice));
-    p = (T *)d;
-    return PARC_OK;
-}
-#define MTERR_ALLOC(...) do { if (int _rc = mterr_alloc(__VA_ARGS__)) return _rc; } while (0)
 
 extern "C" void parc_mterr_destroy(ParcMotionTerrain *h) {
     if (!h) return;
@@ -421,26 +409,9 @@ extern "C" int parc_mterr_create(const ParcMotionTerrainParams *p, ParcMotionTer
         return fail(PARC_ERR_INVALID, "mterr: num_points must be in [1, 512] with points and point bodies given");
     if (p->sdf_mode != PARC_MTERR_SDF_PRUNED && p->sdf_mode != PARC_MTERR_SDF_BRUTE) return fail(PARC_ERR_INVALID, "mterr: unknown sdf_mode");
     mopt::Model M;
-    memset(&M, 0, sizeof(M));
-    M.B = cm.num_bodies; M.D = cm.dof_size; M.NP = PARC_MOPT_NP(cm.dof_size); M.P = p->num_points;
-    for (int b = 0; b < M.B; ++b) {
-        M.parent[b] = cm.parent[b]; M.jtype[b] = cm.joint_type[b]; M.dof_idx[b] = cm.dof_idx[b];
-        if (b > 0 && (cm.parent[b] < 0 || cm.parent[b] >= b)) return fail(PARC_ERR_INVALID, "mterr: parents must precede their children");
-        for (int k = 0; k < 3; ++k) { M.lt[b][k] = cm.local_translation[b][k]; M.axis[b][k] = cm.joint_axis[b][k]; }
-        for (int k = 0; k < 4; ++k) M.lr[b][k] = cm.local_rotation[b][k];
-        M.contact_id[b] = p->contact_body_id[b];
-        if (M.contact_id[b] >= M.B) return fail(PARC_ERR_INVALID, "mterr: contact_body_id out of range");
-    }
-    int prev = -1;
-    for (int k = 0; k < M.P; ++k) {
-        const int b = p->point_body_host[k];
-        if (b < 0 || b >= M.B || b < prev) return fail(PARC_ERR_INVALID, "mterr: point bodies must be in [0, B) and non-decreasing");
-        if (b != prev) M.pt_start[b] = k;
-        M.pt_count[b]++;
-        prev = b;
-        M.pt_body[k] = b;
-        for (int d = 0; d < 3; ++d) M.pts[k][d] = p->points_host[3 * k + d];
-    }
+    PARC_TRY(model_tree("mterr", cm, M));
+    M.NP = PARC_MOPT_NP(cm.dof_size);
+    PARC_TRY(model_points("mterr", M, p->num_points, p->points_host, p->point_body_host, p->contact_body_id));
     int sort_n = 1;
     while (sort_n < M.P) sort_n <<= 1;
     ParcMotionTerrain *h = new (std::nothrow) ParcMotionTerrain();
@@ -448,69 +419,44 @@ extern "C" int parc_mterr_create(const ParcMotionTerrainParams *p, ParcMotionTer
     h->device = p->device; h->host_model = M;
     h->cfg.sdf_mode = p->sdf_mode; h->cfg.sort_n = sort_n;
     h->cfg.z_buf = p->z_buf; h->cfg.jump_buf = (float)p->jump_buf; h->cfg.max_jerk = (float)p->max_jerk;
-    hipError_t e = hipSetDevice(p->device);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_model, sizeof(M));
-    if (e == hipSuccess) e = hipMemcpy(h->d_model, &M, sizeof(M), hipMemcpyHostToDevice);
+    hipError_t e = model_upload(p->device, M, &h->d_model);
     for (int i = 0; i < 8 && e == hipSuccess; ++i) e = hipEventCreate(&h->ev[i]);
     if (e != hipSuccess) { parc_mterr_destroy(h); return fail(PARC_ERR_HIP, std::string("mterr create: ") + hipGetErrorString(e)); }
     *out = h;
     return PARC_OK;
 }
 
-static unsigned mterr_blocks(long long n, int t) { return (unsigned)((n + t - 1) / t); }
-
 extern "C" int parc_mterr_set_clips(ParcMotionTerrain *h, const ParcMotionOptClips *c) {
     if (!h || !c) return fail(PARC_ERR_INVALID, "mterr: null argument");
-    const int C = c->num_clips;
-    if (C < 1) return fail(PARC_ERR_INVALID, "mterr: num_clips must be >= 1");
-    if (!c->frame_off_host || !c->hf_off_host || !c->hf_dims_host || !c->hf_geom_host || !c->hf_host || !c->root_pos_host ||
-        !c->root_rot_host || !c->joint_rot_host || !c->contacts_host)
-        return fail(PARC_ERR_INVALID, "mterr: null clip array");
-    const int B = h->host_model.B, P = h->host_model.P;
-    if (c->frame_off_host[0] != 0 || c->hf_off_host[0] != 0) return fail(PARC_ERR_INVALID, "mterr: offsets must start at 0");
-    std::vector<int> frame_clip;
-    std::vector<float> hf_min(C);
-    for (int i = 0; i < C; ++i) {
-        const long long nf = c->frame_off_host[i + 1] - c->frame_off_host[i];
+    PARC_TRY(clip_batch_arrays("mterr", c));
+    for (int i = 0; i < c->num_clips; ++i) {   // the cell-count bound (a cell index is an int in the kernels), under the analyser's own wording
         const long long X = c->hf_dims_host[2 * i], Y = c->hf_dims_host[2 * i + 1];
-        if (nf < 1) return fail(PARC_ERR_INVALID, "mterr: clip " + std::to_string(i) + " has no frames");
         if (X < 1 || Y < 1 || X * Y > 0x7fffffffLL || c->hf_off_host[i + 1] - c->hf_off_host[i] != X * Y)
             return fail(PARC_ERR_INVALID, "mterr: heightfield dims / offsets disagree (dims >= 1, at most 2^31 - 1 cells)");
-        if (!(c->hf_geom_host[4 * i + 2] > 0.f) || !(c->hf_geom_host[4 * i + 3] > 0.f)) return fail(PARC_ERR_INVALID, "mterr: dx must be > 0");
-        float mn = INFINITY;                                  // torch.min(hf).item()
-        for (long long k = c->hf_off_host[i]; k < c->hf_off_host[i + 1]; ++k) mn = fminf(mn, c->hf_host[k]);
-        hf_min[i] = mn;
-        frame_clip.insert(frame_clip.end(), (size_t)nf, i);
     }
-    const long long F = c->frame_off_host[C], ncell = c->hf_off_host[C];
-    if (F > 0x7fffffffLL) return fail(PARC_ERR_INVALID, "mterr: at most 2^31 - 1 frames per batch");
+    ClipBatch cb;
+    PARC_TRY(clip_batch_clips("mterr", c, cb));
+    const int C = cb.C, B = h->host_model.B, P = h->host_model.P;
+    const long long F = cb.F, ncell = cb.ncell;
     HIPCHK(hipSetDevice(h->device));
     mterr_free_batch(h);
     mopt::Clips &K = h->K;
     mterr::Work &W = h->W;
-    K.C = C; K.F = F;
-    MTERR_ALLOC(h, K.frame_off, C + 1, c->frame_off_host);
-    MTERR_ALLOC(h, K.hf_off, C + 1, c->hf_off_host);
-    MTERR_ALLOC(h, K.frame_clip, F, frame_clip.data());
-    MTERR_ALLOC(h, K.hf_dims, 2 * C, c->hf_dims_host);
-    MTERR_ALLOC(h, K.hf_geom, 4 * C, c->hf_geom_host);
-    MTERR_ALLOC(h, K.hf, ncell, c->hf_host);
-    MTERR_ALLOC(h, K.hf_min, C, hf_min.data());
-    MTERR_ALLOC(h, K.src_root_pos, 3 * F, c->root_pos_host);
-    MTERR_ALLOC(h, K.src_root_rot, 4 * F, c->root_rot_host);
-    MTERR_ALLOC(h, K.src_jrot, 4 * F * (B - 1), c->joint_rot_host);
-    MTERR_ALLOC(h, K.contacts, F * B, c->contacts_host);
-    MTERR_ALLOC(h, W.pos, 3 * F * B);
-    MTERR_ALLOC(h, W.rot, 4 * F * B);
-    MTERR_ALLOC(h, W.valid, F);
-    MTERR_ALLOC(h, W.fterms, F * mterr::NS);
-    MTERR_ALLOC(h, W.keys, F * P);
-    MTERR_ALLOC(h, W.cnt, F);
-    MTERR_ALLOC(h, W.ind_off, F);
-    MTERR_ALLOC(h, W.minh, ncell);
-    MTERR_ALLOC(h, W.touched, ncell);
-    MTERR_ALLOC(h, W.maxmin, 2 * ncell);
-    MTERR_ALLOC(h, W.clip_out, (long long)C * mterr::NOUT);
+    DeviceArena &mem = h->batch;
+    PARC_TRY(clip_batch_upload(mem, K, c, cb, B));
+    PARC_TRY(mem.alloc(K.frame_clip, F, cb.frame_clip.data()));
+    PARC_TRY(mem.alloc(K.hf_min, C, cb.hf_min.data()));
+    PARC_TRY(mem.alloc(W.pos, 3 * F * B));
+    PARC_TRY(mem.alloc(W.rot, 4 * F * B));
+    PARC_TRY(mem.alloc(W.valid, F));
+    PARC_TRY(mem.alloc(W.fterms, F * mterr::NS));
+    PARC_TRY(mem.alloc(W.keys, F * P));
+    PARC_TRY(mem.alloc(W.cnt, F));
+    PARC_TRY(mem.alloc(W.ind_off, F));
+    PARC_TRY(mem.alloc(W.minh, ncell));
+    PARC_TRY(mem.alloc(W.touched, ncell));
+    PARC_TRY(mem.alloc(W.maxmin, 2 * ncell));
+    PARC_TRY(mem.alloc(W.clip_out, (long long)C * mterr::NOUT));
     h->F = F; h->ncell = ncell;
     h->counts.assign((size_t)F, 0);
     h->offsets.assign((size_t)F, 0);
@@ -529,19 +475,19 @@ extern "C" int parc_mterr_run(ParcMotionTerrain *h, float *clip_out, int32_t *ma
     const long long F = h->F, ncell = h->ncell;
     const int C = h->K.C;
     HIPCHK(hipEventRecord(h->ev[0], 0));
-    hipLaunchKernelGGL(mterr::k_mterr_fk, dim3(mterr_blocks(F, 64)), dim3(64), 0, 0, h->d_model, h->K, h->W);
+    hipLaunchKernelGGL(mterr::k_mterr_fk, dim3(blocks(F, 64)), dim3(64), 0, 0, h->d_model, h->K, h->W);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev[1], 0));
-    hipLaunchKernelGGL(mterr::k_mterr_init, dim3(mterr_blocks(ncell, 256)), dim3(256), 0, 0, ncell, h->W);
+    hipLaunchKernelGGL(mterr::k_mterr_init, dim3(blocks(ncell, 256)), dim3(256), 0, 0, ncell, h->W);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev[2], 0));
     hipLaunchKernelGGL(mterr::k_mterr_points, dim3((unsigned)F), dim3(mterr::PT_THREADS), 0, 0, h->d_model, h->K, h->W, h->cfg);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev[3], 0));
-    hipLaunchKernelGGL(mterr::k_mterr_reduce, dim3(mterr_blocks(C, 64)), dim3(64), 0, 0, h->K, h->W, h->host_model.B);
+    hipLaunchKernelGGL(mterr::k_mterr_reduce, dim3(blocks(C, 64)), dim3(64), 0, 0, h->K, h->W, h->host_model.B);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev[4], 0));
-    hipLaunchKernelGGL(mterr::k_mterr_cells, dim3(mterr_blocks(ncell, 256)), dim3(256), 0, 0, h->K, h->W, h->cfg, ncell);
+    hipLaunchKernelGGL(mterr::k_mterr_cells, dim3(blocks(ncell, 256)), dim3(256), 0, 0, h->K, h->W, h->cfg, ncell);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev[5], 0));
     HIPCHK(hipMemcpy(h->counts.data(), h->W.cnt, (size_t)F * sizeof(int), hipMemcpyDeviceToHost));

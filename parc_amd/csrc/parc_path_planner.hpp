@@ -383,7 +383,7 @@ struct ParcPathPlanner {
     int device = 0;
     pplan::Cfg cfg{};
     pplan::Bufs B{};
-    std::vector<void *> allocs;
+    DeviceArena bufs;
     int cap = 0, last_q = 0;
     hipEvent_t ev[3] = {};
     float graph_ms = 0.f;
@@ -391,8 +391,7 @@ struct ParcPathPlanner {
 };
 
 static void pplan_free(ParcPathPlanner *h) {
-    for (void *p : h->allocs) (void)hipFree(p);
-    h->allocs.clear();
+    h->bufs.release();
     h->B = pplan::Bufs{};
     h->cap = 0; h->last_q = 0;
 }
@@ -442,30 +441,20 @@ extern "C" int parc_pathplan_create(const ParcPathPlanParams *p, ParcPathPlanner
     return PARC_OK;
 }
 
-template <typename T> static int pplan_alloc(ParcPathPlanner *h, T *&p, long long count) {
-    void *d = nullptr;
-    HIPCHK(hipMalloc(&d, (size_t)count * sizeof(T)));
-    h->allocs.push_back(d);
-    p = (T *)d;
-    return PARC_OK;
-}
-#define PPLAN_ALLOC(...) do { if (int _rc = pplan_alloc(h, __VA_ARGS__)) return _rc; } while (0)
-
 static int pplan_reserve(ParcPathPlanner *h, int Q) {
     if (Q <= h->cap) return PARC_OK;
     pplan_free(h);
     const pplan::Cfg &G = h->cfg;
     const long long N = (long long)G.X * G.Y;
     pplan::Bufs &B = h->B;
-    float *hf_in = nullptr;
-    PPLAN_ALLOC(hf_in, Q * N);
-    B.hf_in = hf_in;
-    PPLAN_ALLOC(B.hf, Q * N);
-    PPLAN_ALLOC(B.start, 2LL * Q); PPLAN_ALLOC(B.goal, 2LL * Q);
-    PPLAN_ALLOC(B.status, Q); PPLAN_ALLOC(B.num_nodes, Q); PPLAN_ALLOC(B.num_points, Q); PPLAN_ALLOC(B.pops, Q);
-    PPLAN_ALLOC(B.nodes, (long long)Q * G.max_nodes);
-    PPLAN_ALLOC(B.cost, Q);
-    PPLAN_ALLOC(B.points, (long long)Q * G.max_points * 3);
+    DeviceArena &mem = h->bufs;
+    PARC_TRY(mem.alloc(B.hf_in, Q * N));
+    PARC_TRY(mem.alloc(B.hf, Q * N));
+    PARC_TRY(mem.alloc(B.start, 2LL * Q)); PARC_TRY(mem.alloc(B.goal, 2LL * Q));
+    PARC_TRY(mem.alloc(B.status, Q)); PARC_TRY(mem.alloc(B.num_nodes, Q)); PARC_TRY(mem.alloc(B.num_points, Q)); PARC_TRY(mem.alloc(B.pops, Q));
+    PARC_TRY(mem.alloc(B.nodes, (long long)Q * G.max_nodes));
+    PARC_TRY(mem.alloc(B.cost, Q));
+    PARC_TRY(mem.alloc(B.points, (long long)Q * G.max_points * 3));
     h->cap = Q;
     return PARC_OK;
 }

@@ -345,6 +345,20 @@ def check(rc):
         raise ParcError(f"libparc_env error {rc}: {load().parc_last_error().decode()}")
 
 
+def device_index(device) -> int:
+    """The ordinal of ``"cuda:N"`` (a string or a ``torch.device``); 0 when none is given."""
+    dev = str(device)
+    return int(dev.split(":")[1]) if ":" in dev else 0
+
+
+def destroy_handle(obj, destroy: str):
+    """Release ``obj._h`` through ``obj._lib.<destroy>`` and clear it; safe on an object whose constructor did not finish."""
+    h = getattr(obj, "_h", None)
+    if h is not None and h.value:
+        getattr(obj._lib, destroy)(h)
+    obj._h = None
+
+
 def np_f32p(a):
     assert a.dtype == np.float32 and a.flags.c_contiguous
     return a.ctypes.data_as(f32p)

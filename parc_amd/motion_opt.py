@@ -20,6 +20,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from parc_amd.char_model import CharModel, GeomType
+from parc_amd.lib import destroy_handle
 
 
 class LossType(enum.Enum):  # motion_optimization.py:15-25 (LOOPING_LOSS is never computed)
@@ -230,12 +231,25 @@ def pack_clips(clips: Sequence[OptClip], num_bodies: int, dof_size: int):
         cons_point=f32([c.cons_point.reshape(-1, 3) for c in clips]).reshape(-1, 3))
 
 
-def optimizer_params(char_model: CharModel, flat_points, point_body, weights: Dict[str, float], max_jerk: float, step_size: float,
-                     device: int = 0):
-    """``ParcMotionOptParams`` for the character, the sample points and the loss weights (keys ``WEIGHT_KEYS``)."""
+def clip_struct(pk, num_clips):
+    """``ParcMotionOptClips`` over the arrays of ``pack_clips`` (the caller keeps ``pk`` alive)."""
     from parc_amd import lib as L
-    p = L.ParcMotionOptParams()
-    p.struct_size = C.sizeof(L.ParcMotionOptParams)
+    st = L.ParcMotionOptClips()
+    st.num_clips = int(num_clips)
+    i64 = lambda a: a.ctypes.data_as(L.i64p)  # noqa: E731
+    st.frame_off_host, st.hf_off_host, st.cons_off_host = i64(pk["frame_off"]), i64(pk["hf_off"]), i64(pk["cons_off"])
+    st.hf_dims_host, st.hf_geom_host, st.hf_host = L.np_i32p(pk["hf_dims"]), L.np_f32p(pk["hf_geom"]), L.np_f32p(pk["hf"])
+    st.root_pos_host, st.root_rot_host = L.np_f32p(pk["root_pos"]), L.np_f32p(pk["root_rot"])
+    st.joint_rot_host, st.contacts_host = L.np_f32p(pk["joint_rot"]), L.np_f32p(pk["contacts"])
+    st.cons_body_host, st.cons_range_host = L.np_i32p(pk["cons_body"]), L.np_i32p(pk["cons_range"])
+    st.cons_point_host = L.np_f32p(pk["cons_point"])
+    return st
+
+
+def model_points_params(p, char_model: CharModel, flat_points, point_body, device: int):
+    """The head that ``ParcMotionOptParams`` and ``ParcMotionTerrainParams`` share: size, device, character and sample points."""
+    from parc_amd import lib as L
+    p.struct_size = C.sizeof(type(p))
     p.device = int(device)
     p.model = L.make_char_model(char_model)
     pts = np.ascontiguousarray(flat_points, np.float32)
@@ -244,6 +258,14 @@ def optimizer_params(char_model: CharModel, flat_points, point_body, weights: Di
     p.points_host = L.np_f32p(pts)
     p.point_body_host = L.np_i32p(body)
     p._keep = (pts, body)
+    return p
+
+
+def optimizer_params(char_model: CharModel, flat_points, point_body, weights: Dict[str, float], max_jerk: float, step_size: float,
+                     device: int = 0):
+    """``ParcMotionOptParams`` for the character, the sample points and the loss weights (keys ``WEIGHT_KEYS``)."""
+    from parc_amd import lib as L
+    p = model_points_params(L.ParcMotionOptParams(), char_model, flat_points, point_body, device)
     for b in range(char_model.get_num_bodies()):
         geoms = char_model._geoms[b]
         p.geom0_type[b] = -1
@@ -288,8 +310,7 @@ class MotionOptimizer:
             raise ValueError(f"unknown char_point_samples keys: {sorted(unknown)}")
         self.body_points, self.points, self.point_body = char_point_samples(self.char_model, **sampler)
         self.cfg = cfg
-        dev = str(device)
-        self.device_index = int(dev.split(":")[1]) if ":" in dev else 0
+        self.device_index = L.device_index(device)
         params = optimizer_params(self.char_model, self.points, self.point_body, cfg, float(cfg.get("max_jerk", 1000.0)),
                                   float(cfg.get("step_size", 1e-3)), self.device_index)
         h = C.c_void_p()
@@ -302,25 +323,13 @@ class MotionOptimizer:
         self._packed = None
 
     def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            self._lib.parc_mopt_destroy(h)
-            self._h = None
+        destroy_handle(self, "parc_mopt_destroy")
 
     # ------------------------------------------------------------------ batch
     def set_clips(self, clips: Sequence[OptClip]):
-        L = self._L
         pk = pack_clips(clips, self.B, self.D)
-        st = L.ParcMotionOptClips()
-        st.num_clips = len(clips)
-        i64 = lambda a: a.ctypes.data_as(L.i64p)  # noqa: E731
-        st.frame_off_host, st.hf_off_host, st.cons_off_host = i64(pk["frame_off"]), i64(pk["hf_off"]), i64(pk["cons_off"])
-        st.hf_dims_host, st.hf_geom_host, st.hf_host = L.np_i32p(pk["hf_dims"]), L.np_f32p(pk["hf_geom"]), L.np_f32p(pk["hf"])
-        st.root_pos_host, st.root_rot_host = L.np_f32p(pk["root_pos"]), L.np_f32p(pk["root_rot"])
-        st.joint_rot_host, st.contacts_host = L.np_f32p(pk["joint_rot"]), L.np_f32p(pk["contacts"])
-        st.cons_body_host, st.cons_range_host = L.np_i32p(pk["cons_body"]), L.np_i32p(pk["cons_range"])
-        st.cons_point_host = L.np_f32p(pk["cons_point"])
-        L.check(self._lib.parc_mopt_set_clips(self._h, C.byref(st)))
+        st = clip_struct(pk, len(clips))
+        self._L.check(self._lib.parc_mopt_set_clips(self._h, C.byref(st)))
         self._clips = list(clips)
         self._packed = pk
         return pk

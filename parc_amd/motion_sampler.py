@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from parc_amd.char_model import CharModel
+from parc_amd.lib import destroy_handle
 
 FRAME_COMPONENTS = ("ROOT_POS", "ROOT_ROT", "JOINT_POS", "JOINT_ROT", "CONTACTS", "FLOOR_HEIGHTS")   # MDMFrameType (JOINT_VEL: unused)
 RELATIVE_Z = {"RELATIVE_TO_ROOT": 0, "RELATIVE_TO_ROOT_FLOOR": 1}
@@ -191,7 +192,7 @@ class MotionWindowSampler:
         self.char_model = CharModel(char_file)
         self.B = self.char_model.get_num_bodies()
         self.device = torch.device(device)
-        self.device_index = self.device.index or 0
+        self.device_index = L.device_index(self.device)
         clips = [c for c in motion_lib.load_motion_file(motion_file, verbose=False) if c.name not in set(exclude)]
         if extra_vals is not None and len(extra_vals) != len(clips):
             raise ValueError("extra_vals: one entry per clip")
@@ -226,10 +227,7 @@ class MotionWindowSampler:
 
     # ------------------------------------------------------------------ handle
     def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            self._lib.parc_msamp_destroy(h)
-        self._h = None
+        destroy_handle(self, "parc_msamp_destroy")
 
     def _create(self):
         L, c = self._L, self.cfg
@@ -251,8 +249,7 @@ class MotionWindowSampler:
         self._h = h
 
     def _upload(self):
-        from parc_amd.motion_opt import OptClip, pack_clips
-        from parc_amd.motion_terrain import clip_struct
+        from parc_amd.motion_opt import OptClip, clip_struct, pack_clips
         L = self._L
         oc = [OptClip(c.root_pos, c.root_rot, c.joint_rot,
                       c.contacts if c.contacts is not None else np.zeros((c.num_frames, self.B), np.float32),

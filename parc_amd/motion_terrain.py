@@ -15,7 +15,9 @@ from typing import List, Sequence
 import numpy as np
 
 from parc_amd.char_model import CharModel
-from parc_amd.motion_opt import OptClip, char_point_samples, clip_from_ms, pack_clips  # noqa: F401  (re-exported for callers)
+from parc_amd.lib import destroy_handle
+from parc_amd.motion_opt import model_points_params
+from parc_amd.motion_opt import OptClip, char_point_samples, clip_from_ms, clip_struct, pack_clips  # noqa: F401  (re-exported for callers)
 
 SDF_PRUNED, SDF_BRUTE = 0, 1
 Z_BUF, JUMP_BUF, MAX_JERK = 3.0, 0.8, 11666.3906
@@ -28,34 +30,12 @@ def analyzer_params(char_model: CharModel, flat_points, point_body, z_buf=Z_BUF,
                     sdf_mode=SDF_PRUNED, device: int = 0):
     """``ParcMotionTerrainParams``: every body scored with its own contact column (``compute_motion_loss``' ``contacts[..., b]``)."""
     from parc_amd import lib as L
-    p = L.ParcMotionTerrainParams()
-    p.struct_size = C.sizeof(L.ParcMotionTerrainParams)
-    p.device = int(device)
-    p.model = L.make_char_model(char_model)
-    pts = np.ascontiguousarray(flat_points, np.float32)
-    body = np.ascontiguousarray(point_body, np.int32)
-    p.num_points = int(pts.shape[0])
-    p.points_host = L.np_f32p(pts)
-    p.point_body_host = L.np_i32p(body)
-    p._keep = (pts, body)
+    p = model_points_params(L.ParcMotionTerrainParams(), char_model, flat_points, point_body, device)
     for b in range(char_model.get_num_bodies()):
         p.contact_body_id[b] = b
     p.z_buf, p.jump_buf, p.max_jerk = float(z_buf), float(jump_buf), float(max_jerk)
     p.sdf_mode = int(sdf_mode)
     return p
-
-
-def clip_struct(pk, num_clips):
-    """``ParcMotionOptClips`` over the arrays of ``pack_clips`` (the caller keeps ``pk`` alive)."""
-    from parc_amd import lib as L
-    st = L.ParcMotionOptClips()
-    st.num_clips = int(num_clips)
-    i64 = lambda a: a.ctypes.data_as(L.i64p)  # noqa: E731
-    st.frame_off_host, st.hf_off_host, st.cons_off_host = i64(pk["frame_off"]), i64(pk["hf_off"]), i64(pk["cons_off"])
-    st.hf_dims_host, st.hf_geom_host, st.hf_host = L.np_i32p(pk["hf_dims"]), L.np_f32p(pk["hf_geom"]), L.np_f32p(pk["hf"])
-    st.root_pos_host, st.root_rot_host = L.np_f32p(pk["root_pos"]), L.np_f32p(pk["root_rot"])
-    st.joint_rot_host, st.contacts_host = L.np_f32p(pk["joint_rot"]), L.np_f32p(pk["contacts"])
-    return st
 
 
 class MotionTerrainAnalyzer:
@@ -74,8 +54,7 @@ class MotionTerrainAnalyzer:
         else:                # (flat [P, 3], body index [P]), e.g. the reference's own samples
             self.points = np.ascontiguousarray(points[0], np.float32)
             self.point_body = np.ascontiguousarray(points[1], np.int32)
-        dev = str(device)
-        self.device_index = int(dev.split(":")[1]) if ":" in dev else 0
+        self.device_index = L.device_index(device)
         self.sdf_mode = int(sdf_mode)
         self.B = self.char_model.get_num_bodies()
         self.D = self.char_model.get_dof_size()
@@ -87,10 +66,7 @@ class MotionTerrainAnalyzer:
         self._destroy()
 
     def _destroy(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            self._lib.parc_mterr_destroy(h)
-        self._h = None
+        destroy_handle(self, "parc_mterr_destroy")
 
     def _handle(self, z_buf, jump_buf, max_jerk):
         key = (float(z_buf), float(jump_buf), float(max_jerk))

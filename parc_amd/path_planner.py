@@ -17,6 +17,8 @@ from typing import List, Optional
 
 import numpy as np
 
+from parc_amd.lib import destroy_handle
+
 FOUND, NO_PATH, OVER_MAX_COST, BUDGET, NO_DRAW = range(5)
 STATUS_NAMES = ("FOUND", "NO_PATH", "OVER_MAX_COST", "BUDGET", "NO_DRAW")
 MAX_DIM, MAX_JUMP_RADIUS, JUMP_WORDS = 64, 8, 8
@@ -161,8 +163,7 @@ class TerrainPathPlanner:
         self.max_expansions = int(max_expansions)
         self.min_point = (float(min_point[0]), float(min_point[1]))
         self.max_nodes, self.max_points = max_nodes, max_points
-        dev = str(device)
-        self.device_index = int(dev.split(":")[1]) if ":" in dev else 0
+        self.device_index = L.device_index(device)
         self._h = None
         self._key = None
         self._params = None
@@ -171,10 +172,7 @@ class TerrainPathPlanner:
         self._destroy()
 
     def _destroy(self):
-        h = getattr(self, "_h", None)
-        if h is not None:
-            self._lib.parc_pathplan_destroy(h)
-            self._h = None
+        destroy_handle(self, "parc_pathplan_destroy")
 
     def _handle(self, X, Y, dx, dy):
         key = (X, Y, float(np.float32(dx)), float(np.float32(dy)))

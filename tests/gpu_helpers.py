@@ -9,6 +9,18 @@ from conftest import DATA, golden
 from parc_amd.util import path_loader
 
 GOLDEN_WEIGHTS = [1.0, 1.5, 2.0, 2.5]
+# the fields of ParcMotionOptClips that the optimiser, the analyser and the sampler all read (their set_clips refuses a NULL one)
+SHARED_CLIP_ARRAYS = ("frame_off_host", "hf_off_host", "hf_dims_host", "hf_geom_host", "hf_host", "root_pos_host", "root_rot_host",
+                      "joint_rot_host", "contacts_host")
+
+
+def raises_invalid(call, message):
+    """``call()`` must fail with PARC_ERR_INVALID and exactly ``message`` (libparc_env's last error)."""
+    import pytest
+    from parc_amd import lib as L
+    with pytest.raises(L.ParcError) as e:
+        L.check(call())
+    assert str(e.value) == "libparc_env error -1: " + message
 
 
 def default_config():

@@ -229,6 +229,43 @@ def test_argument_errors():
     from parc_amd import lib as L
     with pytest.raises(L.ParcError):
         opt.loss_and_grad()   # no clips yet
+    # one fault per call: the return code and the whole message (the strings of parc_mopt_set_clips and parc_mopt_create)
+    import ctypes as C
+    from gpu_helpers import SHARED_CLIP_ARRAYS, raises_invalid
+    lib = opt._lib
+    pk = mo.pack_clips([c], opt.B, opt.D)
+    nf = c.num_frames
+    assert pk["cons_off"][-1] > 0
+    faults = [(pk, 0, "mopt: num_clips must be >= 1"),
+              (dict(pk, frame_off=np.array([1, nf + 1], np.int64)), 1, "mopt: offsets must start at 0"),
+              (dict(pk, hf_off=pk["hf_off"] + 1), 1, "mopt: offsets must start at 0"),
+              (dict(pk, cons_off=pk["cons_off"] + 1), 1, "mopt: offsets must start at 0"),
+              (dict(pk, frame_off=np.zeros(2, np.int64)), 1, "mopt: clip 0 has no frames"),
+              (dict(pk, hf_dims=np.ascontiguousarray([[c.hf.shape[0] + 1, c.hf.shape[1]]], np.int32)), 1,
+               "mopt: heightfield dims / offsets disagree"),
+              (dict(pk, hf_geom=np.ascontiguousarray([[0, 0, 0, 0.4]], np.float32)), 1, "mopt: dx must be > 0"),
+              (dict(pk, cons_off=pk["cons_off"][::-1].copy() - pk["cons_off"][-1]), 1, "mopt: constraint offsets decrease"),
+              (dict(pk, cons_body=np.full_like(pk["cons_body"], opt.B)), 1, "mopt: constraint body out of range")]
+    faults += [(pk, 1, (name, "mopt: null clip array")) for name in SHARED_CLIP_ARRAYS + ("cons_off_host",)]
+    faults.append((pk, 1, ("cons_point_host", "mopt: null constraint array")))
+    for bad, n, msg in faults:   # `bad` owns the arrays the struct points to
+        st = mo.clip_struct(bad, n)
+        if isinstance(msg, tuple):   # (field passed as NULL, message)
+            setattr(st, msg[0], None)
+            msg = msg[1]
+        raises_invalid(lambda: lib.parc_mopt_set_clips(opt._h, C.byref(st)), msg)
+    args = (opt.char_model, opt.points, opt.point_body, cfg_of(z), float(z["max_jerk"]), float(z["step_size"]))
+    p = mo.optimizer_params(*args)
+    p.struct_size -= 8
+    created = [(p, "ParcMotionOptParams ABI mismatch (struct_size)"),
+               (mo.optimizer_params(args[0], args[1], args[2][::-1], *args[3:]), "mopt: point bodies must be in [0, B) and non-decreasing")]
+    p = mo.optimizer_params(*args)
+    p.model.dof_idx[1] = opt.D   # body 1 hangs on a spherical joint
+    created.append((p, "mopt: dof_idx out of range"))
+    h = C.c_void_p()
+    for p, msg in created:
+        raises_invalid(lambda: lib.parc_mopt_create(C.byref(p), C.byref(h)), msg)
+        assert not h.value
 
 
 def test_driver_end_to_end_files_load_in_the_env(tmp_path):

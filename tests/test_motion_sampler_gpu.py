@@ -330,18 +330,21 @@ def test_error_paths(tmp_path_factory, tmp_path):
     from parc_amd.motion_terrain import clip_struct
     import ctypes as C
 
-    def set_clips(nf, X, Y):
+    def set_clips(nf, X, Y, num_clips=1, null=None, **packed):
+        """One clip of nf frames on an X x Y terrain; `packed` replaces arrays of the packing, `null` names a field passed as NULL."""
         B = s.B
         q = np.tile(np.array([0, 0, 0, 1], np.float32), (nf, 1))
         oc = [OptClip(np.zeros((nf, 3), np.float32), q, np.tile(q[:, None], (1, B - 1, 1)), np.zeros((nf, B), np.float32),
                       np.zeros((X, Y), np.float32), np.zeros(2, np.float32), 0.4)]
-        pk = pack_clips(oc, B, s.char_model.get_dof_size())
-        st = clip_struct(pk, 1)
+        pk = dict(pack_clips(oc, B, s.char_model.get_dof_size()), **packed)
+        st = clip_struct(pk, num_clips)
         info = L.ParcMotionSamplerClipInfo()
         mm, off = np.zeros((X * Y, 2), np.float32), np.zeros(nf + 1, np.int64)
         fps, loop, w = np.array([30], np.int32), np.array([0], np.int32), np.array([1.0])
         info.hf_maxmin_host, info.mask_off_host, info.mask_cells_host = L.np_f32p(mm), off.ctypes.data_as(L.i64p), None
         info.fps_host, info.loop_modes_host, info.weights_host = L.np_i32p(fps), L.np_i32p(loop), w.ctypes.data_as(L.f64p)
+        if null is not None:
+            setattr(info if hasattr(info, null) else st, null, None)
         other = ms.MotionWindowSampler.__new__(ms.MotionWindowSampler)
         other.__dict__.update(s.__dict__)
         other._h = None
@@ -357,6 +360,33 @@ def test_error_paths(tmp_path_factory, tmp_path):
     with pytest.raises(L.ParcError, match="262656 cells, above the limit of 262144"):
         set_clips(16, 513, 512)
     set_clips(16, 512, 512)
+    # one fault per call: the return code and the whole message (the strings of parc_msamp_set_clips and parc_msamp_create)
+    from gpu_helpers import SHARED_CLIP_ARRAYS
+
+    def refused(msg, *a, **k):
+        with pytest.raises(L.ParcError) as e:
+            set_clips(*a, **k)
+        assert str(e.value) == "libparc_env error -1: " + msg
+
+    T = s.cfg.T
+    assert T == 15
+    i64 = lambda *v: np.array(v, np.int64)  # noqa: E731
+    refused("msamp: num_clips must be >= 1", 16, 4, 4, num_clips=0)
+    for name in SHARED_CLIP_ARRAYS + ("hf_maxmin_host", "mask_off_host", "fps_host", "loop_modes_host", "weights_host"):
+        refused("msamp: null clip array", 16, 4, 4, null=name)
+    refused("msamp: offsets must start at 0", 16, 4, 4, frame_off=i64(1, 17))
+    refused("msamp: offsets must start at 0", 16, 4, 4, hf_off=i64(1, 17))
+    refused("msamp: clip 0 is too short: 15 frames for windows of 15", 15, 4, 4)
+    refused("msamp: clip 0 is too short: 0 frames for windows of 15", 16, 4, 4, frame_off=i64(0, 0))
+    refused("msamp: heightfield dims / offsets disagree", 16, 4, 4, hf_dims=np.ascontiguousarray([[5, 4]], np.int32))
+    refused("msamp: dx must be > 0", 16, 4, 4, hf_geom=np.ascontiguousarray([[0, 0, 0, 0.4]], np.float32))
+    refused("msamp: the terrain of clip 0 has 262656 cells, above the limit of 262144 (the window mask is a bitset in LDS)", 16, 513, 512)
+    p = L.ParcMotionSamplerParams()
+    p.struct_size = C.sizeof(L.ParcMotionSamplerParams) - 8
+    h = C.c_void_p()
+    with pytest.raises(L.ParcError) as e:
+        L.check(s._lib.parc_msamp_create(C.byref(p), C.byref(h)))
+    assert str(e.value) == "libparc_env error -1: ParcMotionSamplerParams ABI mismatch (struct_size)" and not h.value
     # num_boxes above max_num_boxes, a motion id outside the library
     p = plan_of(z)
     bad = dict(p, num_boxes=np.full_like(p["num_boxes"], s.cfg.max_num_boxes + 1))

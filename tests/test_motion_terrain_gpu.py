@@ -255,6 +255,7 @@ def test_nan_frame_poisons_only_its_clip(analyzer):
 
 
 def test_argument_errors(analyzer):
+    from gpu_helpers import SHARED_CLIP_ARRAYS, raises_invalid
     from parc_amd import lib as L
     z = fixture("TEASER_TERRAIN")
     lib = L.load()
@@ -285,8 +286,36 @@ def test_argument_errors(analyzer):
         st = mt.clip_struct(bad, 1)
         with pytest.raises(L.ParcError, match="dx"):
             L.check(lib.parc_mterr_set_clips(h, C.byref(st)))
+        # one fault per call: the return code and the whole message (the strings of parc_mterr_set_clips)
+        nf = int(pk["frame_off"][1])
+        faults = [(pk, 0, "mterr: num_clips must be >= 1"),
+                  (dict(pk, frame_off=np.array([1, nf + 1], np.int64)), 1, "mterr: offsets must start at 0"),
+                  (dict(pk, hf_off=pk["hf_off"] + 1), 1, "mterr: offsets must start at 0"),
+                  (dict(pk, frame_off=np.zeros(2, np.int64)), 1, "mterr: clip 0 has no frames"),
+                  (dict(pk, hf_dims=np.ascontiguousarray([[z["hf"].shape[0] + 1, z["hf"].shape[1]]], np.int32)), 1,
+                   "mterr: heightfield dims / offsets disagree (dims >= 1, at most 2^31 - 1 cells)"),
+                  (dict(pk, hf_geom=np.ascontiguousarray([[0, 0, 0, 0.4]], np.float32)), 1, "mterr: dx must be > 0")]
+        faults += [(pk, 1, (name, "mterr: null clip array")) for name in SHARED_CLIP_ARRAYS]
+        for bad, n, msg in faults:   # `bad` owns the arrays the struct points to
+            st = mt.clip_struct(bad, n)
+            if isinstance(msg, tuple):   # (field passed as NULL, message)
+                setattr(st, msg[0], None)
+                msg = msg[1]
+            raises_invalid(lambda: lib.parc_mterr_set_clips(h, C.byref(st)), msg)
+        st = mt.clip_struct(pk, 1)
+        st.cons_off_host = st.cons_body_host = st.cons_range_host = st.cons_point_host = None   # the analyser reads no constraints
+        L.check(lib.parc_mterr_set_clips(h, C.byref(st)))
     finally:
         lib.parc_mterr_destroy(h)
+    h2 = C.c_void_p()
+    p = mt.analyzer_params(analyzer.char_model, analyzer.points, analyzer.point_body)
+    p.struct_size -= 8
+    created = [(p, "ParcMotionTerrainParams ABI mismatch (struct_size)"),
+               (mt.analyzer_params(analyzer.char_model, analyzer.points, analyzer.point_body[::-1]),
+                "mterr: point bodies must be in [0, B) and non-decreasing")]
+    for p, msg in created:
+        raises_invalid(lambda: lib.parc_mterr_create(C.byref(p), C.byref(h2)), msg)
+        assert not h2.value
 
 
 def test_env_step_and_motion_opt_step_unchanged_by_the_analyzer():
