@@ -685,6 +685,70 @@ int parc_pathplan_get_graph(ParcPathPlanner *h, int32_t q0, int32_t n, uint8_t *
 /* Device time (hipEvents) of the last run, ms: prepare (draw + simplification), search, and the last parc_pathplan_get_graph. */
 int parc_pathplan_kernel_times(ParcPathPlanner *h, float *ms3);
 
+/* Batched procedural terrain generator: stage 2's BOXES, PATHS and STAIRS procgen modes (terrain_util's
+ * add_boxes_to_hf2 without the hf_maxmin clamp, gen_paths_hf, add_stairs_to_hf / draw_box, driven as scripts/parc_2_kin_gen.py:247-290)
+ * for n terrains at once, one wave per terrain.  Its own handle: one mode and one grid shape per handle.  Every random value comes from
+ * a plan of device arrays holding the derived fp32 values (not the uniforms); parc_tgen_draw_plan fills one with Philox4x32-10 keyed by
+ * the seed, counter hi = 1 << 61 | mode << 56 | terrain index, u = top 24 bits / 2^24, normals by Box-Muller on (0, 1] uniforms:
+ *   BOXES   lo = 2 b: center x, y, len x, y of box b; lo = 2 b + 1: angle, height
+ *   PATHS   lo = 256 p: start x, y, angle, height of path p; 256 p + 1: vy; 256 p + 2 + i / 4: turn normals 4 (i / 4) .. 4 (i / 4) + 3
+ *           (r0 cos, r0 sin, r1 cos, r1 sin of the uniform pairs (0, 1) and (2, 3))
+ *   STAIRS  lo = 2 s: start x, y, end x, y of stair s; lo = 2 s + 1: start height, step height, thickness
+ * The terrain index is first_terrain + the position in the batch: a terrain is the same bits alone or in any batch.  Limits (a refusal
+ * names the macro): sides of 4 .. PARC_TGEN_MAX_DIM cells, num_boxes <= PARC_TGEN_MAX_BOXES, num_terrain_paths <= PARC_TGEN_MAX_PATHS (a
+ * lane per path), num_stairs <= PARC_TGEN_MAX_STAIRS, maxpool_size <= PARC_TGEN_MAX_POOL; a path has PARC_TGEN_PATH_POINTS points; a stair
+ * paints at most PARC_TGEN_MAX_STEPS steps (a plan whose stair would need more is cut there; the validate pass refuses it). */
+#define PARC_TGEN_MAX_DIM 64
+#define PARC_TGEN_MAX_BOXES 64
+#define PARC_TGEN_MAX_PATHS 64
+#define PARC_TGEN_MAX_STAIRS 16
+#define PARC_TGEN_MAX_POOL 8
+#define PARC_TGEN_PATH_POINTS 1000
+#define PARC_TGEN_MAX_STEPS 1024
+#define PARC_TGEN_BOX_FLOATS 6                   /* center x, y (index units), len x, y, angle, height: PARC_MSAMP_BOX_FLOATS' layout */
+#define PARC_TGEN_STAIR_FLOATS 7                 /* start x, y, end x, y (metres), start height, step height, thickness */
+#define PARC_TGEN_BOXES 0                        /* ProcGenMode (parc_2_kin_gen.py:30-34) */
+#define PARC_TGEN_PATHS 1
+#define PARC_TGEN_STAIRS 2
+typedef struct ParcTerrainGen ParcTerrainGen;
+typedef struct {
+    uint32_t struct_size;                    /* sizeof(ParcTerrainGenParams) */
+    int32_t device;
+    int32_t mode;                            /* PARC_TGEN_BOXES / PATHS / STAIRS */
+    int32_t dim_x, dim_y;
+    float dx, dy;                            /* SubTerrain.dxdy */
+    float min_point[2];                      /* SubTerrain.min_point (stage 2: 0, 0) */
+    /* the ranges parc_tgen_draw_plan draws from: ProcGenBoxesSettings, ProcGenPathsSettings, ProcGenStairsSettings */
+    int32_t num_boxes;
+    float min_box_h, max_box_h, box_min_len, box_max_len, min_box_angle, max_box_angle;
+    int32_t num_terrain_paths, maxpool_size;
+    float path_min_height, path_max_height, floor_height;
+    int32_t num_stairs;
+    float min_stair_start_height, max_stair_start_height, min_step_height, max_step_height, min_stair_thickness, max_stair_thickness;
+} ParcTerrainGenParams;
+typedef struct {                             /* device arrays of n terrains; only the handle's mode is read (the others may be NULL) */
+    int32_t n;
+    const float *boxes;                      /* [n][num_boxes][PARC_TGEN_BOX_FLOATS] */
+    const float *path_start;                 /* [n][num_terrain_paths][2] metres */
+    const float *path_vy;                    /* [n][num_terrain_paths] the start velocity is (1, vy) rotated by path_angle */
+    const float *path_angle;                 /* [n][num_terrain_paths] */
+    const float *path_turn;                  /* [n][num_terrain_paths][PARC_TGEN_PATH_POINTS] standard normals */
+    const float *path_height;                /* [n][num_terrain_paths] */
+    const float *stairs;                     /* [n][num_stairs][PARC_TGEN_STAIR_FLOATS] */
+} ParcTerrainGenPlan;
+int parc_tgen_create(const ParcTerrainGenParams *p, ParcTerrainGen **out);
+void parc_tgen_destroy(ParcTerrainGen *h);
+/* Fills the (writable, caller-owned) arrays of `plan` for plan->n terrains from (seed, first_terrain + position).  No host sync. */
+int parc_tgen_draw_plan(ParcTerrainGen *h, uint64_t seed, uint64_t first_terrain, const ParcTerrainGenPlan *plan, void *stream);
+/* The deterministic path: hf [n][dim_x][dim_y] (device) from the plan.  With validate != 0 a pass over the plan runs first and the
+ * call synchronises: a non-finite entry, or a stair of more than PARC_TGEN_MAX_STEPS steps, is PARC_ERR_INVALID naming the field, and the
+ * generator is not launched.  Without it nothing synchronises; a non-finite entry is handled memory-safely (indices clamp to the grid). */
+int parc_tgen_generate_with(ParcTerrainGen *h, const ParcTerrainGenPlan *plan, float *hf, int32_t validate, void *stream);
+/* draw_plan + generate_with in one kernel, the plan never in memory: the same bits as the two calls. */
+int parc_tgen_generate(ParcTerrainGen *h, int32_t n, uint64_t seed, uint64_t first_terrain, float *hf, void *stream);
+/* Device time (hipEvents; waits for the last event), ms: the last parc_tgen_draw_plan, the last generate_with / generate (0 = not run). */
+int parc_tgen_kernel_times(ParcTerrainGen *h, float *ms2);
+
 #ifdef __cplusplus
 }
 #endif

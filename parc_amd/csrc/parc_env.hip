@@ -2971,3 +2971,4 @@ extern "C" int parc_env_profile_step(ParcEnv *e, const float *action_dev, void *
 #include "parc_motion_terrain.hpp"   // parc_mterr_*: motion-terrain analysis (its own handle; reuses the motion optimiser FK, sdBox, model and clip layout)
 #include "parc_motion_sampler.hpp"   // parc_msamp_*: the generator's motion-window sampler (its own handle; reuses frame_blend, philox4, the optimiser FK, model and clip layout, grid_index)
 #include "parc_path_planner.hpp"     // parc_pathplan_*: stage 2's batched A* terrain path planner (its own handle; reuses philox4 and the device arena)
+#include "parc_terrain_gen.hpp"      // parc_tgen_*: stage 2's BOXES / PATHS / STAIRS terrain generators, batched (its own handle; reuses philox4)

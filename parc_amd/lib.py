@@ -159,6 +159,28 @@ class ParcPathPlanOutputs(C.Structure):
     _fields_ = [(n, {"f": f32p, "i": i32p}[t]) for n, t in PATHPLAN_OUTPUT_FIELDS]
 
 
+TGEN_MAX_DIM, TGEN_MAX_BOXES, TGEN_MAX_PATHS, TGEN_MAX_STAIRS, TGEN_MAX_POOL = 64, 64, 64, 16, 8   # PARC_TGEN_*
+TGEN_PATH_POINTS, TGEN_MAX_STEPS, TGEN_BOX_FLOATS, TGEN_STAIR_FLOATS = 1000, 1024, 6, 7
+TGEN_MODES = ("BOXES", "PATHS", "STAIRS")                                                        # PARC_TGEN_BOXES / PATHS / STAIRS
+# the three settings blocks, in struct order: (name, "i" / "f")
+TGEN_BOXES_FIELDS = [("num_boxes", "i"), ("min_box_h", "f"), ("max_box_h", "f"), ("box_min_len", "f"), ("box_max_len", "f"),
+                     ("min_box_angle", "f"), ("max_box_angle", "f")]
+TGEN_PATHS_FIELDS = [("num_terrain_paths", "i"), ("maxpool_size", "i"), ("path_min_height", "f"), ("path_max_height", "f"), ("floor_height", "f")]
+TGEN_STAIRS_FIELDS = [("num_stairs", "i"), ("min_stair_start_height", "f"), ("max_stair_start_height", "f"), ("min_step_height", "f"),
+                      ("max_step_height", "f"), ("min_stair_thickness", "f"), ("max_stair_thickness", "f")]
+TGEN_PLAN_FIELDS = ["boxes", "path_start", "path_vy", "path_angle", "path_turn", "path_height", "stairs"]
+
+
+class ParcTerrainGenParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("mode", C.c_int32), ("dim_x", C.c_int32), ("dim_y", C.c_int32),
+                ("dx", C.c_float), ("dy", C.c_float), ("min_point", C.c_float * 2)] + \
+               [(n, C.c_int32 if t == "i" else C.c_float) for n, t in TGEN_BOXES_FIELDS + TGEN_PATHS_FIELDS + TGEN_STAIRS_FIELDS]
+
+
+class ParcTerrainGenPlan(C.Structure):
+    _fields_ = [("n", C.c_int32)] + [(n, C.c_void_p) for n in TGEN_PLAN_FIELDS]
+
+
 BUFFER_FIELDS = [
     ("char_root_pos", "f"), ("char_root_rot", "f"), ("char_root_vel", "f"), ("char_root_ang_vel", "f"),
     ("char_dof_pos", "f"), ("char_dof_vel", "f"), ("char_body_pos", "f"), ("contact_forces", "f"),
@@ -289,6 +311,13 @@ def load():
     lib.parc_pathplan_run.argtypes = [vp, C.c_int32, f32p, i32p, i32p, C.c_uint64, C.c_uint64, C.POINTER(ParcPathPlanOutputs)]
     lib.parc_pathplan_get_graph.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)]
     lib.parc_pathplan_kernel_times.argtypes = [vp, f32p]
+    lib.parc_tgen_create.argtypes = [C.POINTER(ParcTerrainGenParams), C.POINTER(vp)]
+    lib.parc_tgen_destroy.argtypes = [vp]
+    lib.parc_tgen_destroy.restype = None
+    lib.parc_tgen_draw_plan.argtypes = [vp, C.c_uint64, C.c_uint64, C.POINTER(ParcTerrainGenPlan), vp]
+    lib.parc_tgen_generate_with.argtypes = [vp, C.POINTER(ParcTerrainGenPlan), vp, C.c_int32, vp]
+    lib.parc_tgen_generate.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, vp, vp]
+    lib.parc_tgen_kernel_times.argtypes = [vp, f32p]
     _lib = lib
     return lib
 
@@ -310,6 +339,7 @@ EXPORTED_SYMBOLS = [
     "parc_msamp_create", "parc_msamp_destroy", "parc_msamp_set_clips", "parc_msamp_sample_with", "parc_msamp_draw_plan",
     "parc_msamp_sample", "parc_msamp_enumerate", "parc_msamp_plan_status", "parc_msamp_kernel_times",
     "parc_pathplan_create", "parc_pathplan_destroy", "parc_pathplan_run", "parc_pathplan_get_graph", "parc_pathplan_kernel_times",
+    "parc_tgen_create", "parc_tgen_destroy", "parc_tgen_draw_plan", "parc_tgen_generate_with", "parc_tgen_generate", "parc_tgen_kernel_times",
 ]
 
 # parc_test_quat_op selectors (include/parc_env.h)
