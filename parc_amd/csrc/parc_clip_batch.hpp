@@ -1,33 +1,20 @@
-// parc_clip_batch.hpp — host code shared by the handles of the motion tools (parc_mopt_*, parc_mterr_*, parc_msamp_*, parc_pathplan_*;
-// DESIGN.md section 8d): a device arena, the fill and upload of mopt::Model from ParcCharModel, and the validation and upload of the
-// part of a packed ParcMotionOptClips batch that the optimiser, the analyser and the sampler all read.  No kernel lives here.
+// parc_clip_batch.hpp — host code shared by the handles of the motion tools (parc_mopt_*, parc_mterr_*, parc_msamp_*; DESIGN.md
+// section 8d): the fill and upload of mopt::Model from ParcCharModel, and the validation and upload of the part of a packed
+// ParcMotionOptClips batch that the optimiser, the analyser and the sampler all read.  No kernel lives here.
 //
 // `pre` is the caller's message prefix ("mopt", "mterr", "msamp"); the functions know nothing else about their caller.  What only one
 // module checks or uploads stays in that module.  mopt::Model and mopt::Clips are defined with the kernels that read them
-// (parc_motion_opt.hpp, included after this file), so the functions that fill them take them as a template parameter.
+// (parc_motion_opt.hpp, which includes this file), so the functions that fill them take them as a template parameter.
 #pragma once
+#include <hip/hip_runtime.h>
 
-#define PARC_TRY(x) do { if (int _rc = (x)) return _rc; } while (0)
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
 
-static unsigned blocks(long long n, int t) { return (unsigned)((n + t - 1) / t); }
-
-struct DeviceArena {                      // device buffers with one lifetime: freed together
-    std::vector<void *> ptrs;
-    // p = count elements of T on the current device (16 B when count is 0), copied from the host array src when given
-    template <typename T> int alloc(T *&p, long long count, const void *src = nullptr) {
-        void *d = nullptr;
-        const size_t bytes = count > 0 ? (size_t)count * sizeof(T) : 16;
-        HIPCHK(hipMalloc(&d, bytes));
-        ptrs.push_back(d);
-        if (src && count > 0) HIPCHK(hipMemcpy(d, src, (size_t)count * sizeof(T), hipMemcpyHostToDevice));
-        p = (T *)d;
-        return PARC_OK;
-    }
-    void release() {
-        for (void *p : ptrs) (void)hipFree(p);
-        ptrs.clear();
-    }
-};
+#include "../../include/parc_env.h"
+#include "parc_common.hpp"
 
 // ---- the character model ---------------------------------------------------------------------------------------------------------
 // M = zeros, then B, D and the tree of cm.  The caller has checked num_bodies (and dof_size) against the limits.

@@ -1,4 +1,6 @@
-// parc_env.hip — gfx950 kernels + the C-ABI of include/parc_env.h.
+// parc_env.hip — the env's gfx950 kernels (step, dynamics, renderer) + the parc_env_* C-ABI of include/parc_env.h.
+// One of the library's two translation units: the stage-2 motion tools (parc_mopt_*, parc_mterr_*, parc_msamp_*, parc_pathplan_*,
+// parc_tgen_*) are parc_tools.hip, and what both units use is parc_common.hpp.
 //
 // One wavefront (64 lanes) owns one environment per iteration of a grid-stride loop:
 //   * the joint hierarchy / per-body tables are staged once per wave into LDS;
@@ -24,6 +26,7 @@
 #include <vector>
 
 #include "../../include/parc_env.h"
+#include "parc_common.hpp"    // what this unit shares with parc_tools.hip: g_err / fail / HIPCHK, MotionMeta, frame_blend, philox4
 #include "parc_math.hpp"
 #include "parc_dynamics.hpp"
 #include "parc_dynamics_coop.hpp"
@@ -63,14 +66,6 @@ struct DevTables { // global memory; `h` is staged into LDS, the rest is read on
     float pose_term_dist[16];
 };
 
-struct MotionMeta { // 32 B
-    int start, nframes;
-    float length;
-    int loop;
-    float dx, dy, dz;
-    float fps;
-};
-
 struct StepParams {
     int N, B, J, D, K, S, R, M, T;
     int lds_wave_floats; // dynamic LDS per wave of k_env_post
@@ -98,24 +93,6 @@ struct StepParams {
     float4 *prep;        // [N][16]: slot 0 = (cos h, sin h, hinv.z, hinv.w), slots 1..B-1 = character joint quats
     ParcEnvBuffers buf;
 };
-
-struct Blend { int i0, i1; float b; };
-
-// motion_lib.py:425-438 (+ calc_phase :520)
-__device__ __forceinline__ Blend frame_blend(const MotionMeta &m, float t) {
-    float phase = t / m.length;
-    if (m.loop == PARC_LOOP_WRAP) phase = phase - floorf(phase);
-    phase = fminf(fmaxf(phase, 0.f), 1.f);
-    float pf = phase * (float)(m.nframes - 1);
-    int f0 = (int)pf;                       // .long(): truncation
-    f0 = max(0, min(f0, m.nframes - 1));    // memory safety only (no-op for finite phase)
-    int f1 = min(f0 + 1, m.nframes - 1);
-    Blend r;
-    r.b = pf - (float)f0;
-    r.i0 = f0 + m.start;
-    r.i1 = f1 + m.start;
-    return r;
-}
 
 // Joint.dof_to_rot kin_char_model.py:61-81
 __device__ __forceinline__ Q4 joint_dof_to_rot(int type, const float *axis4, const float *dof) {
@@ -1319,22 +1296,6 @@ __global__ void k_fk(const DevTables *T, const float *root_pos, const float *roo
               bp + 3 * (size_t)i * B, br ? br + 4 * (size_t)i * B : nullptr);
 }
 
-// ---- device RNG for resets: Philox4x32-10 ---------------------------------------------------------
-__device__ __forceinline__ void philox_round(unsigned &c0, unsigned &c1, unsigned &c2, unsigned &c3, unsigned k0, unsigned k1) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
-    const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
-    const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-}
-__device__ __forceinline__ void philox4(unsigned long long seed, unsigned long long ctr_hi, unsigned ctr_lo, float *u4) {
-    unsigned c0 = ctr_lo, c1 = (unsigned)ctr_hi, c2 = (unsigned)(ctr_hi >> 32), c3 = 0x5041524Bu;
-    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-    for (int r = 0; r < 10; ++r) { philox_round(c0, c1, c2, c3, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-    u4[0] = (c0 >> 8) * (1.0f / 16777216.0f); u4[1] = (c1 >> 8) * (1.0f / 16777216.0f);
-    u4[2] = (c2 >> 8) * (1.0f / 16777216.0f); u4[3] = (c3 >> 8) * (1.0f / 16777216.0f);
-}
-
 __device__ __forceinline__ double shfl_up_f64(double v, int d) {
     const long long b = __double_as_longlong(v);
     const int lo = __shfl_up((int)(b & 0xffffffffll), d, 64), hi = __shfl_up((int)(b >> 32), d, 64);
@@ -1590,11 +1551,6 @@ __global__ __launch_bounds__(1024) void k_build_cdf(const float *fail_rates, con
 // ================================================================================================
 // host side
 // ================================================================================================
-static thread_local std::string g_err;
-static int fail(int code, const std::string &msg) { g_err = msg; return code; }
-
-#define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) return fail(PARC_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(_e)); } while (0)
-
 // ParcEnvConfig::dev_options, "key=value;key=value"
 static std::string dev_opt(const ParcEnvConfig *cfg, const char *key) {
     if (!cfg->dev_options) return "";
@@ -2965,10 +2921,3 @@ extern "C" int parc_env_profile_step(ParcEnv *e, const float *action_dev, void *
     e->last_dyn_ms = (float)(dyn / iters);
     return PARC_OK;
 }
-
-#include "parc_clip_batch.hpp"   // host code the four handles below share: the device arena, mopt::Model setup, clip-batch validation and upload (uses fail(), HIPCHK)
-#include "parc_motion_opt.hpp"   // parc_mopt_*: the batched kinematic motion optimiser (its own handle; uses parc_math.hpp; defines mopt::Model / mopt::Clips)
-#include "parc_motion_terrain.hpp"   // parc_mterr_*: motion-terrain analysis (its own handle; reuses the motion optimiser FK, sdBox, model and clip layout)
-#include "parc_motion_sampler.hpp"   // parc_msamp_*: the generator's motion-window sampler (its own handle; reuses frame_blend, philox4, the optimiser FK, model and clip layout, grid_index)
-#include "parc_path_planner.hpp"     // parc_pathplan_*: stage 2's batched A* terrain path planner (its own handle; reuses philox4 and the device arena)
-#include "parc_terrain_gen.hpp"      // parc_tgen_*: stage 2's BOXES / PATHS / STAIRS terrain generators, batched (its own handle; reuses philox4)

@@ -13,6 +13,18 @@
 //   k_mopt_adam    lane per parameter: torch.optim.Adam (single-tensor path, fp32)
 // No float atomics, no reduction whose order depends on the batch: a clip's result is bit-identical alone or in any batch.
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/parc_env.h"
+#include "parc_common.hpp"
+#include "parc_math.hpp"
+#include "parc_clip_batch.hpp"
 
 namespace mopt {
 using namespace parc;

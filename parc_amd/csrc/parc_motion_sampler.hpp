@@ -14,6 +14,20 @@
 // No float atomics; the only atomic is the integer OR of the LDS bitset (order-free).  Each sample is computed by its own wave /
 // workgroup from its own plan entries only: its outputs are bit-identical alone or in any batch, in any position.
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/parc_env.h"
+#include "parc_common.hpp"
+#include "parc_math.hpp"
+#include "parc_clip_batch.hpp"
+#include "parc_motion_opt.hpp"       // mopt::Model / Clips, fk_frame, qmul, to_i64
+#include "parc_motion_terrain.hpp"   // mterr::grid_index
 
 namespace msamp {
 using namespace parc;

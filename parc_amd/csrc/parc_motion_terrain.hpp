@@ -15,6 +15,20 @@
 //   k_mterr_gather  block per frame: the frame's unique cells to their place in the [K][2] output (offsets from the host's scan)
 // No float atomics and no reduction whose order depends on the batch: a clip's results are bit-identical alone or in any batch.
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/parc_env.h"
+#include "parc_common.hpp"
+#include "parc_math.hpp"
+#include "parc_clip_batch.hpp"
+#include "parc_motion_opt.hpp"       // mopt::Model / Clips, fk_frame, sd_box, to_i64
 
 namespace mterr {
 using namespace parc;

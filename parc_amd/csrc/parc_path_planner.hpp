@@ -17,6 +17,16 @@
 // start / goal draw number t of query q: (hi = 1 << 62 | q, lo = t), words 0 and 1.  q is first_query + the index in the batch, so a
 // query computes the same bits alone or in any batch.
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <new>
+#include <string>
+
+#include "../../include/parc_env.h"
+#include "parc_common.hpp"
+#include "parc_math.hpp"
 
 namespace pplan {
 using namespace parc;

@@ -13,6 +13,17 @@
 // k_tgen_draw uses, so parc_tgen_generate gives the bits of parc_tgen_draw_plan + parc_tgen_generate_with.  Integer LDS atomics only.
 // LDS: boxes 2.3 KB, stairs 0.8 KB (static); paths 8 B per cell (dynamic): 2 KB at 16 x 16, 32 KB at 64 x 64 (5 waves per CU there).
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/parc_env.h"
+#include "parc_common.hpp"
+#include "parc_math.hpp"
 
 namespace tgen {
 using namespace parc;

@@ -1,0 +1,8 @@
+// parc_tools.hip -- the stage-2 motion tools of include/parc_env.h as one translation unit, apart from the env (parc_env.hip).
+// Every header includes what it uses; the order below does not matter.
+#include "parc_clip_batch.hpp"       // host code the motion-tool handles share: mopt::Model setup, clip-batch validation and upload
+#include "parc_motion_opt.hpp"       // parc_mopt_*: the batched kinematic motion optimiser (defines mopt::Model / mopt::Clips)
+#include "parc_motion_terrain.hpp"   // parc_mterr_*: motion-terrain analysis
+#include "parc_motion_sampler.hpp"   // parc_msamp_*: the generator's motion-window sampler
+#include "parc_path_planner.hpp"     // parc_pathplan_*: stage 2's batched A* terrain path planner
+#include "parc_terrain_gen.hpp"      // parc_tgen_*: stage 2's BOXES / PATHS / STAIRS terrain generators, batched

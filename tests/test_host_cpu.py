@@ -317,7 +317,8 @@ def test_quat_to_exp_map_host_helper_matches_reference_rows():
 def test_dynamics_kernel_of_the_built_library_uses_no_scratch(tmp_path):
     """k_dynamics_wave keeps every body of a chain in registers: that needs its body loops fully unrolled (build flag
     -pragma-unroll-threshold, __graft_entry__.py) -- with the loops rolled the per-body arrays turn into ~1 KB of scratch per lane and the
-    kernel is several times slower, silently.  Read from the code object of the library as built: private segment 0, 1 wave per SIMD."""
+    kernel is several times slower, silently.  Read from the code objects of the library as built (one per translation unit): private
+    segment 0, 1 wave per SIMD; and no motion-tool kernel shares the code object, i.e. the translation unit, of k_dynamics_wave."""
     import re
     import shutil
     import subprocess
@@ -328,14 +329,17 @@ def test_dynamics_kernel_of_the_built_library_uses_no_scratch(tmp_path):
     so = tmp_path / "lib.so"
     shutil.copy(L.LIB_PATH, so)
     subprocess.check_call([objdump, "--offloading", str(so)], cwd=str(tmp_path), stdout=subprocess.DEVNULL)
-    co = [f for f in os.listdir(tmp_path) if "gfx950" in f]
-    assert len(co) == 1, os.listdir(tmp_path)
-    notes = subprocess.check_output([readelf, "--notes", str(tmp_path / co[0])], text=True)
-    kern = {}
-    for blk in notes.split("- .agpr_count:")[1:]:     # one metadata block per kernel
-        m = re.search(r"\.name:\s+(\S+)", blk)
-        if m:
-            kern[m.group(1)] = {k: int(v) for k, v in re.findall(r"\.(private_segment_fixed_size|vgpr_count|sgpr_count|group_segment_fixed_size):\s+(\d+)", blk)}
+    co = sorted(f for f in os.listdir(tmp_path) if "gfx950" in f)   # one code object per translation unit: the env, the motion tools
+    assert co, os.listdir(tmp_path)
+    kern, home = {}, {}
+    for c in co:
+        notes = subprocess.check_output([readelf, "--notes", str(tmp_path / c)], text=True)
+        for blk in notes.split("- .agpr_count:")[1:]:     # one metadata block per kernel
+            m = re.search(r"\.name:\s+(\S+)", blk)
+            if m:
+                assert m.group(1) not in kern, m.group(1)
+                kern[m.group(1)] = {k: int(v) for k, v in re.findall(r"\.(private_segment_fixed_size|vgpr_count|sgpr_count|group_segment_fixed_size):\s+(\d+)", blk)}
+                home[m.group(1)] = c
     wave = [v for k, v in kern.items() if "k_dynamics_wave" in k]
     assert len(wave) == 2, list(kern)                   # the pd instantiation and k_dynamics_wave_ff (the other control modes)
     for wk in wave:
@@ -343,3 +347,8 @@ def test_dynamics_kernel_of_the_built_library_uses_no_scratch(tmp_path):
         assert wk["vgpr_count"] > 256, wk               # VGPRs + AGPRs of the one resident wave per SIMD
     post = [v for k, v in kern.items() if "k_env_post" in k]
     assert len(post) == 9 and all(p["vgpr_count"] <= 102 for p in post), post   # (STEP, OBS) x MIRROR, the two track_root=false STEP instantiations, three with global_obs; 5 waves per SIMD need <= 102 registers
+    # the motion tools are a unit of their own (parc_tools.hip): an edit of a tool must not recompile k_dynamics_wave
+    env_co = {home[k] for k in kern if "k_dynamics_wave" in k}
+    tools = [k for k in kern if re.match(r"_ZN(4mopt|5mterr|5msamp|5pplan|4tgen)\d", k)]
+    assert len(env_co) == 1 and len(tools) >= 5, (env_co, tools)
+    assert not [k for k in tools if home[k] in env_co], [k for k in tools if home[k] in env_co]
