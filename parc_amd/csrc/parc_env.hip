@@ -23,11 +23,13 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/parc_env.h"
 #include "parc_common.hpp"    // what this unit shares with parc_tools.hip: g_err / fail / HIPCHK, MotionMeta, frame_blend, philox4
 #include "parc_math.hpp"
+#include "parc_rowmap.hpp"    // row phase of k_env_post: (pass, lane) -> (row, slot)
 #include "parc_dynamics.hpp"
 #include "parc_dynamics_coop.hpp"
 #include "parc_dynamics_wave.hpp"
@@ -83,6 +85,7 @@ struct StepParams {
     const float *hf; int X, Y; float min_x, min_y, dx, dy; int tile_r;
     float rdx, rdy;      // correctly rounded 1/dx, 1/dy (host): the ray loop divides by multiply + one exact correction
     unsigned tile_mul;   // idx / (2 tile_r + 1) == (idx * tile_mul) >> 16 for every tile cell (checked on the host)
+    unsigned row_mul;    // joint item j of the row phase: j / (B - 1) == (j * row_mul) >> 16 (parc_rowmap.hpp, checked on the host)
     float tstep[8];      // control_dt * tar_obs_steps (fp32 product, mgdm_dm_util.py:232)
     // tables
     const float4 *records; const MotionMeta *meta; const float *motion_offsets; const float *env_offsets;
@@ -314,9 +317,12 @@ __global__ __launch_bounds__(256, 5) void k_env_post(const StepParams P, const i
         else if (lane == 31) src = P.buf.char_root_ang_vel + 3 * (size_t)e;
         if (src) { aux0 = src[0]; aux1 = src[1]; aux2 = src[2]; }
     }
-    const int qi = lane & 15;
+    // the lane's (row, slot) item of the two row passes (parc_rowmap.hpp): pass A = every root item + the first 48 joint items, pass B = joints
+    // as row * 16 + slot, -1 = none (one register per pass is all the row phase keeps across the ray loop)
+    const int item[2] = {parc_rowmap_item<true>(lane, B, 2 + S, P.row_mul), parc_rowmap_item<false>(lane, B, 2 + S, P.row_mul)};
     float4 prepq = make_float4(0.f, 0.f, 0.f, 1.f);
-    if (lane < 16) prepq = P.prep[(size_t)e * 16 + lane]; // slot 0 heading terms, 1..B-1 character joint quats (k_env_prep)
+    // slot 0 heading terms (lane 0), 1..B-1 character joint quats (k_env_prep): row 0's items all sit in pass A
+    if ((unsigned)item[0] < 15u) prepq = P.prep[(size_t)e * 16 + item[0]];
     float2 rayp[RAY_UNROLL];
 #pragma unroll
     for (int i = 0; i < RAY_UNROLL; ++i) {
@@ -342,7 +348,7 @@ __global__ __launch_bounds__(256, 5) void k_env_post(const StepParams P, const i
     const Q4 root_rot = mk4(crr[0], crr[1], crr[2], crr[3]);
     const float gx = root_pos.x + eox, gy = root_pos.y + eoy, gz = root_pos.z + eoz; // ig_parkour_env.py:522
 
-    // (c) reference motion: rows 1..1+S (row = pass*4 + lane/16), two 512-byte frame records per sample.  The frame pair and blend factor
+    // (c) reference motion: rows 1..1+S (the lane's item of each row pass), two 512-byte frame records per sample.  The frame pair and blend factor
     // of a sample (motion_lib.py:425-438) are formed once, by lane (sample & 7): sample 0 = the reference at t, sample s = look-ahead
     // target s; the row / contact / velocity lanes fetch theirs with a lane shuffle instead of evaluating the blend four times per lane.
     Blend myb;
@@ -358,15 +364,15 @@ __global__ __launch_bounds__(256, 5) void k_env_post(const StepParams P, const i
     Blend bl[2];
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
-        const int r = p * 4 + (lane >> 4);
+        const int r = max(item[p], 0) >> 4;
         const int src = max(r - 1, 0);
         bl[p].b = __shfl(myb.b, src, 64);
         bl[p].i0 = __shfl(myb.i0, src, 64);
         bl[p].i1 = min(bl[p].i0 + 1, last_frame); // = frame_blend's i1
         fA[p] = make_float4(0.f, 0.f, 0.f, 1.f); fB[p] = fA[p];
-        if (r >= 1 && r < 2 + S) {
-            fA[p] = P.records[(size_t)bl[p].i0 * REC_F4 + qi];
-            fB[p] = P.records[(size_t)bl[p].i1 * REC_F4 + qi];
+        if (r >= 1) {
+            fA[p] = P.records[(size_t)bl[p].i0 * REC_F4 + (item[p] & 15)];
+            fB[p] = P.records[(size_t)bl[p].i1 * REC_F4 + (item[p] & 15)];
         }
     }
     // (d) contacts of the 1+S samples (lanes < 4(1+S)) / velocity block of sample 0 (lanes 32..)
@@ -491,70 +497,74 @@ __global__ __launch_bounds__(256, 5) void k_env_post(const StepParams P, const i
     }
     STAMP(2);
 
-    // ================= 8 rows x 16 lanes: quaternions of char / ref / targets + tan-norm observations =================
+    // ================= row items: quaternions of char / ref / targets + tan-norm observations =================
+    // One body for both passes.  ROOT (pass A) carries the code of the root items (slot 0 = root rotation, slot 15 = root position: the
+    // position lerp with its loop and terrain offsets, the heading products) and of rows 0 and 1, whose joints all sit in pass A; pass B
+    // is compiled without any of it: joint items of target rows only.
+    static_assert(2 * (PARC_MAX_BODIES - 2) <= PARC_ROWMAP_JOINTS_A, "the joints of rows 0 and 1 must fit into pass A");
+    auto row_pass = [&](auto root_tag, const int itm, const float4 A, const float4 Bv, const float bb) {
+        constexpr bool ROOT = decltype(root_tag)::value;
+        if (itm < 0) return;
+        const int r = itm >> 4, i = itm & 15;
+        const bool is_rot = ROOT && i == 0, is_pos = ROOT && i == 15;
+        const bool row0 = ROOT && r == 0, row1 = ROOT && r == 1;
+        float4 res = make_float4(0.f, 0.f, 0.f, 1.f);
+        if (row0) { // character: dof -> quat (kin_char_model.py:586)
+            if (is_rot) res = root_rot;
+            else if (is_pos) res = make_float4(root_pos.x, root_pos.y, root_pos.z, 0.f);
+            else res = prepq;
+        } else { // reference motion sample (motion_lib.py:94-128)
+            if (is_pos) {
+                const float a = 1.0f - bb;
+                res.x = a * A.x + bb * Bv.x;
+                res.y = a * A.y + bb * Bv.y;
+                res.z = a * A.z + bb * Bv.z;
+                res.w = 0.f;
+                if (meta.loop == PARC_LOOP_WRAP) { // _calc_loop_offset :440
+                    float t = mt;
 #pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        const int r = p * 4 + (lane >> 4);
-        const int i = qi;
-        if (r < 2 + S) {
-            float4 res = make_float4(0.f, 0.f, 0.f, 1.f);
-            if (r == 0) { // character: dof -> quat (kin_char_model.py:586)
-                if (i == 0) res = root_rot;
-                else if (i == 15) res = make_float4(root_pos.x, root_pos.y, root_pos.z, 0.f);
-                else if (i < B) res = prepq;
-            } else { // reference motion sample (motion_lib.py:94-128)
-                const float4 A = fA[p], Bv = fB[p];
-                const float bb = bl[p].b;
-                if (i == 15) {
-                    const float a = 1.0f - bb;
-                    res.x = a * A.x + bb * Bv.x;
-                    res.y = a * A.y + bb * Bv.y;
-                    res.z = a * A.z + bb * Bv.z;
-                    res.w = 0.f;
-                    if (meta.loop == PARC_LOOP_WRAP) { // _calc_loop_offset :440
-                        float t = mt;
-#pragma unroll
-                        for (int q = 0; q < PARC_MAX_TAR_STEPS; ++q) t = (r - 2 == q) ? mt + P.tstep[q] : t;
-                        const float ph = floorf(t / meta.length);
-                        res.x = res.x + ph * meta.dx; res.y = res.y + ph * meta.dy; res.z = res.z + ph * meta.dz;
-                    }
-                    res.x = res.x + offx; // _move_to_motion_terrain dm_env.py:554
-                    res.y = res.y + offy;
-                } else if (i < B) {
-                    res = slerp_rr(A, Bv, bb);
+                    for (int q = 0; q < PARC_MAX_TAR_STEPS; ++q) t = (r - 2 == q) ? mt + P.tstep[q] : t;
+                    const float ph = floorf(t / meta.length);
+                    res.x = res.x + ph * meta.dx; res.y = res.y + ph * meta.dy; res.z = res.z + ph * meta.dz;
                 }
-            }
-            if (i >= 1 && i < B) { // the FK chains multiply parent (x) (lr (x) q): the inner product is formed here, once per joint,
-                                   // instead of once per chain level (same operations, same order)
-                const Q4 lq = P.lr_identity ? res : quat_mul(mk4(s_tab.lr[i][0], s_tab.lr[i][1], s_tab.lr[i][2], s_tab.lr[i][3]), res);
-                if (r < 2) { s_lq[r][i] = lq; s_q[r][i] = res; } else s_q[r][i] = lq;
+                res.x = res.x + offx; // _move_to_motion_terrain dm_env.py:554
+                res.y = res.y + offy;
             } else {
-                s_q[r][i] = res;
-            }
-            if (r == 1) { // optional mirrors of the reference's ref_* tensors
-                if (MIRROR && i == 0 && P.buf.ref_root_rot) *(float4 *)(P.buf.ref_root_rot + 4 * (size_t)e) = res;
-                if (MIRROR && i >= 1 && i < B && P.buf.ref_joint_rot) *(float4 *)(P.buf.ref_joint_rot + 4 * ((size_t)e * J + i - 1)) = res;
-                if (MIRROR && i == 15 && P.buf.ref_root_pos) {
-                    float *o = P.buf.ref_root_pos + 3 * (size_t)e;
-                    o[0] = res.x; o[1] = res.y; o[2] = res.z;
-                }
-            } else if (r == 0 || TAROBS) { // observation pieces (ig_char_env.py:582, mgdm_dm_util.py:405)
-                const int base = r == 0 ? 0 : P.off_tar + (r - 2) * P.tar_w;
-                if (i < B) {
-                    const Q4 qq = (i == 0 && !GLOBALOBS) ? quat_mul(hinv, res) : res;
-                    float tn[6];
-                    quat_to_tan_norm(qq, tn);
-                    const int o = r == 0 ? oc + (i == 0 ? 0 : 12 + 6 * (i - 1)) : base + 3 + 6 * i;
-#pragma unroll
-                    for (int c = 0; c < 6; ++c) s_obs[o + c] = tn[c];
-                } else if (i == 15 && r >= 2) {
-                    const V3 rpd = mk3(res.x - root_pos.x, res.y - root_pos.y, res.z - root_pos.z);
-                    const V3 rpo = GLOBALOBS ? rpd : quat_rotate(hinv, rpd);
-                    s_obs[base + 0] = rpo.x; s_obs[base + 1] = rpo.y; s_obs[base + 2] = rpo.z;
-                }
+                res = slerp_rr(A, Bv, bb);
             }
         }
-    }
+        if (!is_rot && !is_pos) { // the FK chains multiply parent (x) (lr (x) q): the inner product is formed here, once per joint,
+                                  // instead of once per chain level (same operations, same order)
+            const Q4 lq = P.lr_identity ? res : quat_mul(mk4(s_tab.lr[i][0], s_tab.lr[i][1], s_tab.lr[i][2], s_tab.lr[i][3]), res);
+            if (row0 || row1) { s_lq[r][i] = lq; s_q[r][i] = res; } else s_q[r][i] = lq;
+        } else {
+            s_q[r][i] = res;
+        }
+        if (row1) { // optional mirrors of the reference's ref_* tensors
+            if (MIRROR && is_rot && P.buf.ref_root_rot) *(float4 *)(P.buf.ref_root_rot + 4 * (size_t)e) = res;
+            if (MIRROR && !is_rot && !is_pos && P.buf.ref_joint_rot) *(float4 *)(P.buf.ref_joint_rot + 4 * ((size_t)e * J + i - 1)) = res;
+            if (MIRROR && is_pos && P.buf.ref_root_pos) {
+                float *o = P.buf.ref_root_pos + 3 * (size_t)e;
+                o[0] = res.x; o[1] = res.y; o[2] = res.z;
+            }
+        } else if (row0 || TAROBS) { // observation pieces (ig_char_env.py:582, mgdm_dm_util.py:405)
+            const int base = row0 ? 0 : P.off_tar + (r - 2) * P.tar_w;
+            if (!is_pos) {
+                const Q4 qq = (is_rot && !GLOBALOBS) ? quat_mul(hinv, res) : res;
+                float tn[6];
+                quat_to_tan_norm(qq, tn);
+                const int o = row0 ? oc + (is_rot ? 0 : 12 + 6 * (i - 1)) : base + 3 + 6 * i;
+#pragma unroll
+                for (int c = 0; c < 6; ++c) s_obs[o + c] = tn[c];
+            } else if (!row0) {
+                const V3 rpd = mk3(res.x - root_pos.x, res.y - root_pos.y, res.z - root_pos.z);
+                const V3 rpo = GLOBALOBS ? rpd : quat_rotate(hinv, rpd);
+                s_obs[base + 0] = rpo.x; s_obs[base + 1] = rpo.y; s_obs[base + 2] = rpo.z;
+            }
+        }
+    };
+    row_pass(std::true_type(), item[0], fA[0], fB[0], bl[0].b);
+    row_pass(std::false_type(), item[1], fA[1], fB[1], bl[1].b);
     // ---- contacts of the 1+S samples and the velocity block of sample 0 ---------------------------------
     if (lane < 4 * (1 + S)) {
         const int s = lane >> 2, c = lane & 3;
@@ -602,13 +612,13 @@ __global__ __launch_bounds__(256, 5) void k_env_post(const StepParams P, const i
                 s_fk[k * 16] = make_float4(ppos.x, ppos.y, ppos.z, 0.f);
                 if (MIRROR && P.tracking) s_br[k][0] = prot;
             }
+            int b = s_tab.fk_paths[c][0];
 #pragma unroll 1
-            for (int d = 0; d < PARC_MAX_FK_DEPTH; ++d) {
-                const int b = s_tab.fk_paths[c][d];
-                if (b < 0) break;
+            for (int d = 0; d < PARC_MAX_FK_DEPTH && b >= 0; ++d) {
+                const int nb = d + 1 < PARC_MAX_FK_DEPTH ? s_tab.fk_paths[c][d + 1] : -1; // the chain's next body, known before the product is formed
                 const V3 wt = quat_rotate(prot, mk3(s_tab.lt[b][0], s_tab.lt[b][1], s_tab.lt[b][2]));
                 ppos = mk3(ppos.x + wt.x, ppos.y + wt.y, ppos.z + wt.z);
-                prot = quat_mul(prot, jq[b]);
+                if (nb >= 0 || (MIRROR && P.tracking)) prot = quat_mul(prot, jq[b]); // a leaf's rotation is only read by the tracking-error mirror
                 if (k < 2) {
                     s_fk[k * 16 + b] = make_float4(ppos.x, ppos.y, ppos.z, 0.f);
                     if (MIRROR && P.tracking) s_br[k][b] = prot;
@@ -616,6 +626,7 @@ __global__ __launch_bounds__(256, 5) void k_env_post(const StepParams P, const i
                     const int slot = s_tab.key_slot[b];
                     if (slot >= 0) s_fk[32 + (k - 2) * 8 + slot] = make_float4(ppos.x, ppos.y, ppos.z, 0.f);
                 }
+                b = nb;
             }
         }
     }
@@ -1714,6 +1725,8 @@ extern "C" int parc_env_create(const ParcEnvConfig *cfg, ParcEnv **out) {
     sp.off_key = sp.off_dofvel + D;
     sp.off_tar = sp.off_key + 3 * K;
     sp.tar_w = 3 + 6 + 6 * J + 3 * K;
+    sp.row_mul = parc_rowmap_mul(B);
+    if (!parc_rowmap_mul_ok(B, sp.row_mul)) { delete e; return fail(PARC_ERR_INVALID, "internal: row item multiplier"); }
     sp.lr_identity = 1;
     for (int b = 0; b < B; ++b)
         if (!(cfg->model.local_rotation[b][0] == 0.f && cfg->model.local_rotation[b][1] == 0.f && cfg->model.local_rotation[b][2] == 0.f && cfg->model.local_rotation[b][3] == 1.f)) sp.lr_identity = 0;
