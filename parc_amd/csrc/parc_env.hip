@@ -30,6 +30,7 @@
 #include "parc_common.hpp"    // what this unit shares with parc_tools.hip: g_err / fail / HIPCHK, MotionMeta, frame_blend, philox4
 #include "parc_math.hpp"
 #include "parc_rowmap.hpp"    // row phase of k_env_post: (pass, lane) -> (row, slot)
+#include "parc_lanetab.hpp"   // prefetch phase of k_env_post: what depends on the lane and on the handle's constants only
 #include "parc_dynamics.hpp"
 #include "parc_dynamics_coop.hpp"
 #include "parc_dynamics_wave.hpp"
@@ -66,6 +67,7 @@ struct DevTables { // global memory; `h` is staged into LDS, the rest is read on
     float dof_err_w[PARC_MAX_DOFS];
     float contact_w[16];
     float pose_term_dist[16];
+    ParcLaneEntry lane[64];  // parc_lanetab.hpp: refilled when the tile radius changes (parc_env_load_terrain)
 };
 
 struct StepParams {
@@ -84,8 +86,6 @@ struct StepParams {
     // terrain
     const float *hf; int X, Y; float min_x, min_y, dx, dy; int tile_r;
     float rdx, rdy;      // correctly rounded 1/dx, 1/dy (host): the ray loop divides by multiply + one exact correction
-    unsigned tile_mul;   // idx / (2 tile_r + 1) == (idx * tile_mul) >> 16 for every tile cell (checked on the host)
-    unsigned row_mul;    // joint item j of the row phase: j / (B - 1) == (j * row_mul) >> 16 (parc_rowmap.hpp, checked on the host)
     float tstep[8];      // control_dt * tar_obs_steps (fp32 product, mgdm_dm_util.py:232)
     // tables
     const float4 *records; const MotionMeta *meta; const float *motion_offsets; const float *env_offsets;
@@ -307,27 +307,36 @@ __global__ __launch_bounds__(256, 5) void k_env_post(const StepParams P, const i
     int tabreg[HN];
 #pragma unroll
     for (int i = 0; i < HN; ++i) { const int w = lane + 64 * i; tabreg[i] = w < HW ? ((const int *)&T->h)[w] : 0; }
-    float dofv = 0.f;
-    if (lane < D) dofv = P.buf.char_dof_vel[(size_t)e * D + lane];
-    float aux0 = 0.f, aux1 = 0.f, aux2 = 0.f; // lanes 32..32+B: contact force; 30/31: root (ang) vel
+    // the lane's table entry (parc_lanetab.hpp): the address needs the lane only.  Every index it yields is in bounds on every lane, so
+    // the loads below carry no branch and no default; a lane without an item loads a neighbour's value that nothing consumes
+    unsigned lt[PARC_LANETAB_WORDS];
     {
-        const float *src = nullptr;
-        if (lane >= 32 && lane < 32 + B) src = P.buf.contact_forces + 3 * ((size_t)e * B + (lane - 32));
-        else if (lane == 30) src = P.buf.char_root_vel + 3 * (size_t)e;
-        else if (lane == 31) src = P.buf.char_root_ang_vel + 3 * (size_t)e;
-        if (src) { aux0 = src[0]; aux1 = src[1]; aux2 = src[2]; }
+        static_assert(sizeof(ParcLaneEntry) == sizeof(uint4), "one 16-byte load per lane");
+        const uint4 l0 = *reinterpret_cast<const uint4 *>(T->lane + lane);
+        lt[0] = l0.x; lt[1] = l0.y; lt[2] = l0.z; lt[3] = l0.w;
+    }
+    const float dofv = P.buf.char_dof_vel[(size_t)e * D + parc_lt_dof(lt)];
+    const unsigned role = parc_lt_role(lt); // lanes 32..32+B: contact force; 30/31: root (ang) vel
+    float aux0, aux1, aux2;
+    {
+        const float *src = P.buf.contact_forces + 3 * (size_t)e * B + parc_lt_force_off(lt);
+        src = role == PARC_LT_ROLE_ROOT_VEL ? P.buf.char_root_vel + 3 * (size_t)e : src;
+        src = role == PARC_LT_ROLE_ROOT_ANG_VEL ? P.buf.char_root_ang_vel + 3 * (size_t)e : src;
+        aux0 = src[0]; aux1 = src[1]; aux2 = src[2];
     }
     // the lane's (row, slot) item of the two row passes (parc_rowmap.hpp): pass A = every root item + the first 48 joint items, pass B = joints
     // as row * 16 + slot, -1 = none (one register per pass is all the row phase keeps across the ray loop)
-    const int item[2] = {parc_rowmap_item<true>(lane, B, 2 + S, P.row_mul), parc_rowmap_item<false>(lane, B, 2 + S, P.row_mul)};
-    float4 prepq = make_float4(0.f, 0.f, 0.f, 1.f);
-    // slot 0 heading terms (lane 0), 1..B-1 character joint quats (k_env_prep): row 0's items all sit in pass A
-    if ((unsigned)item[0] < 15u) prepq = P.prep[(size_t)e * 16 + item[0]];
+    const int item[2] = {parc_lt_item(lt, 0), parc_lt_item(lt, 1)};
+    // slot 0 heading terms (lane 0), 1..B-1 character joint quats (k_env_prep): row 0's items all sit in pass A, where the record slot
+    // of a row-0 lane is its slot of this record too (lane 0: slot 0, read back by every lane below)
+    const float4 prepq = P.prep[(size_t)e * 16 + parc_lt_row_slot(lt, 0)];
     float2 rayp[RAY_UNROLL];
+    // ray lane + 64 i, clamped to the last ray (parc_lt_ray_off).  A slot wholly past R (top < 0, i.e. 64 i >= R) is not loaded and stays
+    // unset: the ray loop reads slot i under `base + 64 * i < P.R` (tile path) or `r < P.R` (gathers) only, which imply top >= 0
 #pragma unroll
     for (int i = 0; i < RAY_UNROLL; ++i) {
-        const int r = lane + 64 * i;
-        rayp[i] = r < P.R ? ((const float2 *)P.ray_points)[r] : make_float2(0.f, 0.f);
+        const int top = parc_lt_ray_top(P.R, i); // uniform
+        if (top >= 0) rayp[i] = *(const float2 *)((const char *)P.ray_points + parc_lt_ray_off(lane, i, top));
     }
 
     // (b) bookkeeping + time (ig_env.py:391-394, dm_env.py:547-552): uniform, scalar loads
@@ -364,48 +373,32 @@ __global__ __launch_bounds__(256, 5) void k_env_post(const StepParams P, const i
     Blend bl[2];
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
-        const int r = max(item[p], 0) >> 4;
-        const int src = max(r - 1, 0);
-        bl[p].b = __shfl(myb.b, src, 64);
-        bl[p].i0 = __shfl(myb.i0, src, 64);
+        const int src4 = (int)parc_lt_src4(lt, p); // 4 x the sample of the item's row (sample 0 on row 0 and on a lane without an item)
+        bl[p].b = __int_as_float(__builtin_amdgcn_ds_bpermute(src4, __float_as_int(myb.b)));
+        bl[p].i0 = __builtin_amdgcn_ds_bpermute(src4, myb.i0);
         bl[p].i1 = min(bl[p].i0 + 1, last_frame); // = frame_blend's i1
-        fA[p] = make_float4(0.f, 0.f, 0.f, 1.f); fB[p] = fA[p];
-        if (r >= 1) {
-            fA[p] = P.records[(size_t)bl[p].i0 * REC_F4 + (item[p] & 15)];
-            fB[p] = P.records[(size_t)bl[p].i1 * REC_F4 + (item[p] & 15)];
-        }
+        const unsigned slot = parc_lt_row_slot(lt, p);
+        fA[p] = P.records[(size_t)bl[p].i0 * REC_F4 + slot];
+        fB[p] = P.records[(size_t)bl[p].i1 * REC_F4 + slot];
     }
     // (d) contacts of the 1+S samples (lanes < 4(1+S)) / velocity block of sample 0 (lanes 32..)
-    float4 cA = make_float4(0.f, 0.f, 0.f, 0.f), cB = cA;
-    float cblend = 0.f;
+    // (every other lane: contact slot 0 of sample 0)
     const int nvel = 2 + (D + 3) / 4;
-    {
-        const int src = lane < 4 * (1 + S) ? lane >> 2 : 0;
-        const float b2b = __shfl(myb.b, src, 64);
-        const int b2i0 = __shfl(myb.i0, src, 64), b2i1 = min(b2i0 + 1, last_frame);
-        if (lane < 4 * (1 + S)) {
-            const int c = lane & 3;
-            cblend = b2b;
-            cA = P.records[(size_t)b2i0 * REC_F4 + REC_Q_CONTACT + c];
-            cB = P.records[(size_t)b2i1 * REC_F4 + REC_Q_CONTACT + c];
-        } else if (lane >= 32 && lane < 32 + nvel) { // velocities come from frame idx0 un-interpolated (:103-109)
-            cA = P.records[(size_t)b2i0 * REC_F4 + REC_Q_VEL + (lane - 32)];
-        }
-    }
-    // (e) terrain tile cells
-    const int tr = P.tile_r, TW = 2 * tr + 1, ncell = tr >= 0 ? TW * TW : 0;
+    const int src4c = (int)parc_lt_src4(lt, 2);
+    const float cblend = __int_as_float(__builtin_amdgcn_ds_bpermute(src4c, __float_as_int(myb.b)));
+    const int b2i0 = __builtin_amdgcn_ds_bpermute(src4c, myb.i0), b2i1 = min(b2i0 + 1, last_frame);
+    const float4 cA = P.records[(size_t)b2i0 * REC_F4 + parc_lt_cv_slot0(lt)]; // velocities come from frame idx0 un-interpolated (:103-109)
+    const float4 cB = P.records[(size_t)b2i1 * REC_F4 + parc_lt_cv_slot1(lt)];
+    // (e) terrain tile cells: (a, bq) of the lane's five cells from the table, (0, 0) where the tile ends (or there is none: tr < 0)
+    static_assert(64 * PARC_LANETAB_TILE_CELLS == TILE_MAX_CELLS && TILE_MAX_CELLS * sizeof(float) == sizeof(s_fk_all[0]), "the five tile stores of a lane stay inside s_fk");
+    const int tr = P.tile_r, TW = 2 * tr + 1;
     // (the origin is kept within +-2^22 cells so that it and the tile bounds are exact as floats: the ray loop clamps in float)
     const int ox = min(max(cell_index(gx, P.min_x, P.dx) - tr, -(1 << 22)), 1 << 22), oy = min(max(cell_index(gy, P.min_y, P.dy) - tr, -(1 << 22)), 1 << 22);
     float tilev[5];
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
-        const int idx = lane + 64 * i;
-        tilev[i] = 0.f;
-        if (idx < ncell) {
-            const int a = (int)(((unsigned)idx * P.tile_mul) >> 16), bq = idx - a * TW;
-            const int cx = min(max(ox + a, 0), P.X - 1), cy = min(max(oy + bq, 0), P.Y - 1);
-            tilev[i] = P.hf[(size_t)cx * P.Y + cy];
-        }
+        const int cx = min(max(ox + (int)parc_lt_cell_a(lt, i), 0), P.X - 1), cy = min(max(oy + (int)parc_lt_cell_b(lt, i), 0), P.Y - 1);
+        tilev[i] = P.hf[(size_t)cx * P.Y + cy];
     }
 
     // ================= heading terms from k_env_prep (uniform), LDS fills =================
@@ -418,18 +411,18 @@ __global__ __launch_bounds__(256, 5) void k_env_post(const StepParams P, const i
         s_obs[P.off_dofvel + lane] = dofv;
     }
     if (OBSVAR && oc && lane == 29) s_obs[0] = root_pos.z; // root_height_obs (ig_char_env.py:620-622)
-    if (lane == 30 || lane == 31) { // root velocities in the heading frame (ig_char_env.py:593-597)
+    if (role == PARC_LT_ROLE_ROOT_VEL || role == PARC_LT_ROLE_ROOT_ANG_VEL) { // root velocities in the heading frame (ig_char_env.py:593-597)
         const V3 r = GLOBALOBS ? mk3(aux0, aux1, aux2) : quat_rotate(hinv, mk3(aux0, aux1, aux2));
-        const int o = oc + (lane == 30 ? 6 : 9);
+        const int o = oc + (role == PARC_LT_ROLE_ROOT_VEL ? 6 : 9);
         s_obs[o + 0] = r.x; s_obs[o + 1] = r.y; s_obs[o + 2] = r.z;
     }
-    if (lane >= 32 && lane < 32 + B) { // contact flags + clamped force norms (ig_parkour_env.py:655-662, mgdm_dm_util.py:505-508)
+    if (role == PARC_LT_ROLE_FORCE) { // contact flags + clamped force norms (ig_parkour_env.py:655-662, mgdm_dm_util.py:505-508)
         const float n = norm3(mk3(aux0, aux1, aux2));
         if (CONTACTOBS) orow[P.off_cc + (lane - 32)] = n > 1e-5f ? 1.f : 0.f;
         s_cfn[lane - 32] = fminf(n, 1.0f);
     }
 #pragma unroll
-    for (int i = 0; i < 5; ++i) { const int idx = lane + 64 * i; if (idx < ncell) s_tile[idx] = tilev[i]; }
+    for (int i = 0; i < 5; ++i) s_tile[lane + 64 * i] = tilev[i]; // past the tile's last cell: scratch that FK overwrites
     WAVE_SYNC();
     STAMP(1);
 
@@ -453,7 +446,7 @@ __global__ __launch_bounds__(256, 5) void k_env_post(const StepParams P, const i
 #pragma unroll
                 for (int i = 0; i < RAY_UNROLL; ++i) {
                     tix[i] = 0;
-                    if (base + 64 * i < P.R) { // uniform
+                    if (base + 64 * i < P.R) { // uniform; for base = 0 the condition under which the prefetch loaded rayp[i]
                         const float px = (rayp[i].x * ch - rayp[i].y * sh) + gx; // rotate_2d_vec torch_util.py:651
                         const float py = (rayp[i].x * sh + rayp[i].y * ch) + gy;
                         // nearest cell (cell_index_rcp), clamped to the tile while still a float: the bounds are small integers, so
@@ -1604,6 +1597,8 @@ struct ParcEnv {
     bool use_wave = false, wave_rejected = false;
     DevTables h_tab;
     DevTables *d_tab = nullptr;
+    unsigned row_mul = 0;  // joint item j of the row phase: j / (B - 1) == (j * row_mul) >> 16 (parc_rowmap.hpp, checked at create)
+    unsigned tile_mul = 0; // idx / (2 tile_r + 1) == (idx * tile_mul) >> 16 for every tile cell (checked when the terrain is loaded)
     float *d_ray = nullptr, *d_env_off = nullptr, *d_hf = nullptr, *d_motion_off = nullptr;
     float4 *d_records = nullptr;
     MotionMeta *d_meta = nullptr;
@@ -1725,8 +1720,9 @@ extern "C" int parc_env_create(const ParcEnvConfig *cfg, ParcEnv **out) {
     sp.off_key = sp.off_dofvel + D;
     sp.off_tar = sp.off_key + 3 * K;
     sp.tar_w = 3 + 6 + 6 * J + 3 * K;
-    sp.row_mul = parc_rowmap_mul(B);
-    if (!parc_rowmap_mul_ok(B, sp.row_mul)) { delete e; return fail(PARC_ERR_INVALID, "internal: row item multiplier"); }
+    e->row_mul = parc_rowmap_mul(B);
+    if (!parc_rowmap_mul_ok(B, e->row_mul)) { delete e; return fail(PARC_ERR_INVALID, "internal: row item multiplier"); }
+    if (!parc_lanetab_fill(t.lane, B, S, D, R, -1, e->row_mul, 0u)) { delete e; return fail(PARC_ERR_INVALID, "internal: lane table"); } // the tile cells follow with the terrain
     sp.lr_identity = 1;
     for (int b = 0; b < B; ++b)
         if (!(cfg->model.local_rotation[b][0] == 0.f && cfg->model.local_rotation[b][1] == 0.f && cfg->model.local_rotation[b][2] == 0.f && cfg->model.local_rotation[b][3] == 1.f)) sp.lr_identity = 0;
@@ -1966,6 +1962,23 @@ extern "C" int parc_env_load_terrain(ParcEnv *e, const float *hf, int32_t X, int
     if (!e || !hf || !motion_offsets || X < 1 || Y < 1 || T < 1 || !(dx > 0.f) || !(dy > 0.f)) return fail(PARC_ERR_INVALID, "bad terrain");
     if (!e->have_motions || M != e->M) return fail(PARC_ERR_STATE, "load_motions first; motion_offsets must have one row per motion");
     HIPCHK(hipSetDevice(e->cfg.device));
+    // terrain tile radius: farthest ray sample in cells, +1 for the two independent roundings.  Radius, index multiplier and the lane table
+    // that holds the tile cells (parc_lanetab.hpp) are formed before anything of the handle changes: a failure leaves it as it was
+    std::vector<float> ray(2 * (size_t)e->R);
+    HIPCHK(hipMemcpy(ray.data(), e->d_ray, sizeof(float) * 2 * e->R, hipMemcpyDeviceToHost));
+    float rmax = 0.f;
+    for (int r = 0; r < e->R; ++r) rmax = fmaxf(rmax, sqrtf(ray[2 * r] * ray[2 * r] + ray[2 * r + 1] * ray[2 * r + 1]));
+    int tr = (int)ceilf(rmax / fminf(dx, dy) + 0.01f); // max |round(a+d)-round(a)| = ceil(|d|)
+    if ((2 * tr + 1) * (2 * tr + 1) > TILE_MAX_CELLS) tr = -1; // fan too wide for the LDS tile: direct gathers
+    unsigned tile_mul = e->tile_mul;
+    if (tr >= 0) { // magic multiplier for idx / TW, verified for every cell of the tile
+        const unsigned TW = 2 * tr + 1;
+        tile_mul = (65536u + TW - 1) / TW;
+        for (unsigned idx = 0; idx < TW * TW; ++idx)
+            if (((idx * tile_mul) >> 16) != idx / TW) return fail(PARC_ERR_INVALID, "internal: tile index multiplier");
+    }
+    ParcLaneEntry lanes[64];
+    if (!parc_lanetab_fill(lanes, e->B, e->S, e->D, e->R, tr, e->row_mul, tile_mul)) return fail(PARC_ERR_INVALID, "internal: lane table");
     if (e->d_hf) (void)hipFree(e->d_hf);
     if (e->d_motion_off) (void)hipFree(e->d_motion_off);
     e->d_hf = nullptr; e->d_motion_off = nullptr;
@@ -1982,21 +1995,10 @@ extern "C" int parc_env_load_terrain(ParcEnv *e, const float *hf, int32_t X, int
     for (size_t q = 1; q < (size_t)X * Y; ++q) e->hf_max = fmaxf(e->hf_max, hf[q]);
     e->hf_min = hf[0];
     for (size_t q = 1; q < (size_t)X * Y; ++q) e->hf_min = fminf(e->hf_min, hf[q]);
-    // terrain tile radius: farthest ray sample in cells, +1 for the two independent roundings
-    std::vector<float> ray(2 * (size_t)e->R);
-    HIPCHK(hipMemcpy(ray.data(), e->d_ray, sizeof(float) * 2 * e->R, hipMemcpyDeviceToHost));
-    float rmax = 0.f;
-    for (int r = 0; r < e->R; ++r) rmax = fmaxf(rmax, sqrtf(ray[2 * r] * ray[2 * r] + ray[2 * r + 1] * ray[2 * r + 1]));
-    int tr = (int)ceilf(rmax / fminf(dx, dy) + 0.01f); // max |round(a+d)-round(a)| = ceil(|d|)
-    if ((2 * tr + 1) * (2 * tr + 1) > TILE_MAX_CELLS) tr = -1; // fan too wide for the LDS tile: direct gathers
     sp.tile_r = tr;
-    if (tr >= 0) { // magic multiplier for idx / TW, verified for every cell of the tile
-        const unsigned TW = 2 * tr + 1;
-        const unsigned mul = (65536u + TW - 1) / TW;
-        for (unsigned idx = 0; idx < TW * TW; ++idx)
-            if (((idx * mul) >> 16) != idx / TW) return fail(PARC_ERR_INVALID, "internal: tile index multiplier");
-        sp.tile_mul = mul;
-    }
+    e->tile_mul = tile_mul;
+    memcpy(e->h_tab.lane, lanes, sizeof(lanes));
+    HIPCHK(hipMemcpy(e->d_tab->lane, e->h_tab.lane, sizeof(e->h_tab.lane), hipMemcpyHostToDevice));
     const int stage_pad = (sp.off_tarc + 3) & ~3;
     e->lds_bytes = sizeof(float) * (size_t)stage_pad + (e->cfg.report_tracking_error ? 2 * 16 * sizeof(float4) : 0); // per wave of k_env_post
     e->sp.lds_wave_floats = (int)(e->lds_bytes / sizeof(float));
