@@ -205,16 +205,23 @@ typedef struct {
 const char *parc_last_error(void);
 int parc_abi_version(void);
 
-/* IGParkourEnv.__init__ (ig_parkour_env.py:43-149) minus Isaac Gym */
+/* IGParkourEnv.__init__ (ig_parkour_env.py:43-149) minus Isaac Gym.  The arguments are checked before the device is touched; on any
+ * failure nothing is left allocated and *out is not written.  parc_env_destroy(NULL) is a no-op. */
 int parc_env_create(const ParcEnvConfig *cfg, ParcEnv **out);
 void parc_env_destroy(ParcEnv *env);
 /* obs width for this configuration (IGEnv.get_obs_space, ig_env.py:86-96) */
 int parc_env_obs_dim(const ParcEnv *env);
 
-/* MotionLib._load_motion_file (motion_lib.py:255-401) */
+/* MotionLib._load_motion_file (motion_lib.py:255-401).  May be called again: the new set replaces the old one as the last step of the
+ * call, and every fail rate starts at 1 (dm_env.py:87).  A call that returns non-zero (PARC_ERR_INVALID: a clip of fewer than 2 frames,
+ * fps <= 0, a negative weight, more than 2^30 frames; PARC_ERR_HIP) leaves the handle as it was in every observable way: motion info,
+ * fail rates, and what step / reset / the graph step compute.  A successful load whose num_motions differs from the loaded terrain's M
+ * drops that terrain (its motion_offsets have one row per motion of the old set): the step-family calls return PARC_ERR_STATE until
+ * parc_env_load_terrain is called again.  A reload with the same num_motions keeps the terrain. */
 int parc_env_load_motions(ParcEnv *env, const ParcMotionClips *clips);
 /* DeepMimicEnv.build_terrain_square / load_terrain result (dm_env.py:157-316,447-463):
- * hf [X][Y] x-major, motion_offsets [M][T][2] */
+ * hf [X][Y] x-major, motion_offsets [M][T][2].  After parc_env_load_motions, with M = its num_motions (else PARC_ERR_STATE).  May be
+ * called again; like parc_env_load_motions, a call that returns non-zero leaves the handle, its previous terrain included, as it was. */
 int parc_env_load_terrain(ParcEnv *env, const float *hf_host, int32_t X, int32_t Y, float min_x, float min_y,
                           float dx, float dy, const float *motion_offsets_host, int32_t M, int32_t T);
 /* IGCharEnv._build_sim_tensors / IGParkourEnv._build_data_buffers tensor views */

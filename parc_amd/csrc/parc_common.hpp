@@ -1,6 +1,6 @@
 // parc_common.hpp — what the env unit (parc_env.hip) and the tools unit (parc_tools.hip) both use, and nothing else.
 //   host:   the thread's last error message (one instance for the whole library), fail / HIPCHK / PARC_TRY, blocks, the device arena
-//   device: Philox4x32-10, the motion table entry and the frame blend of motion_lib.py
+//   device: Philox4x32-10 and the frame blend of motion_lib.py (the motion table entry it reads: parc_motion_table.hpp)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/parc_env.h"
+#include "parc_motion_table.hpp"   // MotionMeta, and the host code that fills it
 
 // ================================================================================================
 // host side
@@ -22,8 +23,12 @@ static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 
 static unsigned blocks(long long n, int t) { return (unsigned)((n + t - 1) / t); }
 
-struct DeviceArena {                      // device buffers with one lifetime: freed together
+struct DeviceArena {                      // device buffers with one lifetime: freed together, by release() or with the arena
     std::vector<void *> ptrs;
+    DeviceArena() = default;
+    DeviceArena(const DeviceArena &) = delete;
+    DeviceArena &operator=(const DeviceArena &) = delete;
+    ~DeviceArena() { release(); }
     // p = count elements of T on the current device (16 B when count is 0), copied from the host array src when given
     template <typename T> int alloc(T *&p, long long count, const void *src = nullptr) {
         void *d = nullptr;
@@ -34,6 +39,13 @@ struct DeviceArena {                      // device buffers with one lifetime: f
         p = (T *)d;
         return PARC_OK;
     }
+    // p = count elements of T, every byte set to `byte`
+    template <typename T> int alloc_fill(T *&p, long long count, int byte = 0) {
+        PARC_TRY(alloc(p, count));
+        if (count > 0) HIPCHK(hipMemset(p, byte, (size_t)count * sizeof(T)));
+        return PARC_OK;
+    }
+    void swap(DeviceArena &o) { ptrs.swap(o.ptrs); }
     void release() {
         for (void *p : ptrs) (void)hipFree(p);
         ptrs.clear();
@@ -43,14 +55,6 @@ struct DeviceArena {                      // device buffers with one lifetime: f
 // ================================================================================================
 // device side
 // ================================================================================================
-struct MotionMeta { // 32 B
-    int start, nframes;
-    float length;
-    int loop;
-    float dx, dy, dz;
-    float fps;
-};
-
 struct Blend { int i0, i1; float b; };
 
 // motion_lib.py:425-438 (+ calc_phase :520)

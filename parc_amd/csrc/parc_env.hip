@@ -21,6 +21,7 @@
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <type_traits>
@@ -1581,6 +1582,10 @@ struct ParcEnv {
     int64_t F = 0;
     bool bound = false, have_motions = false, have_terrain = false;
     bool done_list_fresh = false;     // a step has produced a done list that parc_env_reset_done has not consumed yet
+    // The device memory of the handle, one arena per lifetime; the d_* members below are views into them.
+    DeviceArena mem;                  // create .. destroy: tables, prep records, done lists, dynamics tables, root shadow, manifold overflow, render geoms
+    DeviceArena motions;              // parc_env_load_motions: d_records, d_meta, d_weights, d_fail, d_cdf, d_motion_done
+    DeviceArena terrain;              // parc_env_load_terrain: d_hf, d_motion_off
     StepParams sp;
     float4 *d_prep = nullptr;
     std::string dev_options_s, describe_s; // the dev_options this handle was created with (owned copy) / parc_env_describe
@@ -1608,16 +1613,17 @@ struct ParcEnv {
     unsigned char *d_ema = nullptr;
     int *d_done_list = nullptr, *d_done_key = nullptr, *d_chunk_count = nullptr, *d_motion_done = nullptr, *d_reset_count = nullptr;
     int nchunks = 0;
-    float *d_scratch_jr = nullptr, *d_start_frac = nullptr;
+    float *d_scratch_jr = nullptr;
+    float *d_start_frac = nullptr;                 // parc_env_set_start_time_fraction (caller-owned)
     RenderGeoms *d_rgeom = nullptr;                // parc_env_render: the collision geoms, uploaded at creation
     float hf_max = 0.f;                            // highest column top (parc_env_load_terrain), bounds the renderer's terrain traversal
     float hf_min = 0.f;                            // lowest column top: the floor of the scene render's shadow-caster cull
-    char *d_scene = nullptr;                       // parc_env_render_scene workspace, allocated on the first call (scene_ws_bytes)
+    char *d_scene = nullptr;                       // parc_env_render_scene workspace, allocated on the first call (scene_ws_bytes), owned here
     int scene_cap = 0;                             // envs the workspace holds
     unsigned long long *d_reset_calls = nullptr;   // device counter of sampling resets (Philox call index)
-    const float *action_bound = nullptr;           // parc_env_bind_action
+    const float *action_bound = nullptr;           // parc_env_bind_action (caller-owned)
     hipGraphExec_t graph_exec = nullptr;           // parc_env_step_reset_graph
-    bool graph_dirty = true;
+    bool graph_dirty = true;                       // StepParams travels by value with every launch; a captured graph holds a copy
     bool force_ema_leader = false;                 // test switch PARC_EMA_LEADER=1: the large-library EMA path on a small library
     bool force_two_launch_curriculum = false;      // test switch PARC_CURRICULUM_TWO_LAUNCHES=1: k_done_scatter + k_fail_rate_ema on a small shard
     int grid_waves = 0;
@@ -1632,26 +1638,23 @@ struct ParcEnv {
     bool timing = false;               // parc_env_set_kernel_timing: record events around the kernels of every step
     std::vector<hipEvent_t> tev;       // 3 events per timed step (before dynamics, after dynamics, after the obs kernels)
     size_t tev_used = 0;
+
+    ParcEnv() = default;
+    ParcEnv(const ParcEnv &) = delete;
+    ParcEnv &operator=(const ParcEnv &) = delete;
+    ~ParcEnv() {
+        (void)hipSetDevice(cfg.device);
+        mem.release(); motions.release(); terrain.release();
+        if (d_scene) (void)hipFree(d_scene);
+        if (h_health) (void)hipHostFree(h_health);
+        for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
+        for (hipEvent_t x : tev) if (x) (void)hipEventDestroy(x);
+        if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
+    }
 };
 
 extern "C" const char *parc_last_error(void) { return g_err.c_str(); }
 extern "C" int parc_abi_version(void) { return PARC_ABI_VERSION; }
-
-static void free_dev(ParcEnv *e) {
-    void *ptrs[] = {e->d_man_ovf, e->d_root_shadow, e->d_prep, e->d_dyn, e->d_coop, e->d_wave, e->d_tab, e->d_ray, e->d_env_off, e->d_hf, e->d_motion_off, e->d_records, e->d_meta, e->d_weights, e->d_fail,
-                    e->d_cdf, e->d_ema, e->d_done_list, e->d_done_key, e->d_chunk_count, e->d_motion_done, e->d_reset_count, e->d_reset_calls,
-                    e->d_scratch_jr, e->d_rgeom, e->d_scene};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (e->h_health) (void)hipHostFree(e->h_health);
-    for (auto &ev : e->ev) if (ev) (void)hipEventDestroy(ev);
-    for (auto &ev : e->tev) if (ev) (void)hipEventDestroy(ev);
-    if (e->graph_exec) (void)hipGraphExecDestroy(e->graph_exec);
-}
-
-static int sync_params(ParcEnv *e) { // StepParams travels by value with every launch; a captured graph holds a copy
-    e->graph_dirty = true;
-    return PARC_OK;
-}
 
 extern "C" int parc_env_create(const ParcEnvConfig *cfg, ParcEnv **out) {
     if (!cfg || !out) return fail(PARC_ERR_INVALID, "null argument");
@@ -1663,6 +1666,7 @@ extern "C" int parc_env_create(const ParcEnvConfig *cfg, ParcEnv **out) {
     if (cfg->num_tar_obs_steps < 1 || cfg->num_tar_obs_steps > PARC_MAX_TAR_STEPS) return fail(PARC_ERR_INVALID, "tar_obs_steps: 1..6 entries");
     if (cfg->num_key_bodies < 0 || cfg->num_key_bodies > PARC_MAX_KEY_BODIES) return fail(PARC_ERR_INVALID, "key_bodies: at most 8");
     if (cfg->num_envs < 1) return fail(PARC_ERR_INVALID, "num_envs must be >= 1");
+    if (cfg->num_envs > 1024 * 1024) return fail(PARC_ERR_INVALID, "num_envs must be <= 1048576 per handle"); // 1024 chunks of 1024 (d_chunk_count)
     if (cfg->num_rays < 1 || cfg->num_rays > 4096 || !cfg->ray_points_host) return fail(PARC_ERR_INVALID, "ray fan: 1..4096 points");
     if (!cfg->env_offsets_host) return fail(PARC_ERR_INVALID, "env_offsets_host is required");
     for (int b = 1; b < m.num_bodies; ++b)
@@ -1677,7 +1681,7 @@ extern "C" int parc_env_create(const ParcEnvConfig *cfg, ParcEnv **out) {
     if (cfg->device < 0 || cfg->device >= ndev) return fail(PARC_ERR_INVALID, "device ordinal out of range");
     HIPCHK(hipSetDevice(cfg->device));
 
-    ParcEnv *e = new (std::nothrow) ParcEnv();
+    std::unique_ptr<ParcEnv> e(new (std::nothrow) ParcEnv()); // every failure below is a plain return: ~ParcEnv releases what exists
     if (!e) return fail(PARC_ERR_INVALID, "out of host memory");
     e->cfg = *cfg;
     e->dev_options_s = cfg->dev_options ? cfg->dev_options : "";
@@ -1698,12 +1702,12 @@ extern "C" int parc_env_create(const ParcEnvConfig *cfg, ParcEnv **out) {
     for (int p = 0; p < PARC_MAX_FK_PATHS; ++p)
         for (int d = 0; d < PARC_MAX_FK_DEPTH; ++d) {
             t.h.fk_paths[p][d] = m.fk_paths[p][d];
-            if (m.fk_paths[p][d] >= B) { delete e; return fail(PARC_ERR_INVALID, "fk_paths entry out of range"); }
+            if (m.fk_paths[p][d] >= B) return fail(PARC_ERR_INVALID, "fk_paths entry out of range");
         }
     const float dt_f = (float)cfg->control_dt;
     for (int s = 0; s < S; ++s) t.tstep[s] = dt_f * (float)cfg->tar_obs_steps[s];
     for (int k = 0; k < K; ++k) {
-        if (cfg->key_body_ids[k] < 0 || cfg->key_body_ids[k] >= B) { delete e; return fail(PARC_ERR_INVALID, "key body id out of range"); }
+        if (cfg->key_body_ids[k] < 0 || cfg->key_body_ids[k] >= B) return fail(PARC_ERR_INVALID, "key body id out of range");
         t.h.key_ids[k] = cfg->key_body_ids[k];
         if (t.h.key_slot[cfg->key_body_ids[k]] < 0) t.h.key_slot[cfg->key_body_ids[k]] = k;
     }
@@ -1721,8 +1725,8 @@ extern "C" int parc_env_create(const ParcEnvConfig *cfg, ParcEnv **out) {
     sp.off_tar = sp.off_key + 3 * K;
     sp.tar_w = 3 + 6 + 6 * J + 3 * K;
     e->row_mul = parc_rowmap_mul(B);
-    if (!parc_rowmap_mul_ok(B, e->row_mul)) { delete e; return fail(PARC_ERR_INVALID, "internal: row item multiplier"); }
-    if (!parc_lanetab_fill(t.lane, B, S, D, R, -1, e->row_mul, 0u)) { delete e; return fail(PARC_ERR_INVALID, "internal: lane table"); } // the tile cells follow with the terrain
+    if (!parc_rowmap_mul_ok(B, e->row_mul)) return fail(PARC_ERR_INVALID, "internal: row item multiplier");
+    if (!parc_lanetab_fill(t.lane, B, S, D, R, -1, e->row_mul, 0u)) return fail(PARC_ERR_INVALID, "internal: lane table"); // the tile cells follow with the terrain
     sp.lr_identity = 1;
     for (int b = 0; b < B; ++b)
         if (!(cfg->model.local_rotation[b][0] == 0.f && cfg->model.local_rotation[b][1] == 0.f && cfg->model.local_rotation[b][2] == 0.f && cfg->model.local_rotation[b][3] == 1.f)) sp.lr_identity = 0;
@@ -1741,27 +1745,19 @@ extern "C" int parc_env_create(const ParcEnvConfig *cfg, ParcEnv **out) {
     sp.track_root_h = cfg->track_root_h; sp.tracking = cfg->report_tracking_error; sp.body_pos_from_fk = cfg->body_pos_from_fk;
     sp.fall_mask = cfg->contact_body_mask & ((1u << B) - 1u); sp.term_h = cfg->termination_height;
 
-    auto up = [&](void **dst, const void *src, size_t bytes) -> hipError_t {
-        hipError_t r = hipMalloc(dst, bytes);
-        if (r != hipSuccess) return r;
-        return src ? hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) : hipMemset(*dst, 0, bytes);
-    };
-    hipError_t r = hipSuccess;
-    const size_t N = (size_t)e->N;
-    if ((r = up((void **)&e->d_tab, &t, sizeof(t))) != hipSuccess ||
-        (r = up((void **)&e->d_prep, nullptr, sizeof(float4) * 16 * N)) != hipSuccess ||
-        (r = up((void **)&e->d_ray, cfg->ray_points_host, sizeof(float) * 2 * R)) != hipSuccess ||
-        (r = up((void **)&e->d_env_off, cfg->env_offsets_host, sizeof(float) * 3 * N)) != hipSuccess ||
-        (r = up((void **)&e->d_ema, nullptr, ((N + 1023) / 1024) * 1024)) != hipSuccess ||
-        (r = up((void **)&e->d_done_list, nullptr, sizeof(int) * N)) != hipSuccess ||
-        (r = up((void **)&e->d_done_key, nullptr, sizeof(int) * N)) != hipSuccess ||
-        (r = up((void **)&e->d_chunk_count, nullptr, sizeof(int) * 1024)) != hipSuccess ||
-        (r = up((void **)&e->d_reset_count, nullptr, 2 * sizeof(int))) != hipSuccess ||
-        (r = up((void **)&e->d_reset_calls, nullptr, sizeof(unsigned long long))) != hipSuccess ||
-        (r = up((void **)&e->d_scratch_jr, nullptr, sizeof(float) * 4 * J * N)) != hipSuccess) {
-        free_dev(e); delete e;
-        return fail(PARC_ERR_HIP, std::string("device allocation failed: ") + hipGetErrorString(r));
-    }
+    DeviceArena &mem = e->mem;
+    const long long N = e->N;
+    PARC_TRY(mem.alloc(e->d_tab, 1, &t));
+    PARC_TRY(mem.alloc_fill(e->d_prep, 16 * N));
+    PARC_TRY(mem.alloc(e->d_ray, 2 * R, cfg->ray_points_host));
+    PARC_TRY(mem.alloc(e->d_env_off, 3 * N, cfg->env_offsets_host));
+    PARC_TRY(mem.alloc_fill(e->d_ema, (N + 1023) / 1024 * 1024));
+    PARC_TRY(mem.alloc_fill(e->d_done_list, N));
+    PARC_TRY(mem.alloc_fill(e->d_done_key, N));
+    PARC_TRY(mem.alloc_fill(e->d_chunk_count, 1024));
+    PARC_TRY(mem.alloc_fill(e->d_reset_count, 2));
+    PARC_TRY(mem.alloc_fill(e->d_reset_calls, 1));
+    PARC_TRY(mem.alloc_fill(e->d_scratch_jr, 4 * J * N));
     { // render geometry: the MJCF collision geoms the scene builder puts into ParcDynamicsParams whether or not the dynamics run
         RenderGeoms rg;
         memset(&rg, 0, sizeof(rg));
@@ -1772,11 +1768,7 @@ extern "C" int parc_env_create(const ParcEnvConfig *cfg, ParcEnv **out) {
             rg.body[n] = dp.geom_body[g]; rg.type[n] = dp.geom_type[g];
             for (int c = 0; c < 3; ++c) { rg.p0[n][c] = dp.geom_pos[g][c]; rg.p1[n][c] = dp.geom_pos2[g][c]; rg.size[n][c] = dp.geom_size[g][c]; }
         }
-        r = up((void **)&e->d_rgeom, &rg, sizeof(rg));
-    }
-    if (r != hipSuccess) {
-        free_dev(e); delete e;
-        return fail(PARC_ERR_HIP, std::string("device allocation failed: ") + hipGetErrorString(r));
+        PARC_TRY(mem.alloc(e->d_rgeom, 1, &rg));
     }
     {
         hipDeviceProp_t prop;
@@ -1787,21 +1779,16 @@ extern "C" int parc_env_create(const ParcEnvConfig *cfg, ParcEnv **out) {
     if (cfg->enable_dynamics) {
         memset(&e->h_dyn, 0, sizeof(e->h_dyn));
         parcdyn::fill_dyn_model(e->h_dyn, cfg->model, cfg->dynamics, cfg->action_low, cfg->action_high);
-        if (e->h_dyn.truncated > 0 || cfg->dynamics.num_geoms > PARC_MAX_GEOMS) { // a silently shortened collision set would depend on the geom order
-            const int t = e->h_dyn.truncated;
-            free_dev(e); delete e;
-            return fail(PARC_ERR_INVALID, "dynamics: " + std::to_string(t) + " collision point(s) / segment(s) / geom(s) do not fit the model tables (DYN_MAXC " +
+        if (e->h_dyn.truncated > 0 || cfg->dynamics.num_geoms > PARC_MAX_GEOMS) // a silently shortened collision set would depend on the geom order
+            return fail(PARC_ERR_INVALID, "dynamics: " + std::to_string(e->h_dyn.truncated) + " collision point(s) / segment(s) / geom(s) do not fit the model tables (DYN_MAXC " +
                         std::to_string(DYN_MAXC) + ", DYN_MAXS " + std::to_string(DYN_MAXS) + ", " + std::to_string(PARC_MAX_GEOMS) + " geoms)");
-        }
         { // control mode (ig_char_env.py:21-26, 95)
             const int cm = cfg->dynamics.control_mode;
             bool all_1d = true;
             for (int b = 1; b < cfg->model.num_bodies; ++b) all_1d = all_1d && cfg->model.joint_type[b] != parcdyn::DJ_SPHERICAL;
-            if (cm < PARC_CTRL_PD || cm > PARC_CTRL_PD_1D || (cm == PARC_CTRL_PD_1D && !all_1d)) {
-                free_dev(e); delete e;
+            if (cm < PARC_CTRL_PD || cm > PARC_CTRL_PD_1D || (cm == PARC_CTRL_PD_1D && !all_1d))
                 return fail(PARC_ERR_INVALID, cm == PARC_CTRL_PD_1D ? "control_mode pd_1d only supports characters whose joints all have one dof (the reference asserts it, ig_char_env.py:246-250)"
                                                                      : "unknown control_mode " + std::to_string(cm));
-            }
         }
         // developer switches for ablation measurements (ParcEnvConfig::dev_options; the product never sets them)
         {
@@ -1826,10 +1813,7 @@ extern "C" int parc_env_create(const ParcEnvConfig *cfg, ParcEnv **out) {
                 e->h_dyn.spec_tv = 1.5f * (float)(e->h_dyn.man_period - 1) * e->h_dyn.dt;
             }
         }
-        if ((r = up((void **)&e->d_dyn, &e->h_dyn, sizeof(e->h_dyn))) != hipSuccess) {
-            free_dev(e); delete e;
-            return fail(PARC_ERR_HIP, std::string("device allocation failed: ") + hipGetErrorString(r));
-        }
+        PARC_TRY(mem.alloc(e->d_dyn, 1, &e->h_dyn));
         // Kernel choice by tree shape: wave-per-limb (a trunk chain + <= 4 limb chains of <= 3 bodies, the humanoid),
         // else chain-parallel (<= 8 chains of <= 4 bodies), else thread-per-env.  PARC_DYN_KERNEL=coop|thread forces
         // one of the more general kernels (they are kept as fallbacks for other trees and as cross-checks).
@@ -1840,24 +1824,16 @@ extern "C" int parc_env_create(const ParcEnvConfig *cfg, ParcEnv **out) {
         e->use_wave = wave_ok && want != "coop" && want != "thread";
         e->use_coop = coop_ok && !e->use_wave && want != "thread";
         if (e->use_wave) {
-            r = up((void **)&e->d_wave, &e->h_wave, sizeof(e->h_wave));
-            if (r == hipSuccess && dev_opt(cfg, "no_residual").empty()) { // (developer switch: the precision test measures the drift without it)
-                r = hipMalloc((void **)&e->d_root_shadow, sizeof(float) * 6 * N);
-                if (r == hipSuccess) r = hipMemset(e->d_root_shadow, 0xff, sizeof(float) * 6 * N); // NaN: matches no buffer value
-            }
-            if (r == hipSuccess) { // overflow area of the contact-plane lists (never read before it is written)
-                const int epb = wave_envs_per_block(N, e->num_cus);
-                r = hipMalloc((void **)&e->d_man_ovf, sizeof(float) * (size_t)((N + epb - 1) / epb) * WV_MAXLIMB * WV_MAN_OVF * 8 * 64);
-            }
-            if (r == hipSuccess)
-                r = hipFuncSetAttribute(cfg->dynamics.control_mode == PARC_CTRL_PD ? (const void *)parcdyn::k_dynamics_wave : (const void *)parcdyn::k_dynamics_wave_ff,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, parcdyn::wv_lds_floats() * (int)sizeof(float));
+            PARC_TRY(mem.alloc(e->d_wave, 1, &e->h_wave));
+            if (dev_opt(cfg, "no_residual").empty()) // (developer switch: the precision test measures the drift without it)
+                PARC_TRY(mem.alloc_fill(e->d_root_shadow, 6 * N, 0xff)); // NaN: matches no buffer value
+            const int epb = wave_envs_per_block((int)N, e->num_cus);
+            // overflow area of the contact-plane lists (never read before it is written)
+            PARC_TRY(mem.alloc(e->d_man_ovf, (N + epb - 1) / epb * WV_MAXLIMB * WV_MAN_OVF * 8 * 64));
+            HIPCHK(hipFuncSetAttribute(cfg->dynamics.control_mode == PARC_CTRL_PD ? (const void *)parcdyn::k_dynamics_wave : (const void *)parcdyn::k_dynamics_wave_ff,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, parcdyn::wv_lds_floats() * (int)sizeof(float)));
         } else if (e->use_coop) {
-            r = up((void **)&e->d_coop, &e->h_coop, sizeof(e->h_coop));
-        }
-        if (r != hipSuccess) {
-            free_dev(e); delete e;
-            return fail(PARC_ERR_HIP, std::string("dynamics kernel setup failed: ") + hipGetErrorString(r));
+            PARC_TRY(mem.alloc(e->d_coop, 1, &e->h_coop));
         }
     }
     e->force_ema_leader = !dev_opt(cfg, "ema_leader").empty();
@@ -1870,91 +1846,62 @@ extern "C" int parc_env_create(const ParcEnvConfig *cfg, ParcEnv **out) {
     sp.tables = e->d_tab; sp.ray_points = e->d_ray; sp.env_offsets = e->d_env_off;
     sp.ema_code = e->d_ema; sp.prep = e->d_prep;
 #ifdef PARC_STAMPS
-    if (hipMalloc((void **)&sp.stamp_out, sizeof(unsigned) * 8 * N) != hipSuccess) sp.stamp_out = nullptr;
+    PARC_TRY(mem.alloc(sp.stamp_out, 8 * N));
 #endif
     e->nchunks = (e->N + 1023) / 1024;
-    if (e->nchunks > 1024) { free_dev(e); delete e; return fail(PARC_ERR_INVALID, "num_envs must be <= 1048576 per handle"); }
 
-    *out = e;
+    *out = e.release();
     return PARC_OK;
 }
 
-extern "C" void parc_env_destroy(ParcEnv *e) {
-    if (!e) return;
-    (void)hipSetDevice(e->cfg.device);
-    free_dev(e);
-    delete e;
-}
+extern "C" void parc_env_destroy(ParcEnv *e) { delete e; }
 
 extern "C" int parc_env_obs_dim(const ParcEnv *e) { return e ? e->obs_dim : PARC_ERR_INVALID; }
 
+// The two loads build the new state in locals and swap it into the handle as their last step: a call that returns non-zero has
+// changed nothing (the local arenas release what it allocated), a call that succeeds leaves the old state to the local arena.
 extern "C" int parc_env_load_motions(ParcEnv *e, const ParcMotionClips *c) {
     if (!e || !c || c->num_motions < 1) return fail(PARC_ERR_INVALID, "bad motion clips");
-    HIPCHK(hipSetDevice(e->cfg.device));
     const int M = c->num_motions, B = e->B, J = e->J;
-    int64_t F = 0;
-    e->h_meta.assign(M, MotionMeta());
-    e->h_weights.assign(M, 0.f);
-    float wsum = 0.f;
-    for (int m = 0; m < M; ++m) {
-        if (c->num_frames_host[m] < 2) return fail(PARC_ERR_INVALID, "every clip needs at least 2 frames");
-        if (c->fps_host[m] <= 0) return fail(PARC_ERR_INVALID, "fps must be positive");
-        if (c->weights_host[m] < 0) return fail(PARC_ERR_INVALID, "motion weights must be >= 0");
-        e->h_weights[m] = (float)c->weights_host[m];
-        wsum = wsum + e->h_weights[m];
-    }
+    std::vector<MotionMeta> meta;
+    std::vector<float> weights;
     std::vector<int> frame_motion;
-    for (int m = 0; m < M; ++m) {
-        MotionMeta &mm = e->h_meta[m];
-        const int n = c->num_frames_host[m];
-        mm.start = (int)F; mm.nframes = n; mm.loop = c->loop_modes_host[m]; mm.fps = (float)c->fps_host[m];
-        mm.length = (float)(1.0 / (double)c->fps_host[m] * (double)(n - 1)); // motion_lib.py:305
-        const float *rp = c->root_pos_host + 3 * F;
-        mm.dx = rp[3 * (n - 1)] - rp[0]; mm.dy = rp[3 * (n - 1) + 1] - rp[1]; mm.dz = 0.f; // :307-308
-        e->h_weights[m] = e->h_weights[m] / wsum; // :372
-        for (int f = 0; f < n; ++f) frame_motion.push_back(m);
-        F += n;
-    }
-    if (F > (int64_t)1 << 30) return fail(PARC_ERR_INVALID, "too many frames");
-    void *olds[] = {e->d_records, e->d_meta, e->d_weights, e->d_fail, e->d_cdf, e->d_motion_done};
-    for (void *p : olds) if (p) (void)hipFree(p);
-    e->d_records = nullptr; e->d_meta = nullptr; e->d_weights = nullptr; e->d_fail = nullptr; e->d_cdf = nullptr; e->d_motion_done = nullptr;
-    float *d_rp = nullptr, *d_rr = nullptr, *d_jr = nullptr, *d_ct = nullptr;
-    int *d_fm = nullptr;
-    HIPCHK(hipMalloc((void **)&e->d_records, sizeof(float4) * REC_F4 * F));
-    HIPCHK(hipMalloc((void **)&e->d_meta, sizeof(MotionMeta) * M));
-    HIPCHK(hipMalloc((void **)&e->d_weights, sizeof(float) * M));
-    HIPCHK(hipMalloc((void **)&e->d_fail, sizeof(float) * M));
-    HIPCHK(hipMalloc((void **)&e->d_cdf, sizeof(float) * M));
-    HIPCHK(hipMalloc((void **)&e->d_motion_done, sizeof(int) * M));
-    HIPCHK(hipMemset(e->d_motion_done, 0x7f, sizeof(int) * M)); // 0x7f7f7f7f: larger than any list index (k_ema_first takes the minimum)
-    HIPCHK(hipMalloc((void **)&d_rp, sizeof(float) * 3 * F));
-    HIPCHK(hipMalloc((void **)&d_rr, sizeof(float) * 4 * F));
-    HIPCHK(hipMalloc((void **)&d_jr, sizeof(float) * 4 * J * F));
-    HIPCHK(hipMalloc((void **)&d_fm, sizeof(int) * F));
-    HIPCHK(hipMemcpy(e->d_meta, e->h_meta.data(), sizeof(MotionMeta) * M, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_weights, e->h_weights.data(), sizeof(float) * M, hipMemcpyHostToDevice));
-    std::vector<float> ones(M, 1.0f); // dm_env.py:87
-    HIPCHK(hipMemcpy(e->d_fail, ones.data(), sizeof(float) * M, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_rp, c->root_pos_host, sizeof(float) * 3 * F, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_rr, c->root_rot_host, sizeof(float) * 4 * F, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_jr, c->joint_rot_host, sizeof(float) * 4 * J * F, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_fm, frame_motion.data(), sizeof(int) * F, hipMemcpyHostToDevice));
-    if (c->contacts_host) {
-        HIPCHK(hipMalloc((void **)&d_ct, sizeof(float) * B * F));
-        HIPCHK(hipMemcpy(d_ct, c->contacts_host, sizeof(float) * B * F, hipMemcpyHostToDevice));
-    }
+    if (const char *msg = parc_motion_table(M, c->num_frames_host, c->fps_host, c->loop_modes_host, c->weights_host, c->root_pos_host, meta, weights, frame_motion))
+        return fail(PARC_ERR_INVALID, msg);
+    const long long F = (long long)frame_motion.size();
+    HIPCHK(hipSetDevice(e->cfg.device));
+    DeviceArena set, tmp; // the new motion set / the inputs of k_motion_prep
+    float4 *d_records;
+    MotionMeta *d_meta;
+    float *d_weights, *d_fail, *d_cdf;
+    int *d_motion_done;
+    const std::vector<float> ones((size_t)M, 1.0f); // dm_env.py:87
+    PARC_TRY(set.alloc(d_records, REC_F4 * F));
+    PARC_TRY(set.alloc(d_meta, M, meta.data()));
+    PARC_TRY(set.alloc(d_weights, M, weights.data()));
+    PARC_TRY(set.alloc(d_fail, M, ones.data()));
+    PARC_TRY(set.alloc(d_cdf, M));
+    PARC_TRY(set.alloc_fill(d_motion_done, M, 0x7f)); // 0x7f7f7f7f: larger than any list index (k_ema_first takes the minimum)
     PrepParams pp;
-    pp.F = (int)F; pp.B = B; pp.J = J; pp.D = e->D; pp.root_pos = d_rp; pp.root_rot = d_rr; pp.joint_rot = d_jr; pp.contacts = d_ct;
-    pp.frame_motion = d_fm; pp.meta = e->d_meta; pp.tables = e->d_tab; pp.records = e->d_records;
+    pp.F = (int)F; pp.B = B; pp.J = J; pp.D = e->D; pp.contacts = nullptr;
+    pp.meta = d_meta; pp.tables = e->d_tab; pp.records = d_records;
+    PARC_TRY(tmp.alloc(pp.root_pos, 3 * F, c->root_pos_host));
+    PARC_TRY(tmp.alloc(pp.root_rot, 4 * F, c->root_rot_host));
+    PARC_TRY(tmp.alloc(pp.joint_rot, 4 * J * F, c->joint_rot_host));
+    PARC_TRY(tmp.alloc(pp.frame_motion, F, frame_motion.data()));
+    if (c->contacts_host) PARC_TRY(tmp.alloc(pp.contacts, B * F, c->contacts_host));
     hipLaunchKernelGGL(k_motion_prep, dim3((unsigned)((F + 127) / 128)), dim3(128), 0, 0, pp);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
-    (void)hipFree(d_rp); (void)hipFree(d_rr); (void)hipFree(d_jr); (void)hipFree(d_fm);
-    if (d_ct) (void)hipFree(d_ct);
+
+    e->motions.swap(set);
+    e->h_meta.swap(meta); e->h_weights.swap(weights);
+    e->d_records = d_records; e->d_meta = d_meta; e->d_weights = d_weights; e->d_fail = d_fail; e->d_cdf = d_cdf; e->d_motion_done = d_motion_done;
+    if (M != e->M) e->have_terrain = false; // motion_offsets has one row per motion of the old set: parc_env_load_terrain again
     e->M = M; e->F = F; e->have_motions = true;
-    e->sp.M = M; e->sp.records = e->d_records; e->sp.meta = e->d_meta;
-    return sync_params(e);
+    e->sp.M = M; e->sp.records = d_records; e->sp.meta = d_meta;
+    e->graph_dirty = true;
+    return PARC_OK;
 }
 
 extern "C" int parc_env_load_terrain(ParcEnv *e, const float *hf, int32_t X, int32_t Y, float min_x, float min_y, float dx, float dy,
@@ -1962,8 +1909,7 @@ extern "C" int parc_env_load_terrain(ParcEnv *e, const float *hf, int32_t X, int
     if (!e || !hf || !motion_offsets || X < 1 || Y < 1 || T < 1 || !(dx > 0.f) || !(dy > 0.f)) return fail(PARC_ERR_INVALID, "bad terrain");
     if (!e->have_motions || M != e->M) return fail(PARC_ERR_STATE, "load_motions first; motion_offsets must have one row per motion");
     HIPCHK(hipSetDevice(e->cfg.device));
-    // terrain tile radius: farthest ray sample in cells, +1 for the two independent roundings.  Radius, index multiplier and the lane table
-    // that holds the tile cells (parc_lanetab.hpp) are formed before anything of the handle changes: a failure leaves it as it was
+    // terrain tile radius: farthest ray sample in cells, +1 for the two independent roundings
     std::vector<float> ray(2 * (size_t)e->R);
     HIPCHK(hipMemcpy(ray.data(), e->d_ray, sizeof(float) * 2 * e->R, hipMemcpyDeviceToHost));
     float rmax = 0.f;
@@ -1977,34 +1923,34 @@ extern "C" int parc_env_load_terrain(ParcEnv *e, const float *hf, int32_t X, int
         for (unsigned idx = 0; idx < TW * TW; ++idx)
             if (((idx * tile_mul) >> 16) != idx / TW) return fail(PARC_ERR_INVALID, "internal: tile index multiplier");
     }
-    ParcLaneEntry lanes[64];
+    ParcLaneEntry lanes[64]; // the lane table that holds the tile cells (parc_lanetab.hpp)
     if (!parc_lanetab_fill(lanes, e->B, e->S, e->D, e->R, tr, e->row_mul, tile_mul)) return fail(PARC_ERR_INVALID, "internal: lane table");
-    if (e->d_hf) (void)hipFree(e->d_hf);
-    if (e->d_motion_off) (void)hipFree(e->d_motion_off);
-    e->d_hf = nullptr; e->d_motion_off = nullptr;
-    HIPCHK(hipMalloc((void **)&e->d_hf, sizeof(float) * (size_t)X * Y));
-    HIPCHK(hipMalloc((void **)&e->d_motion_off, sizeof(float) * 2 * (size_t)M * T));
-    HIPCHK(hipMemcpy(e->d_hf, hf, sizeof(float) * (size_t)X * Y, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_motion_off, motion_offsets, sizeof(float) * 2 * (size_t)M * T, hipMemcpyHostToDevice));
+    const size_t cells = (size_t)X * Y;
+    float hf_max = hf[0], hf_min = hf[0];
+    for (size_t q = 1; q < cells; ++q) { hf_max = fmaxf(hf_max, hf[q]); hf_min = fminf(hf_min, hf[q]); }
+    DeviceArena ter;
+    float *d_hf, *d_motion_off;
+    PARC_TRY(ter.alloc(d_hf, (long long)cells, hf));
+    PARC_TRY(ter.alloc(d_motion_off, 2LL * M * T, motion_offsets));
+    HIPCHK(hipMemcpy(e->d_tab->lane, lanes, sizeof(lanes), hipMemcpyHostToDevice)); // the last step that can fail
+
+    e->terrain.swap(ter);
+    e->d_hf = d_hf; e->d_motion_off = d_motion_off;
     StepParams &sp = e->sp;
-    sp.hf = e->d_hf; sp.X = X; sp.Y = Y; sp.min_x = min_x; sp.min_y = min_y; sp.dx = dx; sp.dy = dy; sp.T = T;
+    sp.hf = d_hf; sp.X = X; sp.Y = Y; sp.min_x = min_x; sp.min_y = min_y; sp.dx = dx; sp.dy = dy; sp.T = T;
     sp.rdx = (float)(1.0L / (long double)dx); sp.rdy = (float)(1.0L / (long double)dy);
-    sp.motion_offsets = e->d_motion_off;
+    sp.motion_offsets = d_motion_off;
     e->T = T;
-    e->hf_max = hf[0];
-    for (size_t q = 1; q < (size_t)X * Y; ++q) e->hf_max = fmaxf(e->hf_max, hf[q]);
-    e->hf_min = hf[0];
-    for (size_t q = 1; q < (size_t)X * Y; ++q) e->hf_min = fminf(e->hf_min, hf[q]);
+    e->hf_max = hf_max; e->hf_min = hf_min;
     sp.tile_r = tr;
     e->tile_mul = tile_mul;
     memcpy(e->h_tab.lane, lanes, sizeof(lanes));
-    HIPCHK(hipMemcpy(e->d_tab->lane, e->h_tab.lane, sizeof(e->h_tab.lane), hipMemcpyHostToDevice));
     const int stage_pad = (sp.off_tarc + 3) & ~3;
     e->lds_bytes = sizeof(float) * (size_t)stage_pad + (e->cfg.report_tracking_error ? 2 * 16 * sizeof(float4) : 0); // per wave of k_env_post
-    e->sp.lds_wave_floats = (int)(e->lds_bytes / sizeof(float));
+    sp.lds_wave_floats = (int)(e->lds_bytes / sizeof(float));
     e->have_terrain = true;
     e->graph_dirty = true;
-    return sync_params(e);
+    return PARC_OK;
 }
 
 extern "C" int parc_env_bind_buffers(ParcEnv *e, const ParcEnvBuffers *b) {
@@ -2020,7 +1966,7 @@ extern "C" int parc_env_bind_buffers(ParcEnv *e, const ParcEnvBuffers *b) {
     e->sp.buf = *b;
     e->bound = true;
     e->graph_dirty = true;
-    return sync_params(e);
+    return PARC_OK;
 }
 
 static int check_ready(ParcEnv *e) {
@@ -2149,7 +2095,8 @@ extern "C" int parc_env_set_episode_length(ParcEnv *e, float seconds) {
     if (!e) return fail(PARC_ERR_INVALID, "null env");
     if (!(seconds > 0.f)) return fail(PARC_ERR_INVALID, "episode length must be positive");
     e->sp.episode_length = seconds;
-    return sync_params(e);
+    e->graph_dirty = true;
+    return PARC_OK;
 }
 
 __global__ void k_td_lambda(const float *__restrict__ r, const float *__restrict__ nv, const int *__restrict__ done, float g, float lam0, int T, int N,
@@ -2524,7 +2471,8 @@ extern "C" int parc_env_get_motion_info(ParcEnv *e, float *lengths, float *weigh
 extern "C" int parc_env_set_never_done(ParcEnv *e, int32_t never_done) {
     if (!e) return fail(PARC_ERR_INVALID, "null env");
     e->sp.never_done = never_done != 0;
-    return sync_params(e);
+    e->graph_dirty = true;
+    return PARC_OK;
 }
 
 extern "C" int parc_env_set_rand_reset(ParcEnv *e, int32_t rand_reset, int32_t demo_mode, float scale) {
@@ -2793,9 +2741,11 @@ extern "C" int parc_env_render_scene(ParcEnv *e, const ParcRenderParams *p, int3
     if (!rgba_dev && !depth_dev && !id_dev && !env_map_dev) return PARC_OK;
     HIPCHK(hipSetDevice(e->cfg.device));
     if (e->scene_cap < n) {
-        if (e->d_scene) { HIPCHK(hipFree(e->d_scene)); e->d_scene = nullptr; e->scene_cap = 0; }
-        HIPCHK(hipMalloc((void **)&e->d_scene, scene_ws_bytes(e->B, n)));
-        e->scene_cap = n;
+        if (e->d_scene) (void)hipFree(e->d_scene);
+        e->d_scene = nullptr; e->scene_cap = 0; // a failed allocation leaves no workspace, not a stale one
+        void *ws = nullptr;
+        HIPCHK(hipMalloc(&ws, scene_ws_bytes(e->B, n)));
+        e->d_scene = (char *)ws; e->scene_cap = n;
     }
     SceneArgs S;
     memset(&S, 0, sizeof(S));
