@@ -465,7 +465,10 @@ typedef struct {
 } ParcMotionOptClips;
 int parc_mopt_create(const ParcMotionOptParams *p, ParcMotionOpt **out);
 void parc_mopt_destroy(ParcMotionOpt *h);
-/* Uploads the clips and sets the iterate to the source (root exp map = quat_to_exp_map, dofs = rot_to_dof); resets Adam. */
+/* Uploads the clips and sets the iterate to the source (root exp map = quat_to_exp_map, dofs = rot_to_dof); resets Adam.
+ * The batch is validated first: PARC_ERR_INVALID leaves the batch loaded before in place and usable.  A valid batch replaces it: the
+ * old one is released before the new one is allocated (the handle never holds two), so a failed allocation or upload (PARC_ERR_HIP)
+ * leaves the handle without a batch, and every call that needs one returns PARC_ERR_STATE until a parc_mopt_set_clips succeeds. */
 int parc_mopt_set_clips(ParcMotionOpt *h, const ParcMotionOptClips *c);
 /* Replaces the constraint points (same count as set_clips gave), e.g. after parc_mopt_build_constraints. */
 int parc_mopt_set_constraint_points(ParcMotionOpt *h, const float *cons_point_host);
@@ -511,7 +514,9 @@ typedef struct {
 } ParcMotionTerrainParams;
 int parc_mterr_create(const ParcMotionTerrainParams *p, ParcMotionTerrain **out);
 void parc_mterr_destroy(ParcMotionTerrain *h);
-/* Uploads the clips (num_clips >= 1, every clip >= 1 frame, dims >= 1 with at most 2^31 - 1 cells, dx > 0). */
+/* Uploads the clips (num_clips >= 1, every clip >= 1 frame, dims >= 1 with at most 2^31 - 1 cells, dx > 0).  As parc_mopt_set_clips:
+ * PARC_ERR_INVALID leaves the batch loaded before in place and usable, with its last run's results; a failure after the validation
+ * leaves no batch (PARC_ERR_STATE until a parc_mterr_set_clips succeeds). */
 int parc_mterr_set_clips(ParcMotionTerrain *h, const ParcMotionOptClips *c);
 /* One analysis of the uploaded clips.  Outputs (NULL = not copied): clip_out [num_clips][PARC_MTERR_CLIP_OUTPUTS]; mask_counts [F], the
  * number of distinct cells of each frame; hf_maxmin [cells][2] (max, min), cells in hf_host's order; total_inds = sum of mask_counts.
@@ -609,7 +614,8 @@ typedef struct {                             /* caller-owned device buffers; NUL
 int parc_msamp_create(const ParcMotionSamplerParams *p, ParcMotionSampler **out);
 void parc_msamp_destroy(ParcMotionSampler *h);
 /* Uploads the library.  PARC_ERR_INVALID names the clip (by index) that has no full window (num_frames - T <= 0) or whose terrain has
- * more than PARC_MSAMP_MAX_TERRAIN_CELLS cells. */
+ * more than PARC_MSAMP_MAX_TERRAIN_CELLS cells.  As parc_mopt_set_clips: PARC_ERR_INVALID leaves the library loaded before in place and
+ * usable; a failure after the validation leaves no library, never part of one (PARC_ERR_STATE until a parc_msamp_set_clips succeeds). */
 int parc_msamp_set_clips(ParcMotionSampler *h, const ParcMotionOptClips *c, const ParcMotionSamplerClipInfo *info);
 /* The deterministic path: everything is enqueued on `stream`, no host sync. */
 int parc_msamp_sample_with(ParcMotionSampler *h, const ParcMotionSamplerPlan *plan, const ParcMotionSamplerOutputs *out, void *stream);
@@ -682,7 +688,9 @@ typedef struct {                             /* host arrays of Q entries; NULL =
 int parc_pathplan_create(const ParcPathPlanParams *p, ParcPathPlanner **out);
 void parc_pathplan_destroy(ParcPathPlanner *h);
 /* Plans Q queries: hf_host [Q][dim_x][dim_y]; start_host / goal_host [Q][2] cells, or both NULL to draw them from (seed, query index).
- * Synchronous (the outputs are host arrays). */
+ * Synchronous (the outputs are host arrays).  The device buffers are kept from run to run and replaced when Q exceeds what they hold (the
+ * old ones released first).  PARC_ERR_INVALID leaves the last batch readable by parc_pathplan_get_graph; a later failure leaves none
+ * (PARC_ERR_STATE there until a run succeeds), and a failed allocation leaves no buffers either: the next run allocates them anew. */
 int parc_pathplan_run(ParcPathPlanner *h, int32_t Q, const float *hf_host, const int32_t *start_host, const int32_t *goal_host, uint64_t seed,
                       uint64_t first_query, const ParcPathPlanOutputs *out);
 /* The navigation graph of queries [q0, q0 + n) of the last run, from the predicates the search uses: nbr [n][cells] bit d = the edge to

@@ -52,13 +52,8 @@ static int model_points(const char *pre, Model &M, int num_points, const float *
     return PARC_OK;
 }
 
-// the handle's copy of the model on `device` (which becomes the current device)
-template <typename Model> static hipError_t model_upload(int device, const Model &M, Model **d_model) {
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipMalloc((void **)d_model, sizeof(M));
-    if (e == hipSuccess) e = hipMemcpy(*d_model, &M, sizeof(M), hipMemcpyHostToDevice);
-    return e;
-}
+// the handle's copy of the model on the current device, allocated from `mem`
+template <typename Model> static int model_upload(DeviceArena &mem, const Model &M, Model *&d_model) { return mem.alloc(d_model, 1, &M); }
 
 // ---- the clip batch --------------------------------------------------------------------------------------------------------------
 struct ClipBatch {                        // what clip_batch_clips derives from a valid batch

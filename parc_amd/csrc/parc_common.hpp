@@ -1,5 +1,5 @@
 // parc_common.hpp — what the env unit (parc_env.hip) and the tools unit (parc_tools.hip) both use, and nothing else.
-//   host:   the thread's last error message (one instance for the whole library), fail / HIPCHK / PARC_TRY, blocks, the device arena
+//   host:   the thread's last error message (one instance for the whole library), fail / HIPCHK / PARC_TRY, blocks, the device arena, the event set
 //   device: Philox4x32-10 and the frame blend of motion_lib.py (the motion table entry it reads: parc_motion_table.hpp)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -49,6 +49,23 @@ struct DeviceArena {                      // device buffers with one lifetime: f
     void release() {
         for (void *p : ptrs) (void)hipFree(p);
         ptrs.clear();
+    }
+};
+
+template <int N> struct DeviceEvents {    // N events with one lifetime, indexed like the array they are: ev[i]
+    hipEvent_t ev[N] = {};
+    DeviceEvents() = default;
+    DeviceEvents(const DeviceEvents &) = delete;
+    DeviceEvents &operator=(const DeviceEvents &) = delete;
+    ~DeviceEvents() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    int create() {                        // on the current device, once
+        for (hipEvent_t &e : ev) HIPCHK(hipEventCreate(&e));
+        return PARC_OK;
+    }
+    hipEvent_t operator[](int i) const { return ev[i]; }
+    int elapsed(float &ms, int from, int to) const {   // ms between two recorded events
+        HIPCHK(hipEventElapsedTime(&ms, ev[from], ev[to]));
+        return PARC_OK;
     }
 };
 

@@ -1586,6 +1586,7 @@ struct ParcEnv {
     DeviceArena mem;                  // create .. destroy: tables, prep records, done lists, dynamics tables, root shadow, manifold overflow, render geoms
     DeviceArena motions;              // parc_env_load_motions: d_records, d_meta, d_weights, d_fail, d_cdf, d_motion_done
     DeviceArena terrain;              // parc_env_load_terrain: d_hf, d_motion_off
+    DeviceArena scene;                // d_scene alone: released and allocated anew when it must grow
     StepParams sp;
     float4 *d_prep = nullptr;
     std::string dev_options_s, describe_s; // the dev_options this handle was created with (owned copy) / parc_env_describe
@@ -1602,8 +1603,8 @@ struct ParcEnv {
     bool use_wave = false, wave_rejected = false;
     DevTables h_tab;
     DevTables *d_tab = nullptr;
-    unsigned row_mul = 0;  // joint item j of the row phase: j / (B - 1) == (j * row_mul) >> 16 (parc_rowmap.hpp, checked at create)
-    unsigned tile_mul = 0; // idx / (2 tile_r + 1) == (idx * tile_mul) >> 16 for every tile cell (checked when the terrain is loaded)
+    unsigned row_mul = 0;  // j / (B - 1) == (j * row_mul) >> 16 for every joint item j (parc_rowmap.hpp, checked at create): host only, what
+                           // both fills of the lane table (create, parc_env_load_terrain) form the row items with
     float *d_ray = nullptr, *d_env_off = nullptr, *d_hf = nullptr, *d_motion_off = nullptr;
     float4 *d_records = nullptr;
     MotionMeta *d_meta = nullptr;
@@ -1618,7 +1619,7 @@ struct ParcEnv {
     RenderGeoms *d_rgeom = nullptr;                // parc_env_render: the collision geoms, uploaded at creation
     float hf_max = 0.f;                            // highest column top (parc_env_load_terrain), bounds the renderer's terrain traversal
     float hf_min = 0.f;                            // lowest column top: the floor of the scene render's shadow-caster cull
-    char *d_scene = nullptr;                       // parc_env_render_scene workspace, allocated on the first call (scene_ws_bytes), owned here
+    char *d_scene = nullptr;                       // parc_env_render_scene workspace, grown on demand (scene_ws_bytes), a view into `scene`
     int scene_cap = 0;                             // envs the workspace holds
     unsigned long long *d_reset_calls = nullptr;   // device counter of sampling resets (Philox call index)
     const float *action_bound = nullptr;           // parc_env_bind_action (caller-owned)
@@ -1630,7 +1631,7 @@ struct ParcEnv {
     int num_cus = 256;
     size_t lds_bytes = 0;
     float last_dyn_ms = 0.f;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    DeviceEvents<4> ev;
     float *rec_frames = nullptr, *rec_obs = nullptr;   // recorder ring buffers (caller-owned)
     int rec_cap = 0, rec_ref = 0;
     int *rec_count = nullptr, *rec_nwriting = nullptr;
@@ -1644,10 +1645,8 @@ struct ParcEnv {
     ParcEnv &operator=(const ParcEnv &) = delete;
     ~ParcEnv() {
         (void)hipSetDevice(cfg.device);
-        mem.release(); motions.release(); terrain.release();
-        if (d_scene) (void)hipFree(d_scene);
+        mem.release(); motions.release(); terrain.release(); scene.release();
         if (h_health) (void)hipHostFree(h_health);
-        for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
         for (hipEvent_t x : tev) if (x) (void)hipEventDestroy(x);
         if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
     }
@@ -1842,7 +1841,7 @@ extern "C" int parc_env_create(const ParcEnvConfig *cfg, ParcEnv **out) {
         e->h_health[0] = 0u; e->h_health[1] = 0u;
         if (hipHostGetDevicePointer((void **)&e->d_health, e->h_health, 0) != hipSuccess) e->d_health = nullptr;
     }
-    for (auto &ev : e->ev) (void)hipEventCreate(&ev);
+    PARC_TRY(e->ev.create());
     sp.tables = e->d_tab; sp.ray_points = e->d_ray; sp.env_offsets = e->d_env_off;
     sp.ema_code = e->d_ema; sp.prep = e->d_prep;
 #ifdef PARC_STAMPS
@@ -1916,7 +1915,7 @@ extern "C" int parc_env_load_terrain(ParcEnv *e, const float *hf, int32_t X, int
     for (int r = 0; r < e->R; ++r) rmax = fmaxf(rmax, sqrtf(ray[2 * r] * ray[2 * r] + ray[2 * r + 1] * ray[2 * r + 1]));
     int tr = (int)ceilf(rmax / fminf(dx, dy) + 0.01f); // max |round(a+d)-round(a)| = ceil(|d|)
     if ((2 * tr + 1) * (2 * tr + 1) > TILE_MAX_CELLS) tr = -1; // fan too wide for the LDS tile: direct gathers
-    unsigned tile_mul = e->tile_mul;
+    unsigned tile_mul = 0; // idx / (2 tr + 1) == (idx * tile_mul) >> 16, which only the fill of the tile cells needs: unused without a tile
     if (tr >= 0) { // magic multiplier for idx / TW, verified for every cell of the tile
         const unsigned TW = 2 * tr + 1;
         tile_mul = (65536u + TW - 1) / TW;
@@ -1943,7 +1942,6 @@ extern "C" int parc_env_load_terrain(ParcEnv *e, const float *hf, int32_t X, int
     e->T = T;
     e->hf_max = hf_max; e->hf_min = hf_min;
     sp.tile_r = tr;
-    e->tile_mul = tile_mul;
     memcpy(e->h_tab.lane, lanes, sizeof(lanes));
     const int stage_pad = (sp.off_tarc + 3) & ~3;
     e->lds_bytes = sizeof(float) * (size_t)stage_pad + (e->cfg.report_tracking_error ? 2 * 16 * sizeof(float4) : 0); // per wave of k_env_post
@@ -2741,11 +2739,10 @@ extern "C" int parc_env_render_scene(ParcEnv *e, const ParcRenderParams *p, int3
     if (!rgba_dev && !depth_dev && !id_dev && !env_map_dev) return PARC_OK;
     HIPCHK(hipSetDevice(e->cfg.device));
     if (e->scene_cap < n) {
-        if (e->d_scene) (void)hipFree(e->d_scene);
+        e->scene.release();
         e->d_scene = nullptr; e->scene_cap = 0; // a failed allocation leaves no workspace, not a stale one
-        void *ws = nullptr;
-        HIPCHK(hipMalloc(&ws, scene_ws_bytes(e->B, n)));
-        e->d_scene = (char *)ws; e->scene_cap = n;
+        PARC_TRY(e->scene.alloc(e->d_scene, (long long)scene_ws_bytes(e->B, n)));
+        e->scene_cap = n;
     }
     SceneArgs S;
     memset(&S, 0, sizeof(S));

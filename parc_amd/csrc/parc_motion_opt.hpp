@@ -17,6 +17,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -560,33 +561,24 @@ __global__ void k_mopt_cons_sgd(Clips K, const int *clip, float *pts, int n, flo
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------------
 struct ParcMotionOpt {
+    struct Batch {                        // what one parc_mopt_set_clips loads; a batch is loaded when the handle holds one
+        DeviceArena mem;
+        mopt::Clips K{};
+        mopt::Work W{};
+        long long F = 0, adam_t = 0, ncons = 0;
+    };
     int device = 0;
     mopt::Model host_model;
+    DeviceArena mem;                      // create .. destroy: d_model
     mopt::Model *d_model = nullptr;
-    mopt::Clips K{};
-    mopt::Work W{};
-    DeviceArena batch;                    // everything of the current batch
-    long long F = 0, adam_t = 0, ncons = 0;
+    std::unique_ptr<Batch> batch;
     float step_size = 1e-3f;
-    hipEvent_t ev[7] = {};
+    DeviceEvents<7> ev;
     float kernel_ms[6] = {};
+    ~ParcMotionOpt() { (void)hipSetDevice(device); }   // the members release the rest
 };
 
-static void mopt_free_batch(ParcMotionOpt *h) {
-    h->batch.release();
-    h->K = mopt::Clips{};
-    h->W = mopt::Work{};
-    h->F = 0;
-}
-
-extern "C" void parc_mopt_destroy(ParcMotionOpt *h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    mopt_free_batch(h);
-    if (h->d_model) (void)hipFree(h->d_model);
-    for (int i = 0; i < 7; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-    delete h;
-}
+extern "C" void parc_mopt_destroy(ParcMotionOpt *h) { delete h; }
 
 extern "C" int parc_mopt_create(const ParcMotionOptParams *p, ParcMotionOpt **out) {
     if (!p || !out) return fail(PARC_ERR_INVALID, "mopt: null argument");
@@ -609,16 +601,17 @@ extern "C" int parc_mopt_create(const ParcMotionOptParams *p, ParcMotionOpt **ou
     for (int t = 0; t < mopt::NT; ++t) M.w[t] = p->weights[t];
     const double dt = 1.0 / 30.0;
     M.max_jerk = (float)((double)p->max_jerk * (dt * dt * dt));
-    ParcMotionOpt *h = new (std::nothrow) ParcMotionOpt();
+    std::unique_ptr<ParcMotionOpt> h(new (std::nothrow) ParcMotionOpt());   // every failure below is a plain return
     if (!h) return fail(PARC_ERR_INVALID, "mopt: out of host memory");
     h->device = p->device; h->host_model = M; h->step_size = p->step_size;
-    hipError_t e = model_upload(p->device, M, &h->d_model);
-    for (int i = 0; i < 7 && e == hipSuccess; ++i) e = hipEventCreate(&h->ev[i]);
-    if (e != hipSuccess) { parc_mopt_destroy(h); return fail(PARC_ERR_HIP, std::string("mopt create: ") + hipGetErrorString(e)); }
-    *out = h;
+    HIPCHK(hipSetDevice(p->device));
+    PARC_TRY(model_upload(h->mem, M, h->d_model));
+    PARC_TRY(h->ev.create());
+    *out = h.release();
     return PARC_OK;
 }
 
+// validate; release the old batch (two would double the peak of F x B workspace); build the new one in a local; install it last
 extern "C" int parc_mopt_set_clips(ParcMotionOpt *h, const ParcMotionOptClips *c) {
     if (!h || !c) return fail(PARC_ERR_INVALID, "mopt: null argument");
     PARC_TRY(clip_batch_arrays("mopt", c));
@@ -634,10 +627,12 @@ extern "C" int parc_mopt_set_clips(ParcMotionOpt *h, const ParcMotionOptClips *c
     for (long long q = 0; q < ncons; ++q)
         if (c->cons_body_host[q] < 0 || c->cons_body_host[q] >= B) return fail(PARC_ERR_INVALID, "mopt: constraint body out of range");
     HIPCHK(hipSetDevice(h->device));
-    mopt_free_batch(h);
-    mopt::Clips &K = h->K;
-    mopt::Work &W = h->W;
-    DeviceArena &mem = h->batch;
+    h->batch.reset();
+    std::unique_ptr<ParcMotionOpt::Batch> nb(new (std::nothrow) ParcMotionOpt::Batch());
+    if (!nb) return fail(PARC_ERR_INVALID, "mopt: out of host memory");
+    mopt::Clips &K = nb->K;
+    mopt::Work &W = nb->W;
+    DeviceArena &mem = nb->mem;
     PARC_TRY(clip_batch_upload(mem, K, c, cb, B));
     PARC_TRY(mem.alloc(K.cons_off, C + 1, c->cons_off_host));
     PARC_TRY(mem.alloc(K.frame_clip, F, cb.frame_clip.data()));
@@ -660,36 +655,39 @@ extern "C" int parc_mopt_set_clips(ParcMotionOpt *h, const ParcMotionOptClips *c
     PARC_TRY(mem.alloc(W.patch, 2 * C));
     PARC_TRY(mem.alloc(W.fterms, F * mopt::NT));
     PARC_TRY(mem.alloc(W.terms, (long long)C * mopt::NT));
-    h->F = F; h->ncons = ncons; h->adam_t = 0;
+    nb->F = F; nb->ncons = ncons;
     hipLaunchKernelGGL(mopt::k_mopt_source, dim3(blocks(F, 64)), dim3(64), 0, 0, h->d_model, K, W);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
+    h->batch = std::move(nb);
     return PARC_OK;
 }
 
 static int mopt_check(ParcMotionOpt *h) {
     if (!h) return fail(PARC_ERR_INVALID, "mopt: null handle");
-    if (h->F == 0) return fail(PARC_ERR_STATE, "mopt: parc_mopt_set_clips first");
+    if (!h->batch) return fail(PARC_ERR_STATE, "mopt: parc_mopt_set_clips first");
     return PARC_OK;
 }
 
 extern "C" int parc_mopt_set_constraint_points(ParcMotionOpt *h, const float *pts) {
     if (int rc = mopt_check(h)) return rc;
-    if (h->ncons && !pts) return fail(PARC_ERR_INVALID, "mopt: null points");
+    const long long ncons = h->batch->ncons;
+    if (ncons && !pts) return fail(PARC_ERR_INVALID, "mopt: null points");
     HIPCHK(hipSetDevice(h->device));
-    if (h->ncons) HIPCHK(hipMemcpy(h->K.cons_point, pts, 3 * (size_t)h->ncons * sizeof(float), hipMemcpyHostToDevice));
+    if (ncons) HIPCHK(hipMemcpy(h->batch->K.cons_point, pts, 3 * (size_t)ncons * sizeof(float), hipMemcpyHostToDevice));
     return PARC_OK;
 }
 
 extern "C" int parc_mopt_set_params(ParcMotionOpt *h, const float *params) {
     if (int rc = mopt_check(h)) return rc;
     if (!params) return fail(PARC_ERR_INVALID, "mopt: null params");
-    const size_t n = (size_t)h->F * h->host_model.NP;
+    ParcMotionOpt::Batch &b = *h->batch;
+    const size_t n = (size_t)b.F * h->host_model.NP;
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemcpy(h->W.params, params, n * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(h->W.m, 0, n * sizeof(float)));
-    HIPCHK(hipMemset(h->W.v, 0, n * sizeof(float)));
-    h->adam_t = 0;
+    HIPCHK(hipMemcpy(b.W.params, params, n * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(b.W.m, 0, n * sizeof(float)));
+    HIPCHK(hipMemset(b.W.v, 0, n * sizeof(float)));
+    b.adam_t = 0;
     return PARC_OK;
 }
 
@@ -697,28 +695,29 @@ extern "C" int parc_mopt_get_params(ParcMotionOpt *h, float *params) {
     if (int rc = mopt_check(h)) return rc;
     if (!params) return fail(PARC_ERR_INVALID, "mopt: null params");
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemcpy(params, h->W.params, (size_t)h->F * h->host_model.NP * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(params, h->batch->W.params, (size_t)h->batch->F * h->host_model.NP * sizeof(float), hipMemcpyDeviceToHost));
     return PARC_OK;
 }
 
 // one loss + gradient evaluation: 5 launches on the null stream; with `timed` events bracket each launch
 static int mopt_eval(ParcMotionOpt *h, bool timed) {
-    const long long F = h->F;
-    const int C = h->K.C;
+    const ParcMotionOpt::Batch &b = *h->batch;
+    const long long F = b.F;
+    const int C = b.K.C;
     if (timed) HIPCHK(hipEventRecord(h->ev[0], 0));
-    hipLaunchKernelGGL(mopt::k_mopt_fk, dim3(blocks(F, 64)), dim3(64), 0, 0, h->d_model, h->K, h->W);
+    hipLaunchKernelGGL(mopt::k_mopt_fk, dim3(blocks(F, 64)), dim3(64), 0, 0, h->d_model, b.K, b.W);
     HIPCHK(hipGetLastError());
     if (timed) HIPCHK(hipEventRecord(h->ev[1], 0));
-    hipLaunchKernelGGL(mopt::k_mopt_patch, dim3(blocks(C, 64)), dim3(64), 0, 0, h->K, h->W);
+    hipLaunchKernelGGL(mopt::k_mopt_patch, dim3(blocks(C, 64)), dim3(64), 0, 0, b.K, b.W);
     HIPCHK(hipGetLastError());
     if (timed) HIPCHK(hipEventRecord(h->ev[2], 0));
-    hipLaunchKernelGGL(mopt::k_mopt_points, dim3((unsigned)F), dim3(mopt::PT_THREADS), 0, 0, h->d_model, h->K, h->W);
+    hipLaunchKernelGGL(mopt::k_mopt_points, dim3((unsigned)F), dim3(mopt::PT_THREADS), 0, 0, h->d_model, b.K, b.W);
     HIPCHK(hipGetLastError());
     if (timed) HIPCHK(hipEventRecord(h->ev[3], 0));
-    hipLaunchKernelGGL(mopt::k_mopt_grad, dim3(blocks(F, 64)), dim3(64), 0, 0, h->d_model, h->K, h->W);
+    hipLaunchKernelGGL(mopt::k_mopt_grad, dim3(blocks(F, 64)), dim3(64), 0, 0, h->d_model, b.K, b.W);
     HIPCHK(hipGetLastError());
     if (timed) HIPCHK(hipEventRecord(h->ev[4], 0));
-    hipLaunchKernelGGL(mopt::k_mopt_reduce, dim3(blocks((long long)C * mopt::NT, 64)), dim3(64), 0, 0, h->K, h->W);
+    hipLaunchKernelGGL(mopt::k_mopt_reduce, dim3(blocks((long long)C * mopt::NT, 64)), dim3(64), 0, 0, b.K, b.W);
     HIPCHK(hipGetLastError());
     if (timed) HIPCHK(hipEventRecord(h->ev[5], 0));
     return PARC_OK;
@@ -726,34 +725,36 @@ static int mopt_eval(ParcMotionOpt *h, bool timed) {
 
 extern "C" int parc_mopt_loss_and_grad(ParcMotionOpt *h, float *terms, float *grad) {
     if (int rc = mopt_check(h)) return rc;
+    const ParcMotionOpt::Batch &b = *h->batch;
     HIPCHK(hipSetDevice(h->device));
     if (int rc = mopt_eval(h, false)) return rc;
     HIPCHK(hipDeviceSynchronize());
-    if (terms) HIPCHK(hipMemcpy(terms, h->W.terms, (size_t)h->K.C * mopt::NT * sizeof(float), hipMemcpyDeviceToHost));
-    if (grad) HIPCHK(hipMemcpy(grad, h->W.grad, (size_t)h->F * h->host_model.NP * sizeof(float), hipMemcpyDeviceToHost));
+    if (terms) HIPCHK(hipMemcpy(terms, b.W.terms, (size_t)b.K.C * mopt::NT * sizeof(float), hipMemcpyDeviceToHost));
+    if (grad) HIPCHK(hipMemcpy(grad, b.W.grad, (size_t)b.F * h->host_model.NP * sizeof(float), hipMemcpyDeviceToHost));
     return PARC_OK;
 }
 
 extern "C" int parc_mopt_step(ParcMotionOpt *h, int32_t n_iters, float *terms) {
     if (int rc = mopt_check(h)) return rc;
     if (n_iters < 0) return fail(PARC_ERR_INVALID, "mopt: n_iters must be >= 0");
+    ParcMotionOpt::Batch &b = *h->batch;
     HIPCHK(hipSetDevice(h->device));
-    const long long n = h->F * h->host_model.NP;
+    const long long n = b.F * h->host_model.NP;
     double acc[6] = {0, 0, 0, 0, 0, 0};
     for (int it = 0; it < n_iters; ++it) {
         if (int rc = mopt_eval(h, true)) return rc;
-        h->adam_t++;
-        const double bc1 = 1.0 - pow(0.9, (double)h->adam_t), bc2 = 1.0 - pow(0.999, (double)h->adam_t);
-        hipLaunchKernelGGL(mopt::k_mopt_adam, dim3(blocks(n, 256)), dim3(256), 0, 0, h->W, n, (float)((double)h->step_size / bc1),
+        b.adam_t++;
+        const double bc1 = 1.0 - pow(0.9, (double)b.adam_t), bc2 = 1.0 - pow(0.999, (double)b.adam_t);
+        hipLaunchKernelGGL(mopt::k_mopt_adam, dim3(blocks(n, 256)), dim3(256), 0, 0, b.W, n, (float)((double)h->step_size / bc1),
                            (float)sqrt(bc2));
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(h->ev[6], 0));
-        if (terms) HIPCHK(hipMemcpy(terms + (size_t)it * h->K.C * mopt::NT, h->W.terms, (size_t)h->K.C * mopt::NT * sizeof(float),
+        if (terms) HIPCHK(hipMemcpy(terms + (size_t)it * b.K.C * mopt::NT, b.W.terms, (size_t)b.K.C * mopt::NT * sizeof(float),
                                     hipMemcpyDeviceToHost));
         HIPCHK(hipEventSynchronize(h->ev[6]));
         for (int k = 0; k < 6; ++k) {              // fk, patch, points, grad, reduce, adam
             float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, h->ev[k], h->ev[k + 1]));
+            PARC_TRY(h->ev.elapsed(ms, k, k + 1));
             acc[k] += ms;
         }
     }
@@ -769,16 +770,17 @@ extern "C" int parc_mopt_kernel_times(ParcMotionOpt *h, float *ms6) {
 
 extern "C" int parc_mopt_get_frames(ParcMotionOpt *h, float *root_pos, float *root_rot, float *joint_rot) {
     if (int rc = mopt_check(h)) return rc;
+    const ParcMotionOpt::Batch &b = *h->batch;
     HIPCHK(hipSetDevice(h->device));
-    hipLaunchKernelGGL(mopt::k_mopt_fk, dim3(blocks(h->F, 64)), dim3(64), 0, 0, h->d_model, h->K, h->W);
+    hipLaunchKernelGGL(mopt::k_mopt_fk, dim3(blocks(b.F, 64)), dim3(64), 0, 0, h->d_model, b.K, b.W);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     const int B = h->host_model.B, NP = h->host_model.NP;
-    std::vector<float> rot((size_t)h->F * B * 4), jr((size_t)h->F * B * 4), par((size_t)h->F * NP);
-    HIPCHK(hipMemcpy(rot.data(), h->W.rot, rot.size() * sizeof(float), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(jr.data(), h->W.jrot, jr.size() * sizeof(float), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(par.data(), h->W.params, par.size() * sizeof(float), hipMemcpyDeviceToHost));
-    for (long long f = 0; f < h->F; ++f) {
+    std::vector<float> rot((size_t)b.F * B * 4), jr((size_t)b.F * B * 4), par((size_t)b.F * NP);
+    HIPCHK(hipMemcpy(rot.data(), b.W.rot, rot.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(jr.data(), b.W.jrot, jr.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(par.data(), b.W.params, par.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (long long f = 0; f < b.F; ++f) {
         if (root_pos) for (int k = 0; k < 3; ++k) root_pos[3 * f + k] = par[f * NP + k];
         if (root_rot) for (int k = 0; k < 4; ++k) root_rot[4 * f + k] = rot[f * B * 4 + k];
         if (joint_rot) for (int j = 1; j < B; ++j) for (int k = 0; k < 4; ++k) joint_rot[(f * (B - 1) + j - 1) * 4 + k] = jr[(f * B + j) * 4 + k];
@@ -788,10 +790,11 @@ extern "C" int parc_mopt_get_frames(ParcMotionOpt *h, float *root_pos, float *ro
 
 extern "C" int parc_mopt_get_source_body(ParcMotionOpt *h, float *body_pos, float *body_rot) {
     if (int rc = mopt_check(h)) return rc;
+    const ParcMotionOpt::Batch &b = *h->batch;
     HIPCHK(hipSetDevice(h->device));
-    const size_t n = (size_t)h->F * h->host_model.B;
-    if (body_pos) HIPCHK(hipMemcpy(body_pos, h->K.src_pos, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (body_rot) HIPCHK(hipMemcpy(body_rot, h->K.src_rot, n * 4 * sizeof(float), hipMemcpyDeviceToHost));
+    const size_t n = (size_t)b.F * h->host_model.B;
+    if (body_pos) HIPCHK(hipMemcpy(body_pos, b.K.src_pos, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (body_rot) HIPCHK(hipMemcpy(body_rot, b.K.src_rot, n * 4 * sizeof(float), hipMemcpyDeviceToHost));
     return PARC_OK;
 }
 
@@ -799,20 +802,17 @@ extern "C" int parc_mopt_build_constraints(ParcMotionOpt *h, int32_t n, const in
     if (int rc = mopt_check(h)) return rc;
     if (n < 0 || steps < 0 || (n > 0 && (!clip || !pts))) return fail(PARC_ERR_INVALID, "mopt: bad constraint arguments");
     if (n == 0) return PARC_OK;
-    for (int i = 0; i < n; ++i) if (clip[i] < 0 || clip[i] >= h->K.C) return fail(PARC_ERR_INVALID, "mopt: constraint clip out of range");
+    const mopt::Clips &K = h->batch->K;
+    for (int i = 0; i < n; ++i) if (clip[i] < 0 || clip[i] >= K.C) return fail(PARC_ERR_INVALID, "mopt: constraint clip out of range");
     HIPCHK(hipSetDevice(h->device));
-    int *d_clip = nullptr; float *d_pts = nullptr;
-    HIPCHK(hipMalloc(&d_clip, n * sizeof(int)));
-    hipError_t e = hipMalloc(&d_pts, 3 * (size_t)n * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(d_clip, clip, n * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_pts, pts, 3 * (size_t)n * sizeof(float), hipMemcpyHostToDevice);
-    for (int s = 0; s < steps && e == hipSuccess; ++s) {
-        hipLaunchKernelGGL(mopt::k_mopt_cons_sgd, dim3(blocks(n, 64)), dim3(64), 0, 0, h->K, d_clip, d_pts, n, lr);
-        e = hipGetLastError();
+    DeviceArena tmp;                      // this call's inputs
+    int *d_clip; float *d_pts;
+    PARC_TRY(tmp.alloc(d_clip, n, clip));
+    PARC_TRY(tmp.alloc(d_pts, 3LL * n, pts));
+    for (int s = 0; s < steps; ++s) {
+        hipLaunchKernelGGL(mopt::k_mopt_cons_sgd, dim3(blocks(n, 64)), dim3(64), 0, 0, K, d_clip, d_pts, n, lr);
+        HIPCHK(hipGetLastError());
     }
-    if (e == hipSuccess) e = hipMemcpy(pts, d_pts, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost);
-    (void)hipFree(d_clip);
-    if (d_pts) (void)hipFree(d_pts);
-    if (e != hipSuccess) return fail(PARC_ERR_HIP, std::string("mopt build_constraints: ") + hipGetErrorString(e));
+    HIPCHK(hipMemcpy(pts, d_pts, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return PARC_OK;
 }

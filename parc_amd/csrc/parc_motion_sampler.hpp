@@ -18,6 +18,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -351,50 +352,26 @@ __global__ void k_msamp_draw_noise(Cfg G, float *noise, long long n, unsigned lo
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------------
 struct ParcMotionSampler {
+    struct Library {                      // what one parc_msamp_set_clips loads; a library is loaded when the handle holds one
+        DeviceArena mem;
+        mopt::Clips K{};                  // the frames and terrains
+        msamp::Lib L{};
+        std::vector<int> clip_windows;    // num_frames - T per clip
+        int bit_words = 0;                // words of the largest terrain's cell bitset
+    };
     int device = 0;
     mopt::Model host_model;
+    DeviceArena mem;                      // create .. destroy: d_model, d_status, the times / grid tables of cfg
     mopt::Model *d_model = nullptr;
     msamp::Cfg cfg{};
-    mopt::Clips K{};
-    msamp::Lib L{};
-    DeviceArena lib;                      // the library (set_clips)
-    DeviceArena tables;                   // times / grid tables (create)
-    std::vector<int> clip_windows;        // num_frames - T per clip
-    int bit_words = 0;                    // words of the largest terrain's cell bitset
+    std::unique_ptr<Library> lib;
     int *d_status = nullptr;
-    hipEvent_t ev[4] = {};
-    bool timed = false, drew = false;
+    DeviceEvents<4> ev;
+    bool timed = false;
+    ~ParcMotionSampler() { (void)hipSetDevice(device); }   // the members release the rest
 };
 
-static void msamp_free_lib(ParcMotionSampler *h) {
-    h->lib.release();
-    h->K = mopt::Clips{};
-    h->L = msamp::Lib{};
-    h->clip_windows.clear();
-    h->bit_words = 0;
-}
-
-extern "C" void parc_msamp_destroy(ParcMotionSampler *h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    msamp_free_lib(h);
-    h->tables.release();
-    if (h->d_model) (void)hipFree(h->d_model);
-    if (h->d_status) (void)hipFree(h->d_status);
-    for (int i = 0; i < 4; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-    delete h;
-}
-
-static int msamp_create_device(ParcMotionSampler *h, const ParcMotionSamplerParams *p) {
-    HIPCHK(model_upload(p->device, h->host_model, &h->d_model));
-    HIPCHK(hipMalloc((void **)&h->d_status, sizeof(int)));
-    HIPCHK(hipMemset(h->d_status, 0, sizeof(int)));
-    PARC_TRY(h->tables.alloc(h->cfg.times, p->num_frames, p->times_host));
-    PARC_TRY(h->tables.alloc(h->cfg.gridx, p->grid_dim_x, p->grid_x_host));
-    PARC_TRY(h->tables.alloc(h->cfg.gridy, p->grid_dim_y, p->grid_y_host));
-    for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreate(&h->ev[i]));
-    return PARC_OK;
-}
+extern "C" void parc_msamp_destroy(ParcMotionSampler *h) { delete h; }
 
 extern "C" int parc_msamp_create(const ParcMotionSamplerParams *p, ParcMotionSampler **out) {
     if (!p || !out) return fail(PARC_ERR_INVALID, "msamp: null argument");
@@ -415,7 +392,7 @@ extern "C" int parc_msamp_create(const ParcMotionSamplerParams *p, ParcMotionSam
     if (!(p->timestep > 0.f) || !(p->dx > 0.f)) return fail(PARC_ERR_INVALID, "msamp: sequence_fps and horizontal_scale must be > 0");
     mopt::Model M;
     PARC_TRY(model_tree("msamp", cm, M));
-    ParcMotionSampler *h = new (std::nothrow) ParcMotionSampler();
+    std::unique_ptr<ParcMotionSampler> h(new (std::nothrow) ParcMotionSampler());   // every failure below is a plain return
     if (!h) return fail(PARC_ERR_INVALID, "msamp: out of host memory");
     h->device = p->device; h->host_model = M;
     msamp::Cfg &G = h->cfg;
@@ -426,11 +403,18 @@ extern "C" int parc_msamp_create(const ParcMotionSamplerParams *p, ParcMotionSam
     G.max_h = p->max_h; G.box_min = p->box_min_len; G.box_max = p->box_max_len; G.pool_chance = p->hf_maxpool_chance;
     G.height_chance = p->hf_change_height_chance; G.noise_scale = p->future_pos_noise_scale; G.fw_min = p->future_window_min;
     G.fw_max = p->future_window_max;
-    if (int rc = msamp_create_device(h, p)) { parc_msamp_destroy(h); return rc; }
-    *out = h;
+    HIPCHK(hipSetDevice(p->device));
+    PARC_TRY(model_upload(h->mem, M, h->d_model));
+    PARC_TRY(h->mem.alloc_fill(h->d_status, 1));
+    PARC_TRY(h->mem.alloc(G.times, p->num_frames, p->times_host));
+    PARC_TRY(h->mem.alloc(G.gridx, p->grid_dim_x, p->grid_x_host));
+    PARC_TRY(h->mem.alloc(G.gridy, p->grid_dim_y, p->grid_y_host));
+    PARC_TRY(h->ev.create());
+    *out = h.release();
     return PARC_OK;
 }
 
+// as parc_mopt_set_clips: validate; release the old library; build the new one in a local; install it last (never a half-filled one)
 extern "C" int parc_msamp_set_clips(ParcMotionSampler *h, const ParcMotionOptClips *c, const ParcMotionSamplerClipInfo *info) {
     if (!h || !c || !info) return fail(PARC_ERR_INVALID, "msamp: null argument");
     PARC_TRY(clip_batch_arrays("msamp", c));
@@ -483,18 +467,21 @@ extern "C" int parc_msamp_set_clips(ParcMotionSampler *h, const ParcMotionOptCli
         if ((int)((X * Y + 31) / 32) > bit_words) bit_words = (int)((X * Y + 31) / 32);
     }
     HIPCHK(hipSetDevice(h->device));
-    msamp_free_lib(h);
-    mopt::Clips &K = h->K;
-    msamp::Lib &L = h->L;
-    DeviceArena &mem = h->lib;
+    h->lib.reset();
+    std::unique_ptr<ParcMotionSampler::Library> nl(new (std::nothrow) ParcMotionSampler::Library());
+    if (!nl) return fail(PARC_ERR_INVALID, "msamp: out of host memory");
+    mopt::Clips &K = nl->K;
+    msamp::Lib &L = nl->L;
+    DeviceArena &mem = nl->mem;
     PARC_TRY(clip_batch_upload(mem, K, c, cb, B));
     PARC_TRY(mem.alloc(L.meta, C, meta.data()));
     PARC_TRY(mem.alloc(L.maxmin, 2 * ncell, info->hf_maxmin_host));
     PARC_TRY(mem.alloc(L.mask_off, F + 1, info->mask_off_host));
     PARC_TRY(mem.alloc(L.mask_cells, info->mask_off_host[F], info->mask_cells_host));
     PARC_TRY(mem.alloc(L.cdf, C, cdf.data()));
-    h->clip_windows = windows;
-    h->bit_words = bit_words;
+    nl->clip_windows.swap(windows);
+    nl->bit_words = bit_words;
+    h->lib = std::move(nl);
     return PARC_OK;
 }
 
@@ -514,7 +501,7 @@ static msamp::OutD msamp_out(const ParcMotionSamplerOutputs *o) {
 
 static int msamp_check_plan(ParcMotionSampler *h, const ParcMotionSamplerPlan *p, bool hf) {
     if (!h || !p) return fail(PARC_ERR_INVALID, "msamp: null argument");
-    if (h->K.C == 0) return fail(PARC_ERR_STATE, "msamp: parc_msamp_set_clips first");
+    if (!h->lib) return fail(PARC_ERR_STATE, "msamp: parc_msamp_set_clips first");
     if (p->n < 1) return fail(PARC_ERR_INVALID, "msamp: n must be >= 1");
     if (!p->motion_id || !p->t0 || !p->t_future || !p->future_pos_noise) return fail(PARC_ERR_INVALID, "msamp: null plan array");
     if (hf && h->cfg.aug == PARC_MSAMP_AUG_MAXPOOL_AND_BOXES &&
@@ -531,12 +518,12 @@ static int msamp_launch(ParcMotionSampler *h, const ParcMotionSamplerPlan *plan,
     if ((out->target_pos == nullptr) != (out->target_rot == nullptr)) return fail(PARC_ERR_INVALID, "msamp: target_pos and target_rot go together");
     const msamp::PlanD P = msamp_plan(plan);
     const msamp::OutD O = msamp_out(out);
-    hipLaunchKernelGGL(msamp::k_msamp_window, dim3((unsigned)plan->n), dim3(64), msamp::win_lds_bytes(G.T, G.B), st, h->d_model, h->K, h->L, G, P, O,
+    hipLaunchKernelGGL(msamp::k_msamp_window, dim3((unsigned)plan->n), dim3(64), msamp::win_lds_bytes(G.T, G.B), st, h->d_model, h->lib->K, h->lib->L, G, P, O,
                        -1, h->d_status);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev[2], st));
     if (out->hfs) {
-        hipLaunchKernelGGL(msamp::k_msamp_hf, dim3((unsigned)plan->n), dim3(msamp::HF_THREADS), (size_t)h->bit_words * sizeof(unsigned), st, h->K, h->L, G, P, O,
+        hipLaunchKernelGGL(msamp::k_msamp_hf, dim3((unsigned)plan->n), dim3(msamp::HF_THREADS), (size_t)h->lib->bit_words * sizeof(unsigned), st, h->lib->K, h->lib->L, G, P, O,
                            h->d_status);
         HIPCHK(hipGetLastError());
     }
@@ -550,7 +537,7 @@ static int msamp_draw(ParcMotionSampler *h, uint64_t seed, const ParcMotionSampl
     if (!plan->change_height || !plan->height_value || !plan->pool_kind || !plan->pool_size || !plan->num_boxes || (G.maxb > 0 && !plan->boxes))
         return fail(PARC_ERR_INVALID, "msamp: draw_plan fills every array of the plan (noise may be NULL outside NOISE mode)");
     const long long n = plan->n;
-    hipLaunchKernelGGL(msamp::k_msamp_draw, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, h->K, h->L, G, msamp_plan(plan), n,
+    hipLaunchKernelGGL(msamp::k_msamp_draw, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, h->lib->K, h->lib->L, G, msamp_plan(plan), n,
                        (unsigned long long)seed);
     HIPCHK(hipGetLastError());
     if (plan->noise) {
@@ -590,15 +577,15 @@ extern "C" int parc_msamp_sample(ParcMotionSampler *h, uint64_t seed, const Parc
 
 extern "C" int parc_msamp_enumerate(ParcMotionSampler *h, int32_t clip, const ParcMotionSamplerOutputs *out, void *stream) {
     if (!h || !out) return fail(PARC_ERR_INVALID, "msamp: null argument");
-    if (h->K.C == 0) return fail(PARC_ERR_STATE, "msamp: parc_msamp_set_clips first");
-    if (clip < 0 || clip >= h->K.C) return fail(PARC_ERR_INVALID, "msamp: clip out of range");
+    if (!h->lib) return fail(PARC_ERR_STATE, "msamp: parc_msamp_set_clips first");
+    if (clip < 0 || clip >= h->lib->K.C) return fail(PARC_ERR_INVALID, "msamp: clip out of range");
     if (out->hfs || out->floor_heights || out->target_pos || out->target_rot || out->hf_bounds)
         return fail(PARC_ERR_INVALID, "msamp: enumerate writes the motion outputs only");
     HIPCHK(hipSetDevice(h->device));
     const msamp::Cfg &G = h->cfg;
     msamp::PlanD P{};
-    hipLaunchKernelGGL(msamp::k_msamp_window, dim3((unsigned)h->clip_windows[(size_t)clip]), dim3(64), msamp::win_lds_bytes(G.T, G.B),
-                       (hipStream_t)stream, h->d_model, h->K, h->L, G, P, msamp_out(out), (int)clip, h->d_status);
+    hipLaunchKernelGGL(msamp::k_msamp_window, dim3((unsigned)h->lib->clip_windows[(size_t)clip]), dim3(64), msamp::win_lds_bytes(G.T, G.B),
+                       (hipStream_t)stream, h->d_model, h->lib->K, h->lib->L, G, P, msamp_out(out), (int)clip, h->d_status);
     HIPCHK(hipGetLastError());
     return PARC_OK;
 }
@@ -619,6 +606,6 @@ extern "C" int parc_msamp_kernel_times(ParcMotionSampler *h, float *ms3) {
     if (!h->timed) return fail(PARC_ERR_STATE, "msamp: nothing sampled yet");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipEventSynchronize(h->ev[3]));
-    for (int k = 0; k < 3; ++k) HIPCHK(hipEventElapsedTime(&ms3[k], h->ev[k], h->ev[k + 1]));
+    for (int k = 0; k < 3; ++k) PARC_TRY(h->ev.elapsed(ms3[k], k, k + 1));
     return PARC_OK;
 }

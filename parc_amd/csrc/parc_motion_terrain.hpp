@@ -20,6 +20,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -378,40 +379,30 @@ __global__ void __launch_bounds__(PT_THREADS) k_mterr_point_sdf(const mopt::Mode
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------------
 struct ParcMotionTerrain {
+    struct Batch {                        // what one parc_mterr_set_clips loads; a batch is loaded when the handle holds one
+        DeviceArena mem;
+        mopt::Clips K{};
+        mterr::Work W{};
+        std::vector<int> counts;          // per-frame mask counts of the last run
+        std::vector<long long> offsets;
+        long long F = 0, ncell = 0, total = 0;
+        bool ran = false;
+    };
     int device = 0;
     mopt::Model host_model;
+    DeviceArena mem;                      // create .. destroy: d_model
     mopt::Model *d_model = nullptr;
     mterr::Cfg cfg{};
-    mopt::Clips K{};
-    mterr::Work W{};
-    DeviceArena batch;                    // everything of the current batch
-    std::vector<int> counts;              // per-frame mask counts of the last run
-    std::vector<long long> offsets;
-    long long F = 0, ncell = 0, total = 0;
-    bool ran = false;
-    int *d_inds = nullptr;                // [inds_cap][2]: parc_mterr_get_mask_inds' output, grown as needed, freed by destroy
+    std::unique_ptr<Batch> batch;
+    DeviceArena inds;                     // d_inds alone: released and allocated anew when it must grow
+    int *d_inds = nullptr;                // [inds_cap][2]: parc_mterr_get_mask_inds' output
     long long inds_cap = 0;
-    hipEvent_t ev[8] = {};
+    DeviceEvents<8> ev;
     float kernel_ms[6] = {};
+    ~ParcMotionTerrain() { (void)hipSetDevice(device); }   // the members release the rest
 };
 
-static void mterr_free_batch(ParcMotionTerrain *h) {
-    h->batch.release();
-    h->K = mopt::Clips{};
-    h->W = mterr::Work{};
-    h->F = h->ncell = h->total = 0;
-    h->ran = false;
-}
-
-extern "C" void parc_mterr_destroy(ParcMotionTerrain *h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    mterr_free_batch(h);
-    if (h->d_inds) (void)hipFree(h->d_inds);
-    if (h->d_model) (void)hipFree(h->d_model);
-    for (int i = 0; i < 8; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-    delete h;
-}
+extern "C" void parc_mterr_destroy(ParcMotionTerrain *h) { delete h; }
 
 extern "C" int parc_mterr_create(const ParcMotionTerrainParams *p, ParcMotionTerrain **out) {
     if (!p || !out) return fail(PARC_ERR_INVALID, "mterr: null argument");
@@ -428,18 +419,19 @@ extern "C" int parc_mterr_create(const ParcMotionTerrainParams *p, ParcMotionTer
     PARC_TRY(model_points("mterr", M, p->num_points, p->points_host, p->point_body_host, p->contact_body_id));
     int sort_n = 1;
     while (sort_n < M.P) sort_n <<= 1;
-    ParcMotionTerrain *h = new (std::nothrow) ParcMotionTerrain();
+    std::unique_ptr<ParcMotionTerrain> h(new (std::nothrow) ParcMotionTerrain());   // every failure below is a plain return
     if (!h) return fail(PARC_ERR_INVALID, "mterr: out of host memory");
     h->device = p->device; h->host_model = M;
     h->cfg.sdf_mode = p->sdf_mode; h->cfg.sort_n = sort_n;
     h->cfg.z_buf = p->z_buf; h->cfg.jump_buf = (float)p->jump_buf; h->cfg.max_jerk = (float)p->max_jerk;
-    hipError_t e = model_upload(p->device, M, &h->d_model);
-    for (int i = 0; i < 8 && e == hipSuccess; ++i) e = hipEventCreate(&h->ev[i]);
-    if (e != hipSuccess) { parc_mterr_destroy(h); return fail(PARC_ERR_HIP, std::string("mterr create: ") + hipGetErrorString(e)); }
-    *out = h;
+    HIPCHK(hipSetDevice(p->device));
+    PARC_TRY(model_upload(h->mem, M, h->d_model));
+    PARC_TRY(h->ev.create());
+    *out = h.release();
     return PARC_OK;
 }
 
+// as parc_mopt_set_clips: validate; release the old batch; build the new one in a local; install it last
 extern "C" int parc_mterr_set_clips(ParcMotionTerrain *h, const ParcMotionOptClips *c) {
     if (!h || !c) return fail(PARC_ERR_INVALID, "mterr: null argument");
     PARC_TRY(clip_batch_arrays("mterr", c));
@@ -453,10 +445,12 @@ extern "C" int parc_mterr_set_clips(ParcMotionTerrain *h, const ParcMotionOptCli
     const int C = cb.C, B = h->host_model.B, P = h->host_model.P;
     const long long F = cb.F, ncell = cb.ncell;
     HIPCHK(hipSetDevice(h->device));
-    mterr_free_batch(h);
-    mopt::Clips &K = h->K;
-    mterr::Work &W = h->W;
-    DeviceArena &mem = h->batch;
+    h->batch.reset();
+    std::unique_ptr<ParcMotionTerrain::Batch> nb(new (std::nothrow) ParcMotionTerrain::Batch());
+    if (!nb) return fail(PARC_ERR_INVALID, "mterr: out of host memory");
+    mopt::Clips &K = nb->K;
+    mterr::Work &W = nb->W;
+    DeviceArena &mem = nb->mem;
     PARC_TRY(clip_batch_upload(mem, K, c, cb, B));
     PARC_TRY(mem.alloc(K.frame_clip, F, cb.frame_clip.data()));
     PARC_TRY(mem.alloc(K.hf_min, C, cb.hf_min.data()));
@@ -471,112 +465,110 @@ extern "C" int parc_mterr_set_clips(ParcMotionTerrain *h, const ParcMotionOptCli
     PARC_TRY(mem.alloc(W.touched, ncell));
     PARC_TRY(mem.alloc(W.maxmin, 2 * ncell));
     PARC_TRY(mem.alloc(W.clip_out, (long long)C * mterr::NOUT));
-    h->F = F; h->ncell = ncell;
-    h->counts.assign((size_t)F, 0);
-    h->offsets.assign((size_t)F, 0);
+    nb->F = F; nb->ncell = ncell;
+    nb->counts.assign((size_t)F, 0);
+    nb->offsets.assign((size_t)F, 0);
+    h->batch = std::move(nb);
     return PARC_OK;
 }
 
 static int mterr_check(ParcMotionTerrain *h) {
     if (!h) return fail(PARC_ERR_INVALID, "mterr: null handle");
-    if (h->F == 0) return fail(PARC_ERR_STATE, "mterr: parc_mterr_set_clips first");
+    if (!h->batch) return fail(PARC_ERR_STATE, "mterr: parc_mterr_set_clips first");
     return PARC_OK;
 }
 
 extern "C" int parc_mterr_run(ParcMotionTerrain *h, float *clip_out, int32_t *mask_counts, float *hf_maxmin, int64_t *total_inds) {
     if (int rc = mterr_check(h)) return rc;
+    ParcMotionTerrain::Batch &b = *h->batch;
     HIPCHK(hipSetDevice(h->device));
-    const long long F = h->F, ncell = h->ncell;
-    const int C = h->K.C;
+    const long long F = b.F, ncell = b.ncell;
+    const int C = b.K.C;
     HIPCHK(hipEventRecord(h->ev[0], 0));
-    hipLaunchKernelGGL(mterr::k_mterr_fk, dim3(blocks(F, 64)), dim3(64), 0, 0, h->d_model, h->K, h->W);
+    hipLaunchKernelGGL(mterr::k_mterr_fk, dim3(blocks(F, 64)), dim3(64), 0, 0, h->d_model, b.K, b.W);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev[1], 0));
-    hipLaunchKernelGGL(mterr::k_mterr_init, dim3(blocks(ncell, 256)), dim3(256), 0, 0, ncell, h->W);
+    hipLaunchKernelGGL(mterr::k_mterr_init, dim3(blocks(ncell, 256)), dim3(256), 0, 0, ncell, b.W);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev[2], 0));
-    hipLaunchKernelGGL(mterr::k_mterr_points, dim3((unsigned)F), dim3(mterr::PT_THREADS), 0, 0, h->d_model, h->K, h->W, h->cfg);
+    hipLaunchKernelGGL(mterr::k_mterr_points, dim3((unsigned)F), dim3(mterr::PT_THREADS), 0, 0, h->d_model, b.K, b.W, h->cfg);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev[3], 0));
-    hipLaunchKernelGGL(mterr::k_mterr_reduce, dim3(blocks(C, 64)), dim3(64), 0, 0, h->K, h->W, h->host_model.B);
+    hipLaunchKernelGGL(mterr::k_mterr_reduce, dim3(blocks(C, 64)), dim3(64), 0, 0, b.K, b.W, h->host_model.B);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev[4], 0));
-    hipLaunchKernelGGL(mterr::k_mterr_cells, dim3(blocks(ncell, 256)), dim3(256), 0, 0, h->K, h->W, h->cfg, ncell);
+    hipLaunchKernelGGL(mterr::k_mterr_cells, dim3(blocks(ncell, 256)), dim3(256), 0, 0, b.K, b.W, h->cfg, ncell);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev[5], 0));
-    HIPCHK(hipMemcpy(h->counts.data(), h->W.cnt, (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(b.counts.data(), b.W.cnt, (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
     long long tot = 0;                                        // exclusive scan of the per-frame counts, in frame order
-    for (long long f = 0; f < F; ++f) { h->offsets[f] = tot; tot += h->counts[f]; }
-    HIPCHK(hipMemcpy(h->W.ind_off, h->offsets.data(), (size_t)F * sizeof(long long), hipMemcpyHostToDevice));
-    for (int k = 0; k < 5; ++k) HIPCHK(hipEventElapsedTime(&h->kernel_ms[k], h->ev[k], h->ev[k + 1]));
-    h->total = tot;
-    h->ran = true;
-    if (clip_out) HIPCHK(hipMemcpy(clip_out, h->W.clip_out, (size_t)C * mterr::NOUT * sizeof(float), hipMemcpyDeviceToHost));
-    if (mask_counts) memcpy(mask_counts, h->counts.data(), (size_t)F * sizeof(int));
-    if (hf_maxmin) HIPCHK(hipMemcpy(hf_maxmin, h->W.maxmin, (size_t)ncell * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    for (long long f = 0; f < F; ++f) { b.offsets[f] = tot; tot += b.counts[f]; }
+    HIPCHK(hipMemcpy(b.W.ind_off, b.offsets.data(), (size_t)F * sizeof(long long), hipMemcpyHostToDevice));
+    for (int k = 0; k < 5; ++k) PARC_TRY(h->ev.elapsed(h->kernel_ms[k], k, k + 1));
+    b.total = tot;
+    b.ran = true;
+    if (clip_out) HIPCHK(hipMemcpy(clip_out, b.W.clip_out, (size_t)C * mterr::NOUT * sizeof(float), hipMemcpyDeviceToHost));
+    if (mask_counts) memcpy(mask_counts, b.counts.data(), (size_t)F * sizeof(int));
+    if (hf_maxmin) HIPCHK(hipMemcpy(hf_maxmin, b.W.maxmin, (size_t)ncell * 2 * sizeof(float), hipMemcpyDeviceToHost));
     if (total_inds) *total_inds = tot;
     return PARC_OK;
 }
 
 static int mterr_check_ran(ParcMotionTerrain *h) {
     if (int rc = mterr_check(h)) return rc;
-    if (!h->ran) return fail(PARC_ERR_STATE, "mterr: parc_mterr_run first");
+    if (!h->batch->ran) return fail(PARC_ERR_STATE, "mterr: parc_mterr_run first");
     return PARC_OK;
 }
 
 extern "C" int parc_mterr_get_mask_inds(ParcMotionTerrain *h, int32_t *inds) {
     if (int rc = mterr_check_ran(h)) return rc;
-    if (!inds && h->total > 0) return fail(PARC_ERR_INVALID, "mterr: null output");
+    const ParcMotionTerrain::Batch &b = *h->batch;
+    if (!inds && b.total > 0) return fail(PARC_ERR_INVALID, "mterr: null output");
     h->kernel_ms[5] = 0.f;
-    if (h->total == 0) return PARC_OK;
+    if (b.total == 0) return PARC_OK;
     HIPCHK(hipSetDevice(h->device));
-    if (h->total > h->inds_cap) {
-        if (h->d_inds) (void)hipFree(h->d_inds);
-        h->d_inds = nullptr;
-        h->inds_cap = 0;
-        HIPCHK(hipMalloc(&h->d_inds, (size_t)h->total * 2 * sizeof(int)));
-        h->inds_cap = h->total;
+    if (b.total > h->inds_cap) {
+        h->inds.release();
+        h->d_inds = nullptr; h->inds_cap = 0;   // a failed allocation leaves no buffer, not a stale one
+        PARC_TRY(h->inds.alloc(h->d_inds, 2 * b.total));
+        h->inds_cap = b.total;
     }
-    int *d = h->d_inds;
-    hipError_t e = hipEventRecord(h->ev[6], 0);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(mterr::k_mterr_gather, dim3((unsigned)h->F), dim3(256), 0, 0, h->K, h->W, h->host_model.P, d);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(h->ev[7], 0);
-    if (e == hipSuccess) e = hipMemcpy(inds, d, (size_t)h->total * 2 * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipEventElapsedTime(&h->kernel_ms[5], h->ev[6], h->ev[7]);
-    if (e != hipSuccess) return fail(PARC_ERR_HIP, std::string("mterr get_mask_inds: ") + hipGetErrorString(e));
-    return PARC_OK;
+    HIPCHK(hipEventRecord(h->ev[6], 0));
+    hipLaunchKernelGGL(mterr::k_mterr_gather, dim3((unsigned)b.F), dim3(256), 0, 0, b.K, b.W, h->host_model.P, h->d_inds);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev[7], 0));
+    HIPCHK(hipMemcpy(inds, h->d_inds, (size_t)b.total * 2 * sizeof(int), hipMemcpyDeviceToHost));
+    return h->ev.elapsed(h->kernel_ms[5], 6, 7);
 }
 
 extern "C" int parc_mterr_get_min_heights(ParcMotionTerrain *h, float *min_heights, int32_t *touched) {
     if (int rc = mterr_check_ran(h)) return rc;
     HIPCHK(hipSetDevice(h->device));
-    const size_t n = (size_t)h->ncell;
+    const mterr::Work &W = h->batch->W;
+    const size_t n = (size_t)h->batch->ncell;
     if (min_heights) {
         std::vector<int> e(n);
-        HIPCHK(hipMemcpy(e.data(), h->W.minh, n * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(e.data(), W.minh, n * sizeof(int), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < n; ++i) min_heights[i] = mterr::dec_f(e[i]);
     }
-    if (touched) HIPCHK(hipMemcpy(touched, h->W.touched, n * sizeof(int), hipMemcpyDeviceToHost));
+    if (touched) HIPCHK(hipMemcpy(touched, W.touched, n * sizeof(int), hipMemcpyDeviceToHost));
     return PARC_OK;
 }
 
 extern "C" int parc_mterr_point_sdf(ParcMotionTerrain *h, int64_t frame0, int32_t num_frames, float *ground, float *air) {
     if (int rc = mterr_check_ran(h)) return rc;
-    if (num_frames < 1 || frame0 < 0 || frame0 + num_frames > h->F || !ground || !air) return fail(PARC_ERR_INVALID, "mterr: bad point_sdf range");
+    const ParcMotionTerrain::Batch &b = *h->batch;
+    if (num_frames < 1 || frame0 < 0 || frame0 + num_frames > b.F || !ground || !air) return fail(PARC_ERR_INVALID, "mterr: bad point_sdf range");
     HIPCHK(hipSetDevice(h->device));
     const size_t n = (size_t)num_frames * h->host_model.P;
+    DeviceArena tmp;                      // this call's output
     float *d = nullptr;
-    HIPCHK(hipMalloc(&d, 2 * n * sizeof(float)));
-    hipLaunchKernelGGL(mterr::k_mterr_point_sdf, dim3((unsigned)num_frames), dim3(mterr::PT_THREADS), 0, 0, h->d_model, h->K, h->W, h->cfg,
+    PARC_TRY(tmp.alloc(d, 2 * (long long)n));
+    hipLaunchKernelGGL(mterr::k_mterr_point_sdf, dim3((unsigned)num_frames), dim3(mterr::PT_THREADS), 0, 0, h->d_model, b.K, b.W, h->cfg,
                        (long long)frame0, d, d + n);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(ground, d, n * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(air, d + n, n * sizeof(float), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(PARC_ERR_HIP, std::string("mterr point_sdf: ") + hipGetErrorString(e));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(ground, d, n * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(air, d + n, n * sizeof(float), hipMemcpyDeviceToHost));
     return PARC_OK;
 }
 

@@ -21,6 +21,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <memory>
 #include <new>
 #include <string>
 
@@ -390,29 +391,21 @@ __global__ void __launch_bounds__(64) k_pp_graph(Cfg G, const float *hf, int q0,
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------------
 struct ParcPathPlanner {
+    struct Batch {                        // the buffers of up to cap queries; they exist once the handle holds one
+        DeviceArena mem;
+        pplan::Bufs B{};
+        int cap = 0, last_q = 0;          // last_q: queries of the last completed run (0 = none), what parc_pathplan_get_graph may read
+    };
     int device = 0;
     pplan::Cfg cfg{};
-    pplan::Bufs B{};
-    DeviceArena bufs;
-    int cap = 0, last_q = 0;
-    hipEvent_t ev[3] = {};
+    std::unique_ptr<Batch> batch;
+    DeviceEvents<3> ev;
     float graph_ms = 0.f;
     bool timed = false;
+    ~ParcPathPlanner() { (void)hipSetDevice(device); }   // the members release the rest
 };
 
-static void pplan_free(ParcPathPlanner *h) {
-    h->bufs.release();
-    h->B = pplan::Bufs{};
-    h->cap = 0; h->last_q = 0;
-}
-
-extern "C" void parc_pathplan_destroy(ParcPathPlanner *h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    pplan_free(h);
-    for (int i = 0; i < 3; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-    delete h;
-}
+extern "C" void parc_pathplan_destroy(ParcPathPlanner *h) { delete h; }
 
 extern "C" int parc_pathplan_create(const ParcPathPlanParams *p, ParcPathPlanner **out) {
     if (!p || !out) return fail(PARC_ERR_INVALID, "pathplan: null argument");
@@ -427,7 +420,7 @@ extern "C" int parc_pathplan_create(const ParcPathPlanParams *p, ParcPathPlanner
         return fail(PARC_ERR_INVALID, "pathplan: max_jump_xy_dist / dx gives a jump window radius of " + std::to_string((long long)rr) + " cells, above the limit of " +
                                           std::to_string(PARC_PATHPLAN_MAX_JUMP_RADIUS) + " (PARC_PATHPLAN_MAX_JUMP_RADIUS)");
     if (p->max_expansions < 1 || p->max_nodes < 1 || p->max_points < 1) return fail(PARC_ERR_INVALID, "pathplan: max_expansions, max_nodes and max_points must be >= 1");
-    ParcPathPlanner *h = new (std::nothrow) ParcPathPlanner();
+    std::unique_ptr<ParcPathPlanner> h(new (std::nothrow) ParcPathPlanner());   // every failure below is a plain return
     if (!h) return fail(PARC_ERR_INVALID, "pathplan: out of host memory");
     h->device = p->device;
     pplan::Cfg &G = h->cfg;
@@ -440,24 +433,25 @@ extern "C" int parc_pathplan_create(const ParcPathPlanParams *p, ParcPathPlanner
     G.max_cost = (float)p->max_cost; G.draw_thr = (float)(p->min_start_end_xy_dist - 1e-4);
     G.w_bumpy = p->w_bumpy; G.max_bumpy = p->max_bumpy; G.dxd = (double)p->dx;
     G.split = sqrt((double)p->dx * (double)p->dx + (double)p->dy * (double)p->dy) + 1e-3;
-    if (hipSetDevice(p->device) != hipSuccess) { delete h; return fail(PARC_ERR_HIP, "pathplan: hipSetDevice failed"); }
-    for (int i = 0; i < 3; ++i)
-        if (hipEventCreate(&h->ev[i]) != hipSuccess) { parc_pathplan_destroy(h); return fail(PARC_ERR_HIP, "pathplan: hipEventCreate failed"); }
-    if (hipFuncSetAttribute((const void *)pplan::k_pp_search, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pplan::search_lds(G.X * G.Y)) != hipSuccess) {
-        parc_pathplan_destroy(h);
+    HIPCHK(hipSetDevice(p->device));
+    PARC_TRY(h->ev.create());
+    if (hipFuncSetAttribute((const void *)pplan::k_pp_search, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pplan::search_lds(G.X * G.Y)) != hipSuccess)
         return fail(PARC_ERR_HIP, "pathplan: the search kernel's LDS request was refused");
-    }
-    *out = h;
+    *out = h.release();
     return PARC_OK;
 }
 
+// Buffers for Q queries: kept while they are large enough; otherwise the old ones are released first, the new ones built in a local and
+// installed last, so a failed allocation leaves the handle without buffers (and without a last batch), never with some of them.
 static int pplan_reserve(ParcPathPlanner *h, int Q) {
-    if (Q <= h->cap) return PARC_OK;
-    pplan_free(h);
+    if (h->batch && Q <= h->batch->cap) return PARC_OK;
+    h->batch.reset();
+    std::unique_ptr<ParcPathPlanner::Batch> nb(new (std::nothrow) ParcPathPlanner::Batch());
+    if (!nb) return fail(PARC_ERR_INVALID, "pathplan: out of host memory");
     const pplan::Cfg &G = h->cfg;
     const long long N = (long long)G.X * G.Y;
-    pplan::Bufs &B = h->B;
-    DeviceArena &mem = h->bufs;
+    pplan::Bufs &B = nb->B;
+    DeviceArena &mem = nb->mem;
     PARC_TRY(mem.alloc(B.hf_in, Q * N));
     PARC_TRY(mem.alloc(B.hf, Q * N));
     PARC_TRY(mem.alloc(B.start, 2LL * Q)); PARC_TRY(mem.alloc(B.goal, 2LL * Q));
@@ -465,7 +459,8 @@ static int pplan_reserve(ParcPathPlanner *h, int Q) {
     PARC_TRY(mem.alloc(B.nodes, (long long)Q * G.max_nodes));
     PARC_TRY(mem.alloc(B.cost, Q));
     PARC_TRY(mem.alloc(B.points, (long long)Q * G.max_points * 3));
-    h->cap = Q;
+    nb->cap = Q;
+    h->batch = std::move(nb);
     return PARC_OK;
 }
 
@@ -484,8 +479,8 @@ extern "C" int parc_pathplan_run(ParcPathPlanner *h, int32_t Q, const float *hf_
         }
     HIPCHK(hipSetDevice(h->device));
     if (int rc = pplan_reserve(h, Q)) return rc;
-    h->last_q = 0;
-    const pplan::Bufs &B = h->B;
+    h->batch->last_q = 0;
+    const pplan::Bufs &B = h->batch->B;
     HIPCHK(hipMemcpy((void *)B.hf_in, hf_host, (size_t)(Q * N) * sizeof(float), hipMemcpyHostToDevice));
     if (start_host) {
         HIPCHK(hipMemcpy(B.start, start_host, (size_t)Q * 2 * sizeof(int), hipMemcpyHostToDevice));
@@ -502,7 +497,7 @@ extern "C" int parc_pathplan_run(ParcPathPlanner *h, int32_t Q, const float *hf_
     HIPCHK(hipEventRecord(h->ev[2], 0));
     HIPCHK(hipEventSynchronize(h->ev[2]));
     h->timed = true;
-    h->last_q = Q;
+    h->batch->last_q = Q;
     const size_t q = (size_t)Q;
     if (out->status) HIPCHK(hipMemcpy(out->status, B.status, q * sizeof(int), hipMemcpyDeviceToHost));
     if (out->cost) HIPCHK(hipMemcpy(out->cost, B.cost, q * sizeof(float), hipMemcpyDeviceToHost));
@@ -519,43 +514,35 @@ extern "C" int parc_pathplan_run(ParcPathPlanner *h, int32_t Q, const float *hf_
 
 extern "C" int parc_pathplan_get_graph(ParcPathPlanner *h, int32_t q0, int32_t n, uint8_t *nbr_host, uint8_t *cliff_host, uint32_t *jump_host) {
     if (!h || !nbr_host || !cliff_host || !jump_host) return fail(PARC_ERR_INVALID, "pathplan: null argument");
-    if (h->last_q == 0) return fail(PARC_ERR_STATE, "pathplan: parc_pathplan_run first");
-    if (q0 < 0 || n < 1 || (long long)q0 + n > h->last_q) return fail(PARC_ERR_INVALID, "pathplan: the query range lies outside the last batch");
+    if (!h->batch || h->batch->last_q == 0) return fail(PARC_ERR_STATE, "pathplan: parc_pathplan_run first");
+    if (q0 < 0 || n < 1 || (long long)q0 + n > h->batch->last_q) return fail(PARC_ERR_INVALID, "pathplan: the query range lies outside the last batch");
     HIPCHK(hipSetDevice(h->device));
     const pplan::Cfg &G = h->cfg;
-    const size_t cells = (size_t)n * G.X * G.Y;
+    const long long cells = (long long)n * G.X * G.Y;
+    DeviceArena tmp;                      // this call's outputs and its two events
+    DeviceEvents<2> t;
     unsigned char *d_nbr = nullptr, *d_cliff = nullptr;
     unsigned *d_jump = nullptr;
-    HIPCHK(hipMalloc((void **)&d_nbr, cells));
-    int rc = PARC_OK;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto step = [&](hipError_t e, const char *what) { if (rc == PARC_OK && e != hipSuccess) rc = fail(PARC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
-    step(hipMalloc((void **)&d_cliff, cells), "hipMalloc");
-    step(hipMalloc((void **)&d_jump, cells * PARC_PATHPLAN_JUMP_WORDS * sizeof(unsigned)), "hipMalloc");
-    step(hipEventCreate(&e0), "hipEventCreate");
-    step(hipEventCreate(&e1), "hipEventCreate");
-    if (rc == PARC_OK) {
-        step(hipEventRecord(e0, 0), "hipEventRecord");
-        hipLaunchKernelGGL(pplan::k_pp_graph, dim3((unsigned)n), dim3(64), (size_t)G.X * G.Y * sizeof(float) + (size_t)((G.X * G.Y + 31) / 32) * 4, 0, G, h->B.hf, (int)q0,
-                           d_nbr, d_cliff, d_jump);
-        step(hipGetLastError(), "k_pp_graph");
-        step(hipEventRecord(e1, 0), "hipEventRecord");
-        step(hipMemcpy(nbr_host, d_nbr, cells, hipMemcpyDeviceToHost), "hipMemcpy");
-        step(hipMemcpy(cliff_host, d_cliff, cells, hipMemcpyDeviceToHost), "hipMemcpy");
-        step(hipMemcpy(jump_host, d_jump, cells * PARC_PATHPLAN_JUMP_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost), "hipMemcpy");
-        if (rc == PARC_OK) step(hipEventElapsedTime(&h->graph_ms, e0, e1), "hipEventElapsedTime");
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(d_nbr); (void)hipFree(d_cliff); (void)hipFree(d_jump);
-    return rc;
+    PARC_TRY(tmp.alloc(d_nbr, cells));
+    PARC_TRY(tmp.alloc(d_cliff, cells));
+    PARC_TRY(tmp.alloc(d_jump, cells * PARC_PATHPLAN_JUMP_WORDS));
+    PARC_TRY(t.create());
+    HIPCHK(hipEventRecord(t[0], 0));
+    hipLaunchKernelGGL(pplan::k_pp_graph, dim3((unsigned)n), dim3(64), (size_t)G.X * G.Y * sizeof(float) + (size_t)((G.X * G.Y + 31) / 32) * 4, 0, G, h->batch->B.hf,
+                       (int)q0, d_nbr, d_cliff, d_jump);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(t[1], 0));
+    HIPCHK(hipMemcpy(nbr_host, d_nbr, (size_t)cells, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(cliff_host, d_cliff, (size_t)cells, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(jump_host, d_jump, (size_t)cells * PARC_PATHPLAN_JUMP_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost));
+    return t.elapsed(h->graph_ms, 0, 1);
 }
 
 extern "C" int parc_pathplan_kernel_times(ParcPathPlanner *h, float *ms3) {
     if (!h || !ms3) return fail(PARC_ERR_INVALID, "pathplan: null argument");
     if (!h->timed) return fail(PARC_ERR_STATE, "pathplan: nothing planned yet");
     HIPCHK(hipSetDevice(h->device));
-    for (int k = 0; k < 2; ++k) HIPCHK(hipEventElapsedTime(&ms3[k], h->ev[k], h->ev[k + 1]));
+    for (int k = 0; k < 2; ++k) PARC_TRY(h->ev.elapsed(ms3[k], k, k + 1));
     ms3[2] = h->graph_ms;
     return PARC_OK;
 }

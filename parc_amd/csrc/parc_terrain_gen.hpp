@@ -17,6 +17,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -282,26 +283,14 @@ __global__ void k_tgen_validate_steps(const float *stairs, long long count, floa
 struct ParcTerrainGen {
     int device = 0;
     tgen::Cfg cfg{};
+    DeviceArena mem;                      // create .. destroy: d_status
     int *d_status = nullptr;
-    hipEvent_t ev[4] = {};
+    DeviceEvents<4> ev;
     bool drew = false, ran = false;
+    ~ParcTerrainGen() { (void)hipSetDevice(device); }   // the members release the rest
 };
 
-extern "C" void parc_tgen_destroy(ParcTerrainGen *h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->d_status) (void)hipFree(h->d_status);
-    for (int i = 0; i < 4; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-    delete h;
-}
-
-static int tgen_create_device(ParcTerrainGen *h) {
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMalloc((void **)&h->d_status, sizeof(int)));
-    HIPCHK(hipMemset(h->d_status, 0, sizeof(int)));
-    for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreate(&h->ev[i]));
-    return PARC_OK;
-}
+extern "C" void parc_tgen_destroy(ParcTerrainGen *h) { delete h; }
 
 extern "C" int parc_tgen_create(const ParcTerrainGenParams *p, ParcTerrainGen **out) {
     if (!p || !out) return fail(PARC_ERR_INVALID, "tgen: null argument");
@@ -320,7 +309,7 @@ extern "C" int parc_tgen_create(const ParcTerrainGenParams *p, ParcTerrainGen **
         return fail(PARC_ERR_INVALID, "tgen: maxpool_size = " + std::to_string(p->maxpool_size) + " must be 0 .. PARC_TGEN_MAX_POOL = " + std::to_string(PARC_TGEN_MAX_POOL));
     if (p->mode == PARC_TGEN_STAIRS && (p->num_stairs < 1 || p->num_stairs > PARC_TGEN_MAX_STAIRS))
         return fail(PARC_ERR_INVALID, "tgen: num_stairs = " + std::to_string(p->num_stairs) + " must be 1 .. PARC_TGEN_MAX_STAIRS = " + std::to_string(PARC_TGEN_MAX_STAIRS));
-    ParcTerrainGen *h = new (std::nothrow) ParcTerrainGen();
+    std::unique_ptr<ParcTerrainGen> h(new (std::nothrow) ParcTerrainGen());   // every failure below is a plain return
     if (!h) return fail(PARC_ERR_INVALID, "tgen: out of host memory");
     h->device = p->device;
     tgen::Cfg &G = h->cfg;
@@ -330,8 +319,10 @@ extern "C" int parc_tgen_create(const ParcTerrainGenParams *p, ParcTerrainGen **
     G.ph0 = p->path_min_height; G.ph1 = p->path_max_height; G.floor_h = p->floor_height;
     G.sh0 = p->min_stair_start_height; G.sh1 = p->max_stair_start_height; G.st0 = p->min_step_height; G.st1 = p->max_step_height;
     G.th0 = p->min_stair_thickness; G.th1 = p->max_stair_thickness;
-    if (int rc = tgen_create_device(h)) { parc_tgen_destroy(h); return rc; }
-    *out = h;
+    HIPCHK(hipSetDevice(h->device));
+    PARC_TRY(h->mem.alloc_fill(h->d_status, 1));
+    PARC_TRY(h->ev.create());
+    *out = h.release();
     return PARC_OK;
 }
 
@@ -440,7 +431,7 @@ extern "C" int parc_tgen_kernel_times(ParcTerrainGen *h, float *ms2) {
     if (!h->drew && !h->ran) return fail(PARC_ERR_STATE, "tgen: nothing generated yet");
     HIPCHK(hipSetDevice(h->device));
     ms2[0] = ms2[1] = 0.f;
-    if (h->drew) { HIPCHK(hipEventSynchronize(h->ev[1])); HIPCHK(hipEventElapsedTime(&ms2[0], h->ev[0], h->ev[1])); }
-    if (h->ran) { HIPCHK(hipEventSynchronize(h->ev[3])); HIPCHK(hipEventElapsedTime(&ms2[1], h->ev[2], h->ev[3])); }
+    if (h->drew) { HIPCHK(hipEventSynchronize(h->ev[1])); PARC_TRY(h->ev.elapsed(ms2[0], 0, 1)); }
+    if (h->ran) { HIPCHK(hipEventSynchronize(h->ev[3])); PARC_TRY(h->ev.elapsed(ms2[1], 2, 3)); }
     return PARC_OK;
 }

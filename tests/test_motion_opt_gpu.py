@@ -304,3 +304,67 @@ def test_driver_end_to_end_files_load_in_the_env(tmp_path):
         torch.cuda.synchronize()
         assert torch.isfinite(obs).all() and torch.isfinite(rew).all()
         del env
+
+
+# ---- the handle across set_clips calls: what a batch leaves behind must not reach the next one --------------------------------------
+def _reload_clips(opt):
+    """A: the analyser's TEASER_TERRAIN fixture clip (58 frames, 102 x 102 cells) with two body constraints.  B: its first 8 frames (the
+    optimiser takes 1; the jerk window needs 4) on a cropped terrain, with the one constraint that still fits.  A and B differ in
+    frames, cells and constraints, and [A, B] from [B] in clips."""
+    z = fixture("motion_terrain_TEASER_TERRAIN")
+    A = mo.OptClip(z["root_pos"], z["root_rot"], z["joint_rot"], z["contacts"], z["hf"], z["min_point"], float(z["dx"]))
+    lf, rf = opt.char_model.get_body_id("left_foot"), opt.char_model.get_body_id("right_foot")
+    A.cons_body = np.array([lf, rf], np.int32)
+    A.cons_start, A.cons_end = np.array([2, 30], np.int32), np.array([6, 40], np.int32)
+    A.cons_point = (z["root_pos"][[4, 35]] - np.array([0.0, 0.1, 0.9], np.float32)).astype(np.float32)
+    n = 8
+    B = mo.OptClip(A.root_pos[:n].copy(), A.root_rot[:n].copy(), A.joint_rot[:n].copy(), A.contacts[:n].copy(),
+                   np.ascontiguousarray(A.hf[:80, :60]), A.min_point, A.dx)
+    B.cons_body, B.cons_start, B.cons_end, B.cons_point = A.cons_body[:1], A.cons_start[:1], A.cons_end[:1], A.cons_point[:1]
+    return A, B
+
+
+def _opt_run(opt, p0):
+    """From the iterate p0: the loss terms and the gradient, then the parameters after 3 Adam steps."""
+    opt.set_params(p0)
+    terms, grad = opt.loss_and_grad()
+    opt.step(3)
+    return terms, grad, opt.get_params()
+
+
+def _bits_equal(a, b):
+    return len(a) == len(b) and all(x.shape == y.shape and np.array_equal(x.view(np.int32), y.view(np.int32)) for x, y in zip(a, b))
+
+
+def test_a_reload_equals_a_fresh_handle():
+    z = fixture(FIXTURES[0])
+    opt = mo.MotionOptimizer(CHAR, "cuda:0", cfg_of(z))
+    A, B = _reload_clips(opt)
+    opt.set_clips([A, B])
+    _opt_run(opt, opt.get_params())
+    opt.set_clips([B])
+    p0 = opt.get_params()
+    got = _opt_run(opt, p0)
+    fresh = mo.MotionOptimizer(CHAR, "cuda:0", cfg_of(z))
+    fresh.set_clips([B])
+    q0 = fresh.get_params()
+    want = _opt_run(fresh, q0)
+    assert p0.shape == (8, opt.NP) and _bits_equal([p0], [q0])
+    assert got[0].shape == (1, mo.NUM_TERMS) and _bits_equal(got, want)
+    assert np.isfinite(got[1]).all() and (got[1] != 0).any() and not np.array_equal(got[2], p0)
+
+
+def test_a_rejected_batch_leaves_the_previous_one_usable():
+    import ctypes as C
+    from gpu_helpers import raises_invalid
+    z = fixture(FIXTURES[0])
+    opt = mo.MotionOptimizer(CHAR, "cuda:0", cfg_of(z))
+    A, _ = _reload_clips(opt)
+    pk = opt.set_clips([A])
+    p0 = opt.get_params()
+    before = _opt_run(opt, p0)
+    bad = dict(pk, hf_geom=np.ascontiguousarray([[0, 0, 0, 0.4]], np.float32))
+    st = mo.clip_struct(bad, 1)
+    raises_invalid(lambda: opt._lib.parc_mopt_set_clips(opt._h, C.byref(st)), "mopt: dx must be > 0")
+    after = _opt_run(opt, p0)
+    assert _bits_equal(before, after)

@@ -451,3 +451,73 @@ def test_export_script_end_to_end(tmp_path):
     assert b["features"].shape == (8, 15, 120) and b["hfs"].shape == (8, 31, 31) and np.isfinite(b["features"]).all()
     st = yaml.safe_load(open(out / "feature_stats.yaml"))
     assert np.asarray(st["mean"]).shape == (15, 120) and np.asarray(st["std"]).shape == (15, 120)
+
+
+# ---- the handle across set_clips calls: what a library leaves behind must not reach the next one -----------------------------------
+def _reload_library(tmp_path):
+    """(sampler holding nothing of its own yet, A, B, their extra values).  A: the TEASER_TERRAIN clip (58 frames, 102 x 102 cells).
+    B: its first T + 4 frames (a clip needs more than T) on a cropped terrain that still holds every cell those frames mask."""
+    import copy
+    from parc_amd import motion_sampler as ms
+    z = fixture("root_boxes")
+    y = write_motion_yaml(tmp_path, ["TEASER_TERRAIN"], [1.0])
+    eA = extra_vals(["TEASER_TERRAIN"])[0]
+    s = ms.MotionWindowSampler(z["cfg"], y, CHAR, "cuda:0", extra_vals=[eA])
+    A = s.clips[0]
+    n, X, Y = s.cfg.T + 4, 80, 60
+    ter = copy.copy(A.terrain)
+    ter.hf = np.ascontiguousarray(np.asarray(A.terrain.hf, np.float32)[:X, :Y])
+    B = copy.copy(A)
+    B.name, B.terrain, B.weight = "TEASER_TERRAIN_head", ter, 2.0
+    B.root_pos, B.root_rot, B.joint_rot, B.contacts = A.root_pos[:n].copy(), A.root_rot[:n].copy(), A.joint_rot[:n].copy(), A.contacts[:n].copy()
+    eB = dict(hf_mask_inds=eA["hf_mask_inds"][:n], hf_maxmin=np.ascontiguousarray(eA["hf_maxmin"][:X, :Y]))
+    assert all(a[:, 0].max() < X and a[:, 1].max() < Y for a in eB["hf_mask_inds"] if len(a))
+    return s, (A, eA), (B, eB)
+
+
+def _load(s, *clips):
+    """parc_msamp_set_clips on the handle s holds, through the wrapper's own upload."""
+    s.clips, s.extra_vals = [c for c, _ in clips], [e for _, e in clips]
+    s._upload()
+
+
+def _plan4(s, motion_id):
+    """4 windows of an injected plan: start times inside B's 4 window starts, one height change, one box."""
+    t0 = (np.arange(4, dtype=np.float32) * np.float32(1.0 / 30.0)).astype(np.float32)
+    mb = s.cfg.max_num_boxes
+    boxes = np.zeros((4, mb, 6), np.float32)
+    boxes[2, 0] = [12.0, 14.0, 4.0, 6.0, 0.7, 0.5]
+    return s.plan_from_numpy(dict(motion_id=np.array(motion_id, np.int32), t0=t0, t_future=t0 + np.float32(0.1),
+                                  future_pos_noise=np.full((4, 3), 0.01, np.float32), change_height=np.array([0, 1, 0, 0], np.int32),
+                                  height_value=np.array([0, 0.4, 0, 0], np.float32), num_boxes=np.array([0, 0, 1, 0], np.int32), boxes=boxes))
+
+
+def test_a_reload_equals_a_fresh_handle(tmp_path):
+    s, A, B = _reload_library(tmp_path)
+    _load(s, A, B)
+    outputs(s.sample_with(_plan4(s, [0, 1, 1, 0]), return_bounds=True, validate=True))
+    _load(s, B)
+    got = outputs(s.sample_with(_plan4(s, [0, 0, 0, 0]), return_bounds=True, validate=True))
+    fresh, _, _ = _reload_library(tmp_path)
+    _load(fresh, B)
+    want = outputs(fresh.sample_with(_plan4(fresh, [0, 0, 0, 0]), return_bounds=True, validate=True))
+    assert got["hfs"].shape == (4, s.cfg.Gx, s.cfg.Gy) and bits_equal(got, want)
+    assert all(np.isfinite(v).all() for v in got.values()) and not np.array_equal(got["hfs"][0], got["hfs"][2])
+
+
+def test_a_rejected_library_leaves_the_previous_one_usable(tmp_path):
+    import copy
+    from parc_amd import lib as L
+    s, A, _ = _reload_library(tmp_path)
+    _load(s, A)
+    plan = _plan4(s, [0, 0, 0, 0])
+    before = outputs(s.sample_with(plan, return_bounds=True, validate=True))
+    ter = copy.copy(A[0].terrain)
+    ter.dx = 0.0
+    broken = copy.copy(A[0])
+    broken.terrain = ter
+    with pytest.raises(L.ParcError) as e:
+        _load(s, (broken, A[1]))
+    assert str(e.value) == "libparc_env error -1: msamp: dx must be > 0"
+    after = outputs(s.sample_with(plan, return_bounds=True, validate=True))
+    assert bits_equal(before, after)

@@ -388,3 +388,65 @@ def test_scripts_end_to_end(tmp_path):
     for f, row in zip(sorted(names), rows):
         z = a.analyze([mo.clip_from_ms(str(src / f))])[0]
         assert row["pen_loss"] == z["pen_loss"] and row["contact_loss"] == z["contact_loss"] and row["final_node_dist"] is None
+
+
+# ---- the handle across set_clips calls: what a batch leaves behind must not reach the next one --------------------------------------
+def _reload_clips():
+    """A: the TEASER_TERRAIN fixture clip (58 frames, 102 x 102 cells).  B: its first 8 frames (the analyser takes 1; the jerk window
+    needs 4) on a cropped terrain that still holds every cell those frames touch."""
+    A = clip_of(fixture("TEASER_TERRAIN"))
+    n = 8
+    B = mo.OptClip(A.root_pos[:n].copy(), A.root_rot[:n].copy(), A.joint_rot[:n].copy(), A.contacts[:n].copy(),
+                   np.ascontiguousarray(A.hf[:80, :60]), A.min_point, A.dx)
+    return A, B
+
+
+def _all_outputs(a, r):
+    """run's outputs (r: what MotionTerrainAnalyzer.run returned, mask inds included) and the lowest points, as bit patterns."""
+    mh, tc = a.min_heights()
+    return [bits(r["clip_out"]), r["counts"], r["inds"], bits(r["hf_maxmin"]), bits(mh), tc]
+
+
+def _same_outputs(x, y):
+    assert len(x) == len(y)
+    for i, (p, q) in enumerate(zip(x, y)):
+        assert p.shape == q.shape and np.array_equal(p, q), i
+
+
+@pytest.mark.parametrize("order", ["shrink", "grow"])
+def test_a_reload_equals_a_fresh_handle(order):
+    """shrink: [A, B] then [B].  grow: [B] then [A, B], where get_mask_inds has to grow its buffer between the two runs."""
+    A, B = _reload_clips()
+    first, second = ([A, B], [B]) if order == "shrink" else ([B], [A, B])
+    a = mt.MotionTerrainAnalyzer(CHAR, "cuda:0", points=ref_points())
+    r1 = a.run(first)
+    h = a._h
+    got = _all_outputs(a, a.run(second))
+    assert a._h.value == h.value                     # the same handle served both batches
+    fresh = mt.MotionTerrainAnalyzer(CHAR, "cuda:0", points=ref_points())
+    _same_outputs(got, _all_outputs(fresh, fresh.run(second)))
+    n1, n2 = len(r1["inds"]), len(got[2])
+    assert n1 > 0 and n2 > 0 and (n2 > n1) == (order == "grow")
+
+
+def test_a_rejected_batch_leaves_the_previous_one_usable():
+    from gpu_helpers import raises_invalid
+    from parc_amd import lib as L
+    A, _ = _reload_clips()
+    a = mt.MotionTerrainAnalyzer(CHAR, "cuda:0", points=ref_points())
+    r = a.run([A])
+    before = _all_outputs(a, r)
+    g0, a0 = a.point_sdf(3, 2)
+    pk = r["packed"]
+    bad = dict(pk, hf_geom=np.ascontiguousarray([[0, 0, 0, 0.4]], np.float32))
+    st = mt.clip_struct(bad, 1)
+    raises_invalid(lambda: a._lib.parc_mterr_set_clips(a._h, C.byref(st)), "mterr: dx must be > 0")
+    # the same run again, on the batch the handle still holds (MotionTerrainAnalyzer.run would load it anew)
+    out, counts, maxmin = np.zeros_like(r["clip_out"]), np.zeros_like(r["counts"]), np.zeros_like(r["hf_maxmin"])
+    total = C.c_int64()
+    L.check(a._lib.parc_mterr_run(a._h, L.np_f32p(out), L.np_i32p(counts), L.np_f32p(maxmin), C.byref(total)))
+    inds = np.zeros((int(total.value), 2), np.int32)
+    L.check(a._lib.parc_mterr_get_mask_inds(a._h, L.np_i32p(inds)))
+    _same_outputs(before, _all_outputs(a, dict(clip_out=out, counts=counts, inds=inds, hf_maxmin=maxmin)))
+    g1, a1 = a.point_sdf(3, 2)
+    assert np.array_equal(bits(g0), bits(g1)) and np.array_equal(bits(a0), bits(a1))

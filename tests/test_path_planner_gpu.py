@@ -194,6 +194,37 @@ def test_refusals():
     assert (big.status == pp.FOUND).all()
 
 
+def _same_plan(a, b):
+    assert np.array_equal(a.status, b.status) and a.cost.tobytes() == b.cost.tobytes() and np.array_equal(a.pops, b.pops)
+    assert np.array_equal(a.start, b.start) and np.array_equal(a.goal, b.goal) and a.hf.tobytes() == b.hf.tobytes()
+    assert len(a.nodes) == len(b.nodes) and all(np.array_equal(x, y) for x, y in zip(a.nodes, b.nodes))
+    assert all(x.tobytes() == y.tobytes() for x, y in zip(a.points, b.points))
+
+
+def test_a_planner_reused_across_batch_sizes_equals_a_fresh_one():
+    """Q = 3, then 5 (the buffers grow), then 2 (they stay) on one handle: each batch as a fresh planner plans it; the graph afterwards
+    is the last batch's, and a range beyond it is refused although the buffers are larger."""
+    from gpu_helpers import raises_invalid
+    hfs = terrain_windows(5, 8, 11)
+    starts = np.array([[1, 1], [1, 6], [2, 1], [6, 5], [1, 3]], np.int32)
+    goals = np.array([[6, 6], [6, 1], [5, 6], [1, 2], [6, 4]], np.int32)
+    P = planner(STAGE2, True)
+    for q in (slice(0, 3), slice(0, 5), slice(3, 5)):
+        r = P.plan(hfs[q], starts[q], goals[q], seed=13)
+        F = planner(STAGE2, True)
+        _same_plan(r, F.plan(hfs[q], starts[q], goals[q], seed=13))
+    assert np.isin(r.status, [pp.FOUND, pp.NO_PATH, pp.OVER_MAX_COST]).all()
+    for x, y in zip(P.graph(0, 2), F.graph(0, 2)):
+        assert x.tobytes() == y.tobytes()
+    u8 = C.POINTER(C.c_uint8)
+    nbr, cliff, jump = np.zeros((2, 8, 8), np.uint8), np.zeros((2, 8, 8), np.uint8), np.zeros((2, 8, 8, pp.JUMP_WORDS), np.uint32)
+    raises_invalid(lambda: P._lib.parc_pathplan_get_graph(P._h, 1, 2, nbr.ctypes.data_as(u8), cliff.ctypes.data_as(u8),
+                                                          jump.ctypes.data_as(C.POINTER(C.c_uint32))),
+                   "pathplan: the query range lies outside the last batch")
+    for x, y in zip(P.graph(1, 1), F.graph(1, 1)):
+        assert x.tobytes() == y.tobytes()
+
+
 def test_plan_terrains_first_success():
     hfs = terrain_windows(96, 16, 9)
     P = planner(STAGE2, True)
