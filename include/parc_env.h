@@ -764,6 +764,91 @@ int parc_tgen_generate(ParcTerrainGen *h, int32_t n, uint64_t seed, uint64_t fir
 /* Device time (hipEvents; waits for the last event), ms: the last parc_tgen_draw_plan, the last generate_with / generate (0 = not run). */
 int parc_tgen_kernel_times(ParcTerrainGen *h, float *ms2);
 
+/* Batched motion-terrain augmenter: scripts/run_simple_augment_motions.py:144-202 (window, heading, x / y scale,
+ * SubTerrain.pad, slice_terrain_around_motion, HEIGHT_SCALE / BOXES_ALONG_PATH) and stage 2's mirrored copies (parc_2_kin_gen.py:490-495:
+ * flip_motion_about_XZ_plane, flip_by_XZ_axis) for n variations at once.  Its own handle.  The source clips use the optimiser's layout
+ * (ParcMotionOptClips; the constraint fields are ignored).  Every random value comes from a plan of device arrays holding the derived
+ * values (not the uniforms); parc_maug_draw_plan fills one with Philox4x32-10 keyed by the seed, counter hi = 1 << 62 | variation index,
+ * u = top 24 bits / 2^24:
+ *   lo = 0      source clip (inverse CDF of the sample weights), start frame, heading
+ *   lo = 1      x scale, y scale, height scale (uniform on [min_h_scale, max_h_scale] minus the open bad_h_range), box count
+ *   lo = 2 + 2b frame, len x, len y, angle of box b;  lo = 3 + 2b: its height
+ * The variation index is first_variation + the position in the batch: a variation is the same bits alone or in any batch.  The variations
+ * of a run differ in frame count and slice size: the results stay in the handle, concatenated, until the next run, and
+ * parc_maug_get_result copies them out.  A slice may have at most PARC_MAUG_MAX_DIM cells a side (a refusal names the macro). */
+#define PARC_MAUG_MAX_DIM 128
+#define PARC_MAUG_MAX_BOXES 16
+#define PARC_MAUG_BOX_FLOATS 4                   /* len x, len y (cells), angle, height; the centre is the box's frame */
+#define PARC_MAUG_HEIGHT_SCALE 0                 /* TerrainAugmentationType (run_simple_augment_motions.py:19-22) */
+#define PARC_MAUG_BOXES_ALONG_PATH 1
+#define PARC_MAUG_NONE 2
+#define PARC_MAUG_STATUS_CLAMPED 1               /* parc_maug_plan_status: a plan index lay outside its range and was clamped */
+#define PARC_MAUG_STATUS_NOT_FINITE 2            /* a variation's bounds were NaN or infinite: its slice is 1 x 1 */
+typedef struct ParcMotionAug ParcMotionAug;
+typedef struct {
+    uint32_t struct_size;                    /* sizeof(ParcMotionAugParams) */
+    int32_t device;
+    ParcCharModel model;                     /* the tables parc_env_create takes (fk_paths unused) */
+    int32_t joint_swap[PARC_MAX_BODIES];     /* the left / right partner of every joint (by name), itself when it has none */
+    int32_t contact_swap[PARC_MAX_BODIES];   /* the same for the columns of the contacts array */
+    int32_t mode;                            /* PARC_MAUG_HEIGHT_SCALE / BOXES_ALONG_PATH / NONE */
+    int32_t terrain_padding_size;            /* cells of SubTerrain.pad on every side (0: none) */
+    int32_t slice_terrain;                   /* 0: the (padded) terrain and the frames keep their place (what the mirrored copies use) */
+    int32_t sample_weight_by_length;         /* parc_maug_draw_plan: clips weighted by frames / fps, else uniformly */
+    float min_heading_angle, max_heading_angle;   /* degrees */
+    float x_scale[2], y_scale[2];
+    float min_h_scale, max_h_scale, bad_h_range[2];
+    int32_t min_num_boxes, max_num_boxes;
+    float min_len, max_len, min_angle, max_angle, min_h, max_h;
+} ParcMotionAugParams;
+typedef struct {                             /* with ParcMotionOptClips */
+    const float *hf_maxmin_host;             /* [cells][2] (max, min), or NULL: no hf_maxmin output */
+    const int32_t *fps_host;                 /* [num_clips] */
+    const int32_t *max_frames_host;          /* [num_clips] int(round(fps * max_motion_len)): the longest window parc_maug_draw_plan cuts */
+} ParcMotionAugClipInfo;
+typedef struct {                             /* device arrays of n variations; every array is required */
+    int32_t n;
+    const int32_t *src_clip, *start_frame, *num_frames;   /* [n] */
+    const float *heading;                    /* [n] radians */
+    const float *scale;                      /* [n][2] x, y */
+    const int32_t *mirror;                   /* [n] 0 / 1 */
+    const float *height_scale;               /* [n] (HEIGHT_SCALE) */
+    const int32_t *num_boxes;                /* [n] <= PARC_MAUG_MAX_BOXES (BOXES_ALONG_PATH) */
+    const int32_t *box_frame;                /* [n][PARC_MAUG_MAX_BOXES] frame of the window under which box b sits */
+    const float *boxes;                      /* [n][PARC_MAUG_MAX_BOXES][PARC_MAUG_BOX_FLOATS] */
+} ParcMotionAugPlan;
+typedef struct { int32_t n, has_maxmin; int64_t total_frames, total_cells; } ParcMotionAugSizes;
+typedef struct {                             /* device arrays owned by the caller; a NULL one is not copied */
+    int64_t *frame_off, *cell_off;           /* [n + 1] */
+    int32_t *src_clip;                       /* [n] */
+    int32_t *hf_dims;                        /* [n][2] */
+    float *hf_geom;                          /* [n][4] min_x, min_y, dx, dy */
+    float *canon_z;                          /* [n] the height that was under frame 0 */
+    float *root_pos, *root_rot, *joint_rot, *contacts;   /* [F][3], [F][4] xyzw, [F][B-1][4], [F][B] */
+    float *hf;                               /* [cells], x-major per variation */
+    float *hf_maxmin;                        /* [cells][2] */
+} ParcMotionAugOutputs;
+int parc_maug_create(const ParcMotionAugParams *p, ParcMotionAug **out);
+void parc_maug_destroy(ParcMotionAug *h);
+/* Validates and uploads the source clips (as parc_msamp_set_clips: an invalid batch leaves the loaded one in place). */
+int parc_maug_set_clips(ParcMotionAug *h, const ParcMotionOptClips *c, const ParcMotionAugClipInfo *info);
+/* Fills the (writable, caller-owned) arrays of `plan` for plan->n variations from (seed, first_variation + position); every
+ * variation gets the mirror flag `mirror`.  No host sync.  The struct is the readers' (const members); this call alone writes through them. */
+int parc_maug_draw_plan(ParcMotionAug *h, uint64_t seed, uint64_t first_variation, int32_t mirror, const ParcMotionAugPlan *plan, void *stream);
+/* The deterministic path.  Synchronises twice on small copies (the frame total, the slice dims).  With validate != 0 a pass over the plan
+ * runs first: a non-finite or out-of-range entry is PARC_ERR_INVALID naming the field, and nothing is launched.  Without it a bad index is
+ * clamped into its range (parc_maug_plan_status reports that) and a NaN or infinite heading or scale stays inside its own variation (a
+ * 1 x 1 slice); a finite scale so large that the slice passes PARC_MAUG_MAX_DIM is that refusal, and refuses the run. */
+int parc_maug_augment_with(ParcMotionAug *h, const ParcMotionAugPlan *plan, int32_t validate, void *stream, ParcMotionAugSizes *sizes);
+/* draw_plan + augment_with without the plan in memory: the same bits as the two calls. */
+int parc_maug_augment(ParcMotionAug *h, int32_t n, uint64_t seed, uint64_t first_variation, int32_t mirror, void *stream, ParcMotionAugSizes *sizes);
+/* Copies the last run's results (device to device, on `stream`) into the arrays of `out`, sized by that run's ParcMotionAugSizes. */
+int parc_maug_get_result(ParcMotionAug *h, const ParcMotionAugOutputs *out, void *stream);
+/* Synchronises; the OR of PARC_MAUG_STATUS_* since the last call, then clears it. */
+int parc_maug_plan_status(ParcMotionAug *h, void *stream, int32_t *status);
+/* Device time (hipEvents; waits for the last event), ms: the last draw_plan, then layout + scan, frames + scan, terrain of the last run. */
+int parc_maug_kernel_times(ParcMotionAug *h, float *ms4);
+
 #ifdef __cplusplus
 }
 #endif

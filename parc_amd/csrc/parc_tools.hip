@@ -6,3 +6,4 @@
 #include "parc_motion_sampler.hpp"   // parc_msamp_*: the generator's motion-window sampler
 #include "parc_path_planner.hpp"     // parc_pathplan_*: stage 2's batched A* terrain path planner
 #include "parc_terrain_gen.hpp"      // parc_tgen_*: stage 2's BOXES / PATHS / STAIRS terrain generators, batched
+#include "parc_motion_aug.hpp"       // parc_maug_*: stage 0's motion-terrain augmenter and the mirrored copies, batched

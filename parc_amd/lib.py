@@ -181,6 +181,44 @@ class ParcTerrainGenPlan(C.Structure):
     _fields_ = [("n", C.c_int32)] + [(n, C.c_void_p) for n in TGEN_PLAN_FIELDS]
 
 
+MAUG_MAX_DIM, MAUG_MAX_BOXES, MAUG_BOX_FLOATS = 128, 16, 4                                         # PARC_MAUG_*
+MAUG_MODES = ("HEIGHT_SCALE", "BOXES_ALONG_PATH", "NONE")                                         # PARC_MAUG_HEIGHT_SCALE / BOXES_ALONG_PATH / NONE
+MAUG_STATUS_CLAMPED, MAUG_STATUS_NOT_FINITE = 1, 2
+# the plan's arrays, in struct order: (name, "i" / "f", per-variation shape)
+MAUG_PLAN_FIELDS = [("src_clip", "i", ()), ("start_frame", "i", ()), ("num_frames", "i", ()), ("heading", "f", ()), ("scale", "f", (2,)),
+                    ("mirror", "i", ()), ("height_scale", "f", ()), ("num_boxes", "i", ()), ("box_frame", "i", (MAUG_MAX_BOXES,)),
+                    ("boxes", "f", (MAUG_MAX_BOXES, MAUG_BOX_FLOATS))]
+MAUG_OUTPUT_FIELDS = ["frame_off", "cell_off", "src_clip", "hf_dims", "hf_geom", "canon_z", "root_pos", "root_rot", "joint_rot", "contacts",
+                      "hf", "hf_maxmin"]
+
+
+class ParcMotionAugParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("model", ParcCharModel),
+                ("joint_swap", C.c_int32 * MAX_BODIES), ("contact_swap", C.c_int32 * MAX_BODIES),
+                ("mode", C.c_int32), ("terrain_padding_size", C.c_int32), ("slice_terrain", C.c_int32), ("sample_weight_by_length", C.c_int32),
+                ("min_heading_angle", C.c_float), ("max_heading_angle", C.c_float), ("x_scale", C.c_float * 2), ("y_scale", C.c_float * 2),
+                ("min_h_scale", C.c_float), ("max_h_scale", C.c_float), ("bad_h_range", C.c_float * 2),
+                ("min_num_boxes", C.c_int32), ("max_num_boxes", C.c_int32),
+                ("min_len", C.c_float), ("max_len", C.c_float), ("min_angle", C.c_float), ("max_angle", C.c_float),
+                ("min_h", C.c_float), ("max_h", C.c_float)]
+
+
+class ParcMotionAugClipInfo(C.Structure):
+    _fields_ = [("hf_maxmin_host", f32p), ("fps_host", i32p), ("max_frames_host", i32p)]
+
+
+class ParcMotionAugPlan(C.Structure):
+    _fields_ = [("n", C.c_int32)] + [(n, C.c_void_p) for n, _, _ in MAUG_PLAN_FIELDS]
+
+
+class ParcMotionAugSizes(C.Structure):
+    _fields_ = [("n", C.c_int32), ("has_maxmin", C.c_int32), ("total_frames", C.c_int64), ("total_cells", C.c_int64)]
+
+
+class ParcMotionAugOutputs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in MAUG_OUTPUT_FIELDS]
+
+
 BUFFER_FIELDS = [
     ("char_root_pos", "f"), ("char_root_rot", "f"), ("char_root_vel", "f"), ("char_root_ang_vel", "f"),
     ("char_dof_pos", "f"), ("char_dof_vel", "f"), ("char_body_pos", "f"), ("contact_forces", "f"),
@@ -318,6 +356,16 @@ def load():
     lib.parc_tgen_generate_with.argtypes = [vp, C.POINTER(ParcTerrainGenPlan), vp, C.c_int32, vp]
     lib.parc_tgen_generate.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, vp, vp]
     lib.parc_tgen_kernel_times.argtypes = [vp, f32p]
+    lib.parc_maug_create.argtypes = [C.POINTER(ParcMotionAugParams), C.POINTER(vp)]
+    lib.parc_maug_destroy.argtypes = [vp]
+    lib.parc_maug_destroy.restype = None
+    lib.parc_maug_set_clips.argtypes = [vp, C.POINTER(ParcMotionOptClips), C.POINTER(ParcMotionAugClipInfo)]
+    lib.parc_maug_draw_plan.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_int32, C.POINTER(ParcMotionAugPlan), vp]
+    lib.parc_maug_augment_with.argtypes = [vp, C.POINTER(ParcMotionAugPlan), C.c_int32, vp, C.POINTER(ParcMotionAugSizes)]
+    lib.parc_maug_augment.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, vp, C.POINTER(ParcMotionAugSizes)]
+    lib.parc_maug_get_result.argtypes = [vp, C.POINTER(ParcMotionAugOutputs), vp]
+    lib.parc_maug_plan_status.argtypes = [vp, vp, i32p]
+    lib.parc_maug_kernel_times.argtypes = [vp, f32p]
     _lib = lib
     return lib
 
@@ -340,6 +388,8 @@ EXPORTED_SYMBOLS = [
     "parc_msamp_sample", "parc_msamp_enumerate", "parc_msamp_plan_status", "parc_msamp_kernel_times",
     "parc_pathplan_create", "parc_pathplan_destroy", "parc_pathplan_run", "parc_pathplan_get_graph", "parc_pathplan_kernel_times",
     "parc_tgen_create", "parc_tgen_destroy", "parc_tgen_draw_plan", "parc_tgen_generate_with", "parc_tgen_generate", "parc_tgen_kernel_times",
+    "parc_maug_create", "parc_maug_destroy", "parc_maug_set_clips", "parc_maug_draw_plan", "parc_maug_augment_with", "parc_maug_augment",
+    "parc_maug_get_result", "parc_maug_plan_status", "parc_maug_kernel_times",
 ]
 
 # parc_test_quat_op selectors (include/parc_env.h)

@@ -9,7 +9,10 @@ Semantics of PARC's ``parc_2_kin_gen.py`` optimisation stage: optional body cons
 clip's terrain, constraints in ``misc_data`` as plain arrays) and ``log/log_<name>_opt.txt`` with the loss terms every
 ``log_every`` iterations.  With ``hf_extras: true`` (or ``--hf_extras``) the files also carry stage 2's
 ``compute_hf_extra_vals`` of the optimised frames: ``misc_data["hf_mask_inds"]`` and the recomputed ``hf_maxmin`` (default off: the
-source bounds are kept).
+source bounds are kept).  With ``save_flipped: true`` (or ``--save_flipped``) the mirrored copy of every optimised clip
+(``parc_2_kin_gen.py:490-495``) is written beside it as ``flipped/<name>_opt_flipped.pkl``; the copy carries the motion and the terrain only:
+``hf_mask_inds`` and the body constraints of ``auto_compute_body_constraints`` (``opt:body_constraints``) are not mirrored into it
+(recompute the former with ``scripts/preprocess_motions.py`` on the flipped files).
 """
 import argparse
 import os
@@ -40,6 +43,7 @@ def load_config(path):
     cfg.setdefault("auto_compute_body_constraints", False)
     cfg.setdefault("log_every", 100)
     cfg.setdefault("hf_extras", False)
+    cfg.setdefault("save_flipped", False)
     if int(cfg["frame_stride"]) < 1 or int(cfg["num_iters"]) < 0:
         raise ValueError("frame_stride must be >= 1 and num_iters >= 0")
     return cfg
@@ -103,6 +107,16 @@ def run(cfg):
         p = os.path.join(out_dir, c.name + "_opt.pkl")
         write_clip(p, fr, c, c, ex)
         paths.append(p)
+    if cfg["save_flipped"]:
+        from parc_amd.motion_aug import mirror_clips
+        opt_clips = [mo.OptClip(fr["root_pos"], fr["root_rot"], fr["joint_rot"], fr["contacts"], c.hf, c.min_point, c.dx, c.fps, c.name + "_opt",
+                                hf_maxmin=c.hf_maxmin if ex is None else ex["hf_maxmin"]) for c, fr, ex in zip(clips, frames, extras)]
+        os.makedirs(os.path.join(out_dir, "flipped"), exist_ok=True)
+        for fc in mirror_clips(opt_clips, resolve(cfg["char_model"]), cfg["device"]):
+            p = os.path.join(out_dir, "flipped", fc.name + ".pkl")
+            write_clip(p, dict(root_pos=fc.root_pos, root_rot=fc.root_rot, joint_rot=fc.joint_rot, contacts=fc.contacts), fc, mo.OptClip(
+                fc.root_pos, fc.root_rot, fc.joint_rot, fc.contacts, fc.hf, fc.min_point, fc.dx))
+            paths.append(p)
     print(f"optimised {len(clips)} clips x {cfg['num_iters']} iterations in {time.time() - t0:.2f} s")
     return paths
 
@@ -111,10 +125,13 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--config", required=True)
     ap.add_argument("--hf_extras", action="store_true", help="write hf_mask_inds and recomputed hf_maxmin (config key hf_extras)")
+    ap.add_argument("--save_flipped", action="store_true", help="also write flipped/<name>_opt_flipped.pkl, the mirrored copies (config key save_flipped)")
     args = ap.parse_args(argv)
     cfg = load_config(args.config)
     if args.hf_extras:
         cfg["hf_extras"] = True
+    if args.save_flipped:
+        cfg["save_flipped"] = True
     return run(cfg)
 
 
