@@ -31,7 +31,7 @@
 #include "parc_common.hpp"    // what this unit shares with parc_tools.hip: g_err / fail / HIPCHK, MotionMeta, frame_blend, philox4
 #include "parc_math.hpp"
 #include "parc_rowmap.hpp"    // row phase of k_env_post: (pass, lane) -> (row, slot)
-#include "parc_lanetab.hpp"   // prefetch phase of k_env_post: what depends on the lane and on the handle's constants only
+#include "parc_lanetab.hpp"   // prefetch phase, heading pass and contact block of k_env_post: what depends on the lane and on the handle's constants only
 #include "parc_dynamics.hpp"
 #include "parc_dynamics_coop.hpp"
 #include "parc_dynamics_wave.hpp"
@@ -69,6 +69,7 @@ struct DevTables { // global memory; `h` is staged into LDS, the rest is read on
     float contact_w[16];
     float pose_term_dist[16];
     ParcLaneEntry lane[64];  // parc_lanetab.hpp: refilled when the tile radius changes (parc_env_load_terrain)
+    ParcHrotEntry hrot[64];  // parc_lanetab.hpp: the lane's item of the heading pass and its part in the contact / velocity block
 };
 
 struct StepParams {
@@ -253,14 +254,17 @@ __global__ __launch_bounds__(256, 5) void k_env_post(const StepParams P, const i
     extern __shared__ __align__(16) float s_obs_all[]; // per wave: staged observation prefix [0, off_tarc) (+ the body rotations of the tracking error)
     __shared__ int s_tab_raw[HIER_STAGED_WORDS];
     const HierTables &s_tab = *reinterpret_cast<const HierTables *>(s_tab_raw); // only the staged members are touched through it
-    __shared__ float4 s_q_all[ENVS_PER_BLOCK][8][16];   // row r: quats 0..14 (0 = root), slot 15 = root position.  Target rows (r >= 2) hold lr (x) q for the joints
+    // One block per wave, so that the heading pass addresses any of its float4 with one offset of its table (parc_lanetab.hpp, PARC_HROT_*_F4):
+    //   s_q  [8][16]  row r: quats 0..14 (0 = root), slot 15 = root position.  Target rows (r >= 2) hold lr (x) q for the joints
+    //   s_fk [80]     FK positions: rows 0,1 all bodies [r*16+b]; target rows key slots [32+(r-2)*8+k]
+    //   s_rv [4]      root velocity and root angular velocity of the character as loaded, a zero vector, one spare
+    __shared__ float4 s_blk_all[ENVS_PER_BLOCK][PARC_HROT_BLOCK_F4];
     __shared__ float4 s_lq_all[ENVS_PER_BLOCK][2][16];  // rows 0, 1: lr (x) q of the joints (s_q keeps their raw quaternions for the reward)
-    __shared__ float4 s_fk_all[ENVS_PER_BLOCK][80];     // FK positions: rows 0,1 all bodies [r*16+b]; target rows key slots [32+(r-2)*8+k]
-    // (LDS budget: 864 B of tables + 4 x (4 416 B static + 3 072 B staged row) = 30.1 KB per workgroup: 5 workgroups = 5 waves per SIMD
+    // (LDS budget: 864 B of tables + 4 x (4 432 B static + 3 072 B staged row) = 30.2 KB per workgroup: 5 workgroups = 5 waves per SIMD
     // on a CU's 160 KB)
     __shared__ float s_cdofv_all[ENVS_PER_BLOCK][PARC_MAX_DOFS];
     __shared__ float4 s_refvel_all[ENVS_PER_BLOCK][12]; // record float4 #20..: root_vel, root_ang_vel, dof_vel
-    __shared__ float s_refct_all[ENVS_PER_BLOCK][16];
+    __shared__ __align__(16) float s_refct_all[ENVS_PER_BLOCK][16];
     __shared__ float s_cfn_all[ENVS_PER_BLOCK][16];
     __shared__ float s_sc_all[ENVS_PER_BLOCK][16];      // per-env scalars handed to the wave that forms the rewards (MODE_STEP)
 #ifdef PARC_STAMPS
@@ -273,9 +277,10 @@ __global__ __launch_bounds__(256, 5) void k_env_post(const StepParams P, const i
     const bool TAROBS = !OBSVAR || P.obs_tar != 0;       // enable_tar_obs (ig_parkour_env.py:83): the look-ahead target block exists
     const bool CONTACTOBS = !OBSVAR || P.obs_contact != 0; // use_contact_info (:72): contact blocks of the observation, contact term of the reward
     float *s_obs = s_obs_all + (size_t)wv * P.lds_wave_floats;
-    float4 (*s_q)[16] = s_q_all[wv];
+    float4 (*s_q)[16] = reinterpret_cast<float4 (*)[16]>(s_blk_all[wv] + PARC_HROT_Q_F4);
     float4 (*s_lq)[16] = s_lq_all[wv];
-    float4 *s_fk = s_fk_all[wv];
+    float4 *s_fk = s_blk_all[wv] + PARC_HROT_FK_F4;
+    float4 *s_rv = s_blk_all[wv] + PARC_HROT_RV_F4;
     float4 *s_cbp = s_lq[0];        // simulator rigid-body positions of the character: written once the FK chains are through with s_lq
     float *s_cdofv = s_cdofv_all[wv];
     float4 *s_refvel = s_refvel_all[wv];
@@ -384,14 +389,13 @@ __global__ __launch_bounds__(256, 5) void k_env_post(const StepParams P, const i
     }
     // (d) contacts of the 1+S samples (lanes < 4(1+S)) / velocity block of sample 0 (lanes 32..)
     // (every other lane: contact slot 0 of sample 0)
-    const int nvel = 2 + (D + 3) / 4;
     const int src4c = (int)parc_lt_src4(lt, 2);
     const float cblend = __int_as_float(__builtin_amdgcn_ds_bpermute(src4c, __float_as_int(myb.b)));
     const int b2i0 = __builtin_amdgcn_ds_bpermute(src4c, myb.i0), b2i1 = min(b2i0 + 1, last_frame);
     const float4 cA = P.records[(size_t)b2i0 * REC_F4 + parc_lt_cv_slot0(lt)]; // velocities come from frame idx0 un-interpolated (:103-109)
     const float4 cB = P.records[(size_t)b2i1 * REC_F4 + parc_lt_cv_slot1(lt)];
     // (e) terrain tile cells: (a, bq) of the lane's five cells from the table, (0, 0) where the tile ends (or there is none: tr < 0)
-    static_assert(64 * PARC_LANETAB_TILE_CELLS == TILE_MAX_CELLS && TILE_MAX_CELLS * sizeof(float) == sizeof(s_fk_all[0]), "the five tile stores of a lane stay inside s_fk");
+    static_assert(64 * PARC_LANETAB_TILE_CELLS == TILE_MAX_CELLS && TILE_MAX_CELLS * sizeof(float) == (PARC_HROT_RV_F4 - PARC_HROT_FK_F4) * sizeof(float4), "the five tile stores of a lane stay inside s_fk");
     const int tr = P.tile_r, TW = 2 * tr + 1;
     // (the origin is kept within +-2^22 cells so that it and the tile bounds are exact as floats: the ray loop clamps in float)
     const int ox = min(max(cell_index(gx, P.min_x, P.dx) - tr, -(1 << 22)), 1 << 22), oy = min(max(cell_index(gy, P.min_y, P.dy) - tr, -(1 << 22)), 1 << 22);
@@ -412,11 +416,11 @@ __global__ __launch_bounds__(256, 5) void k_env_post(const StepParams P, const i
         s_obs[P.off_dofvel + lane] = dofv;
     }
     if (OBSVAR && oc && lane == 29) s_obs[0] = root_pos.z; // root_height_obs (ig_char_env.py:620-622)
-    if (role == PARC_LT_ROLE_ROOT_VEL || role == PARC_LT_ROLE_ROOT_ANG_VEL) { // root velocities in the heading frame (ig_char_env.py:593-597)
-        const V3 r = GLOBALOBS ? mk3(aux0, aux1, aux2) : quat_rotate(hinv, mk3(aux0, aux1, aux2));
-        const int o = oc + (role == PARC_LT_ROLE_ROOT_VEL ? 6 : 9);
-        s_obs[o + 0] = r.x; s_obs[o + 1] = r.y; s_obs[o + 2] = r.z;
-    }
+    // root velocities as loaded (roles 1, 2 -> s_rv[0], s_rv[1]): the heading pass rotates them, the reward reads them; lane 29 lays down
+    // the zero vector that the pass subtracts from them
+    static_assert(PARC_LT_ROLE_ROOT_VEL == 1 && PARC_LT_ROLE_ROOT_ANG_VEL == 2 && PARC_HROT_RV_ZERO == 2, "s_rv slots");
+    if (role == PARC_LT_ROLE_ROOT_VEL || role == PARC_LT_ROLE_ROOT_ANG_VEL) s_rv[role - 1] = make_float4(aux0, aux1, aux2, 0.f);
+    if (lane == 29) s_rv[PARC_HROT_RV_ZERO] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (role == PARC_LT_ROLE_FORCE) { // contact flags + clamped force norms (ig_parkour_env.py:655-662, mgdm_dm_util.py:505-508)
         const float n = norm3(mk3(aux0, aux1, aux2));
         if (CONTACTOBS) orow[P.off_cc + (lane - 32)] = n > 1e-5f ? 1.f : 0.f;
@@ -496,6 +500,13 @@ __global__ __launch_bounds__(256, 5) void k_env_post(const StepParams P, const i
     // position lerp with its loop and terrain offsets, the heading products) and of rows 0 and 1, whose joints all sit in pass A; pass B
     // is compiled without any of it: joint items of target rows only.
     static_assert(2 * (PARC_MAX_BODIES - 2) <= PARC_ROWMAP_JOINTS_A, "the joints of rows 0 and 1 must fit into pass A");
+    // the lane's item of the heading pass and its part in the contact / velocity block (parc_lanetab.hpp): loaded here, behind the ray loop;
+    // word 2 is consumed after the row passes, words 0 and 1 once the FK chains are through
+    unsigned hr[3];
+    {
+        const unsigned *h0 = T->hrot[lane].w; // one 12-byte load per lane
+        hr[0] = h0[0]; hr[1] = h0[1]; hr[2] = h0[2];
+    }
     auto row_pass = [&](auto root_tag, const int itm, const float4 A, const float4 Bv, const float bb) {
         constexpr bool ROOT = decltype(root_tag)::value;
         if (itm < 0) return;
@@ -550,34 +561,32 @@ __global__ __launch_bounds__(256, 5) void k_env_post(const StepParams P, const i
                 const int o = row0 ? oc + (is_rot ? 0 : 12 + 6 * (i - 1)) : base + 3 + 6 * i;
 #pragma unroll
                 for (int c = 0; c < 6; ++c) s_obs[o + c] = tn[c];
-            } else if (!row0) {
-                const V3 rpd = mk3(res.x - root_pos.x, res.y - root_pos.y, res.z - root_pos.z);
-                const V3 rpo = GLOBALOBS ? rpd : quat_rotate(hinv, rpd);
-                s_obs[base + 0] = rpo.x; s_obs[base + 1] = rpo.y; s_obs[base + 2] = rpo.z;
-            }
+            } // (a target row's root offset: the heading pass, from s_q[r][15])
         }
     };
     row_pass(std::true_type(), item[0], fA[0], fB[0], bl[0].b);
     row_pass(std::false_type(), item[1], fA[1], fB[1], bl[1].b);
     // ---- contacts of the 1+S samples and the velocity block of sample 0 ---------------------------------
-    if (lane < 4 * (1 + S)) {
-        const int s = lane >> 2, c = lane & 3;
+    // (which lane does what, how many of its four contacts are bodies and where they go: word 2 of the lane's heading-table entry)
+    const unsigned cvk = parc_hr_cv_kind(hr);
+    if (cvk == PARC_HR_CV_REF || cvk == PARC_HR_CV_TAR) {
         const float b = cblend, a = 1.0f - b;
         const float v[4] = {a * cA.x + b * cB.x, a * cA.y + b * cB.y, a * cA.z + b * cB.z, a * cA.w + b * cB.w};
+        const int nk = (int)parc_hr_cv_n(hr);
+        if (cvk == PARC_HR_CV_REF) { // all four at once: s_refct has 16 slots, and one past the last body has no reader
+            const int c = (int)parc_hr_cv_idx(hr);
+            *reinterpret_cast<float4 *>(s_refct + 4 * c) = make_float4(v[0], v[1], v[2], v[3]);
+            if (MIRROR && P.buf.ref_contacts) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int bd = 4 * c + k;
-            if (bd < B) {
-                if (s == 0) {
-                    s_refct[bd] = v[k];
-                    if (MIRROR && P.buf.ref_contacts) P.buf.ref_contacts[(size_t)e * B + bd] = v[k];
-                } else if (TAROBS && CONTACTOBS) {
-                    orow[P.off_tarc + (s - 1) * B + bd] = v[k];
-                }
+                for (int k = 0; k < 4; ++k) if (k < nk) P.buf.ref_contacts[(size_t)e * B + 4 * c + k] = v[k];
             }
+        } else {
+            float *o = reinterpret_cast<float *>(reinterpret_cast<char *>(orow) + parc_hr_cv_off(hr));
+#pragma unroll
+            for (int k = 0; k < 4; ++k) if (k < nk) o[k] = v[k];
         }
-    } else if (lane >= 32 && lane < 32 + nvel) {
-        const int c = lane - 32;
+    } else if (cvk == PARC_HR_CV_VEL) {
+        const int c = (int)parc_hr_cv_idx(hr);
         s_refvel[c] = cA;
         if (MIRROR && c == 0 && P.buf.ref_root_vel) { float *o = P.buf.ref_root_vel + 3 * (size_t)e; o[0] = cA.x; o[1] = cA.y; o[2] = cA.z; }
         if (MIRROR && c == 1 && P.buf.ref_root_ang_vel) { float *o = P.buf.ref_root_ang_vel + 3 * (size_t)e; o[0] = cA.x; o[1] = cA.y; o[2] = cA.z; }
@@ -628,29 +637,27 @@ __global__ __launch_bounds__(256, 5) void k_env_post(const StepParams P, const i
     if (lane < B) s_cbp[lane] = P.body_pos_from_fk ? s_fk[lane] : make_float4(bpx, bpy, bpz, 0.f);
     STAMP(4);
 
-    // ================= key-body observations (ig_char_env.py:603-617, mgdm_dm_util.py:415-440) =================
-    if (lane < 8 * (1 + S)) {
-        const int row = lane >> 3, kk = lane & 7; // row 0 = char, 1.. = target rows 2..
-        if (kk < K) {
-            if (row == 0) {
-                const float4 kp = s_fk[s_tab.key_ids[kk]];
-                const V3 rd = mk3(kp.x - root_pos.x, kp.y - root_pos.y, kp.z - root_pos.z);
-                const V3 rl = GLOBALOBS ? rd : quat_rotate(hinv, rd);
-                const int o = P.off_key + 3 * kk;
-                s_obs[o] = rl.x; s_obs[o + 1] = rl.y; s_obs[o + 2] = rl.z;
-            } else if (TAROBS) {
-                const int r = row + 1;
-                const float4 kp = s_fk[32 + (r - 2) * 8 + s_tab.key_slot[s_tab.key_ids[kk]]], trp = s_q[r][15];
-                const V3 rd = mk3(kp.x - trp.x, kp.y - trp.y, kp.z - trp.z);
-                const int tb = P.off_tar + (r - 2) * P.tar_w, o = tb + 3 + 6 * B + 3 * kk; // [tb, tb + 3): the row's root offset, staged by the row phase
-                if (GLOBALOBS) { // mgdm_dm_util.py:417: global key offsets are not shifted by the root offset
-                    s_obs[o] = rd.x; s_obs[o + 1] = rd.y; s_obs[o + 2] = rd.z;
-                } else {
-                    const V3 rl = quat_rotate(hinv, rd);
-                    s_obs[o] = rl.x + s_obs[tb]; s_obs[o + 1] = rl.y + s_obs[tb + 1]; s_obs[o + 2] = rl.z + s_obs[tb + 2];
-                }
-            }
+    // ================= heading pass: every 3-vector of the observation that turns into the heading frame, one per lane =================
+    // The targets' root offsets (mgdm_dm_util.py:405-411), the root velocities (ig_char_env.py:593-597) and the key-body offsets of the
+    // character and of the targets (ig_char_env.py:603-617, mgdm_dm_util.py:415-440): (source - subtrahend) of the wave's LDS block, rotated by
+    // the inverse heading unless the observation is global, to the lane's place in the staged row.  Source, subtrahend and destination are
+    // the lane's entry of the table; a target's key offset adds the rotated root offset of its row, which another lane of this pass holds
+    // (a lane shuffle; never under global_obs, mgdm_dm_util.py:417).
+    if (parc_hr_item(hr)) {
+        const char *blk = reinterpret_cast<const char *>(s_q);
+        const float *sp = reinterpret_cast<const float *>(blk + parc_hr_src(hr)), *sb = reinterpret_cast<const float *>(blk + parc_hr_sub(hr));
+        const V3 rd = mk3(sp[0] - sb[0], sp[1] - sb[1], sp[2] - sb[2]);
+        V3 rl = rd;
+        if (!GLOBALOBS) {
+            rl = quat_rotate(hinv, rd);
+            const int a4 = (int)parc_hr_add4(hr); // every lane with an item shuffles (a lane that adds nothing reads lane 0, which has one)
+            const float ax = __int_as_float(__builtin_amdgcn_ds_bpermute(a4, __float_as_int(rl.x)));
+            const float ay = __int_as_float(__builtin_amdgcn_ds_bpermute(a4, __float_as_int(rl.y)));
+            const float az = __int_as_float(__builtin_amdgcn_ds_bpermute(a4, __float_as_int(rl.z)));
+            if (parc_hr_adds(hr)) rl = mk3(rl.x + ax, rl.y + ay, rl.z + az);
         }
+        float *o = reinterpret_cast<float *>(reinterpret_cast<char *>(s_obs) + parc_hr_dst(hr));
+        o[0] = rl.x; o[1] = rl.y; o[2] = rl.z;
     }
     STAMP(5);
 
@@ -666,9 +673,7 @@ __global__ __launch_bounds__(256, 5) void k_env_post(const StepParams P, const i
             if (P.fall_mask != 0u && lane >= 32 && lane < 32 + B && !((P.fall_mask >> (lane - 32)) & 1u))
                 fc = fabsf(aux0) > 0.1f || fabsf(aux1) > 0.1f || fabsf(aux2) > 0.1f;
             const bool fcany = __ballot(fc) != 0ull;
-            if (lane == 30) { sc[5] = aux0; sc[6] = aux1; sc[7] = aux2; }
-            if (lane == 31) { sc[8] = aux0; sc[9] = aux1; sc[10] = aux2; }
-            if (lane == 0) {
+            if (lane == 0) { // (the root velocities are in s_rv since the prefetch phase)
                 sc[0] = time; sc[1] = mt; sc[2] = __int_as_float(ts); sc[3] = meta.length; sc[4] = __int_as_float(meta.loop);
                 sc[11] = fcany ? 1.f : 0.f; sc[12] = eox; sc[13] = eoy; sc[14] = __int_as_float(e);
             }
@@ -681,8 +686,8 @@ __global__ __launch_bounds__(256, 5) void k_env_post(const StepParams P, const i
             const int j = lane >> 4, i = lane & 15, rowbase = lane & 48;
             const bool valid = j < nact;
             const int jj = valid ? j : 0;
-            const float4 (*q)[16] = s_q_all[jj];
-            const float4 *fk = s_fk_all[jj];
+            const float4 (*q)[16] = reinterpret_cast<const float4 (*)[16]>(s_blk_all[jj] + PARC_HROT_Q_F4);
+            const float4 *fk = s_blk_all[jj] + PARC_HROT_FK_F4;
             const float4 *cbp = s_lq_all[jj][0];
             const float *scj = s_sc_all[jj];
             const float4 rp4 = q[0][15], trp = q[1][15];
@@ -775,19 +780,20 @@ __global__ __launch_bounds__(256, 5) void k_env_post(const StepParams P, const i
             if (!P.track_root_h) rdz = 0.f;
             const float root_pos_err = rdx * rdx + rdy * rdy + rdz * rdz;
             const float4 tv = s_refvel_all[jj][0], tav = s_refvel_all[jj][1];
+            const float4 cv = s_blk_all[jj][PARC_HROT_RV_F4 + 0], cav = s_blk_all[jj][PARC_HROT_RV_F4 + 1]; // the character's root velocities
             const float rre = root_rot_angle * root_rot_angle;
             float rve, rave;
             if (LOCALROOT) {
                 const V3 tv3 = quat_rotate(hinv_r, mk3(tv.x, tv.y, tv.z)), tav3 = quat_rotate(hinv_r, mk3(tav.x, tav.y, tav.z));
-                const V3 rv3 = quat_rotate(hinv_c, mk3(scj[5], scj[6], scj[7])), rav3 = quat_rotate(hinv_c, mk3(scj[8], scj[9], scj[10]));
+                const V3 rv3 = quat_rotate(hinv_c, mk3(cv.x, cv.y, cv.z)), rav3 = quat_rotate(hinv_c, mk3(cav.x, cav.y, cav.z));
                 float d0 = tv3.x - rv3.x, d1 = tv3.y - rv3.y, d2 = tv3.z - rv3.z;
                 rve = d0 * d0 + d1 * d1 + d2 * d2;
                 d0 = tav3.x - rav3.x; d1 = tav3.y - rav3.y; d2 = tav3.z - rav3.z;
                 rave = d0 * d0 + d1 * d1 + d2 * d2;
             } else {
-                float d0 = tv.x - scj[5], d1 = tv.y - scj[6], d2 = tv.z - scj[7];
+                float d0 = tv.x - cv.x, d1 = tv.y - cv.y, d2 = tv.z - cv.z;
                 rve = d0 * d0 + d1 * d1 + d2 * d2;
-                d0 = tav.x - scj[8]; d1 = tav.y - scj[9]; d2 = tav.z - scj[10];
+                d0 = tav.x - cav.x; d1 = tav.y - cav.y; d2 = tav.z - cav.z;
                 rave = d0 * d0 + d1 * d1 + d2 * d2;
             }
             float earg = -0.25f * pose_err;
@@ -1731,6 +1737,8 @@ extern "C" int parc_env_create(const ParcEnvConfig *cfg, ParcEnv **out) {
         if (!(cfg->model.local_rotation[b][0] == 0.f && cfg->model.local_rotation[b][1] == 0.f && cfg->model.local_rotation[b][2] == 0.f && cfg->model.local_rotation[b][3] == 1.f)) sp.lr_identity = 0;
     sp.obs_tar = cfg->enable_tar_obs != 0; sp.obs_contact = cfg->use_contact_info != 0;
     sp.off_tarc = sp.off_tar + (sp.obs_tar ? S * sp.tar_w : 0);          // ig_parkour_env.py:927-946: the blocks that exist, in this order
+    if (!parc_hrot_fill(t.hrot, B, S, D, K, t.h.key_ids, t.h.key_slot, sp.off_char, sp.off_key, sp.off_tar, sp.tar_w, sp.obs_tar, sp.obs_tar && sp.obs_contact, sp.global_obs, sp.off_tarc))
+        return fail(PARC_ERR_INVALID, "internal: heading-pass table");
     sp.off_cc = sp.off_tarc + (sp.obs_tar && sp.obs_contact ? S * B : 0);
     sp.off_hf = sp.off_cc + (sp.obs_contact ? B : 0);
     sp.obs_dim = sp.off_hf + R;
