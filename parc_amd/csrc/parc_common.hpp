@@ -1,5 +1,6 @@
-// parc_common.hpp — what the env unit (parc_env.hip) and the tools unit (parc_tools.hip) both use, and nothing else.
-//   host:   the thread's last error message (one instance for the whole library), fail / HIPCHK / PARC_TRY, blocks, the device arena, the event set
+// parc_common.hpp — what more than one of the library's units (parc_env.hip, parc_dynamics.hip, parc_tools.hip) uses, and nothing else.
+//   host:   the thread's last error message (one instance for the whole library), fail / HIPCHK / PARC_TRY, blocks, the device arena, the event set,
+//           dev_opt
 //   device: Philox4x32-10 and the frame blend of motion_lib.py (the motion table entry it reads: parc_motion_table.hpp)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -22,6 +23,20 @@ static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 #define PARC_TRY(x) do { if (int _rc = (x)) return _rc; } while (0)
 
 static unsigned blocks(long long n, int t) { return (unsigned)((n + t - 1) / t); }
+
+// ParcEnvConfig::dev_options, "key=value;key=value"
+static std::string dev_opt(const ParcEnvConfig *cfg, const char *key) {
+    if (!cfg->dev_options) return "";
+    const std::string all = cfg->dev_options, k = std::string(key) + "=";
+    size_t at = 0;
+    while (at < all.size()) {
+        size_t end = all.find(';', at);
+        if (end == std::string::npos) end = all.size();
+        if (all.compare(at, k.size(), k) == 0) return all.substr(at + k.size(), end - at - k.size());
+        at = end + 1;
+    }
+    return "";
+}
 
 struct DeviceArena {                      // device buffers with one lifetime: freed together, by release() or with the arena
     std::vector<void *> ptrs;

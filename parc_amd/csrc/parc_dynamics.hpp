@@ -22,10 +22,12 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/parc_env.h"
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #define PARC_HD __host__ __device__ __forceinline__
 #define PARC_UNROLL _Pragma("unroll")
 #else

@@ -12,6 +12,8 @@
 // Chains run level by level (limbs, then trunk, on the way in; trunk, then limbs, on the way out), so a wave
 // executes ~6 body-units of work per pass instead of 15.
 #pragma once
+#include <string.h>
+
 #include "parc_dynamics.hpp"
 
 #pragma clang fp contract(fast)

@@ -27,7 +27,12 @@
 // packed-fp32 operand selection on SGPR pairs was checked in isolation and behaves correctly, so the suspect is the
 // handling of 64-bit register pairs at this kernel's register pressure (256 VGPR + 242 AGPR).
 #pragma once
+#include <string.h>
+
 #include "parc_dynamics_coop.hpp"
+#if defined(__HIPCC__)
+#include "parc_math.hpp"   // parsed here, ahead of the pragma below: the prep-record quaternions keep the command line's -ffp-contract=off (see above)
+#endif
 
 #if defined(__HIPCC__)
 #pragma clang fp contract(fast)

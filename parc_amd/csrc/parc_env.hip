@@ -1,6 +1,7 @@
-// parc_env.hip — the env's gfx950 kernels (step, dynamics, renderer) + the parc_env_* C-ABI of include/parc_env.h.
-// One of the library's two translation units: the stage-2 motion tools (parc_mopt_*, parc_mterr_*, parc_msamp_*, parc_pathplan_*,
-// parc_tgen_*) are parc_tools.hip, and what both units use is parc_common.hpp.
+// parc_env.hip — the env's gfx950 kernels (step, curriculum, resets, renderer) + the parc_env_* C-ABI of include/parc_env.h.
+// One of the library's three translation units: the rigid-body dynamics kernels are parc_dynamics.hip, seen from here through
+// parc_dynamics_host.hpp alone; the stage-2 motion tools (parc_mopt_*, parc_mterr_*, parc_msamp_*, parc_pathplan_*, parc_tgen_*) and the
+// learner's kernels are parc_tools.hip; what more than one unit uses is parc_common.hpp.
 //
 // One wavefront (64 lanes) owns one environment per iteration of a grid-stride loop:
 //   * the joint hierarchy / per-body tables are staged once per wave into LDS;
@@ -28,13 +29,11 @@
 #include <vector>
 
 #include "../../include/parc_env.h"
-#include "parc_common.hpp"    // what this unit shares with parc_tools.hip: g_err / fail / HIPCHK, MotionMeta, frame_blend, philox4
+#include "parc_common.hpp"    // what this unit shares with the other two: g_err / fail / HIPCHK, MotionMeta, frame_blend, philox4
 #include "parc_math.hpp"
 #include "parc_rowmap.hpp"    // row phase of k_env_post: (pass, lane) -> (row, slot)
 #include "parc_lanetab.hpp"   // prefetch phase, heading pass and contact block of k_env_post: what depends on the lane and on the handle's constants only
-#include "parc_dynamics.hpp"
-#include "parc_dynamics_coop.hpp"
-#include "parc_dynamics_wave.hpp"
+#include "parc_dynamics_host.hpp"   // the dynamics step, as an opaque handle
 
 using namespace parc;
 
@@ -141,24 +140,6 @@ __device__ __forceinline__ int cell_index(float p, float mn, float d) {
     float f = rintf((p - mn) / d);
     f = fminf(fmaxf(f, -1.0e9f), 1.0e9f);
     return (int)f;
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_dynamics: one THREAD per env advances the articulated character by one control step (nsub solver
-// substeps) — clip action -> PD targets -> ABA with implicit drives and implicit cell-column contact
-// (parc_dynamics.hpp).  Replaces gym.set_dof_position_target_tensor + gym.simulate x sim_steps + refresh_*
-// (ig_char_env.py:488-497, ig_env.py:359-389).
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_dynamics(const parcdyn::DynModel *__restrict__ M, parcdyn::DynTerrain T, ParcEnvBuffers buf,
-                                                 const float *__restrict__ action, const float *__restrict__ env_off, int N) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= N) return;
-    parcdyn::DynState S;
-    S.root_pos = buf.char_root_pos + 3 * (size_t)e; S.root_rot = buf.char_root_rot + 4 * (size_t)e;
-    S.root_vel = buf.char_root_vel + 3 * (size_t)e; S.root_ang_vel = buf.char_root_ang_vel + 3 * (size_t)e;
-    S.dof_pos = buf.char_dof_pos + (size_t)M->D * e; S.dof_vel = buf.char_dof_vel + (size_t)M->D * e;
-    S.contact_force = buf.contact_forces + (size_t)3 * M->B * e; S.body_pos = nullptr;
-    parcdyn::dyn_control_step(*M, T, S, action + (size_t)M->D * e, env_off + 3 * (size_t)e);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -964,15 +945,20 @@ __device__ __forceinline__ void done_scatter_block(const unsigned char *__restri
 // The health counters of the dynamics kernel (flag waits that timed out, contact planes that found no slot) go to two words of
 // host-mapped pinned memory with the first launch after every step: the host reads them without a synchronisation or a copy
 // (HipParkourEnv.step looks at them every step: a protocol error aborts the run at the next step instead of at the next log interval).
-__device__ __forceinline__ void publish_health(unsigned int *health) {
-    if (health && blockIdx.x == 0 && threadIdx.x == 0) {
-        __builtin_nontemporal_store(parcdyn::g_wave_timeouts, health);
-        __builtin_nontemporal_store(parcdyn::g_wave_man_drops, health + 1);
+// `words` is null when there is nothing to publish (no dynamics, or no mapped memory): the host's words then stay 0.
+struct HealthOut {
+    unsigned int *words;     // device alias of the host's two words
+    ParcDynCounters from;    // the counters of the dynamics unit
+};
+__device__ __forceinline__ void publish_health(const HealthOut &health) {
+    if (health.words && blockIdx.x == 0 && threadIdx.x == 0) {
+        __builtin_nontemporal_store(*health.from.timeouts, health.words);
+        __builtin_nontemporal_store(*health.from.man_drops, health.words + 1);
     }
 }
 
 __global__ __launch_bounds__(1024) void k_done_scatter(const unsigned char *__restrict__ ema_code, const int *__restrict__ motion_ids,
-                                                       int N, int *done_list, int *done_key, int *reset_count, int never_done, unsigned int *health) {
+                                                       int N, int *done_list, int *done_key, int *reset_count, int never_done, HealthOut health) {
     publish_health(health);
     done_scatter_block(ema_code, motion_ids, N, done_list, done_key, reset_count, never_done, blockIdx.x, gridDim.x);
 }
@@ -1114,7 +1100,7 @@ __global__ __launch_bounds__(1024) void k_fail_rate_ema(const int *__restrict__ 
 #define CURRICULUM_ONE_LAUNCH_MAX 8192 // measured: -1.6 us per step at 8 192 envs, +1.6 us at 16 384 (two passes of the scan)
 __global__ __launch_bounds__(1024) void k_curriculum_small(const unsigned char *__restrict__ ema_code, const int *__restrict__ motion_ids, int N,
                                                           int *done_list, int *done_key, int *reset_count, int never_done, int nchunks,
-                                                          float *fail_rates, int M, float w, unsigned int *health) {
+                                                          float *fail_rates, int M, float w, HealthOut health) {
     publish_health(health);
     if ((int)blockIdx.x < nchunks) {
         done_scatter_block(ema_code, motion_ids, N, done_list, done_key, reset_count, never_done, blockIdx.x, nchunks);
@@ -1562,25 +1548,6 @@ __global__ __launch_bounds__(1024) void k_build_cdf(const float *fail_rates, con
 // ================================================================================================
 // host side
 // ================================================================================================
-// ParcEnvConfig::dev_options, "key=value;key=value"
-static std::string dev_opt(const ParcEnvConfig *cfg, const char *key) {
-    if (!cfg->dev_options) return "";
-    const std::string all = cfg->dev_options, k = std::string(key) + "=";
-    size_t at = 0;
-    while (at < all.size()) {
-        size_t end = all.find(';', at);
-        if (end == std::string::npos) end = all.size();
-        if (all.compare(at, k.size(), k) == 0) return all.substr(at + k.size(), end - at - k.size());
-        at = end + 1;
-    }
-    return "";
-}
-
-// k_dynamics_wave, envs per block.  A block's latency does not depend on how many of its 64 lanes carry an env, so when 64-env blocks
-// would leave half the CUs without one (a multi-GPU shard), 32-env blocks put the same work on twice the CUs: -5 % at 8 192 envs (less LDS
-// and memory traffic per block; the vector instructions themselves take as long with 32 lanes as with 64)
-static int wave_envs_per_block(int N, int num_cus) { return (N + 63) / 64 <= num_cus / 2 ? 32 : 64; }
-
 struct ParcEnv {
     ParcEnvConfig cfg;
     int B, J, D, K, S, R, N, M = 0, T = 1;
@@ -1589,7 +1556,7 @@ struct ParcEnv {
     bool bound = false, have_motions = false, have_terrain = false;
     bool done_list_fresh = false;     // a step has produced a done list that parc_env_reset_done has not consumed yet
     // The device memory of the handle, one arena per lifetime; the d_* members below are views into them.
-    DeviceArena mem;                  // create .. destroy: tables, prep records, done lists, dynamics tables, root shadow, manifold overflow, render geoms
+    DeviceArena mem;                  // create .. destroy: tables, prep records, done lists, render geoms
     DeviceArena motions;              // parc_env_load_motions: d_records, d_meta, d_weights, d_fail, d_cdf, d_motion_done
     DeviceArena terrain;              // parc_env_load_terrain: d_hf, d_motion_off
     DeviceArena scene;                // d_scene alone: released and allocated anew when it must grow
@@ -1597,16 +1564,8 @@ struct ParcEnv {
     float4 *d_prep = nullptr;
     std::string dev_options_s, describe_s; // the dev_options this handle was created with (owned copy) / parc_env_describe
     unsigned int *h_health = nullptr, *d_health = nullptr; // two words of host-mapped pinned memory (publish_health) and their device alias
-    float *d_man_ovf = nullptr;       // k_dynamics_wave: overflow area of the per-lane contact-plane lists, [blocks][4 waves][WV_MAN_OVF][8][64]
-    float *d_root_shadow = nullptr;   // [N][6]: root position the dynamics last wrote + what that write rounded away (k_dynamics_wave)
-    parcdyn::DynModel h_dyn;
-    parcdyn::DynModel *d_dyn = nullptr;
-    parcdyn::CoopTables h_coop;
-    parcdyn::CoopTables *d_coop = nullptr;
-    bool use_coop = false;
-    parcdyn::WaveTables h_wave;
-    parcdyn::WaveTables *d_wave = nullptr;
-    bool use_wave = false, wave_rejected = false;
+    HealthOut health = {nullptr, {nullptr, nullptr}};      // what the curriculum kernels publish: set when the dynamics run and d_health exists
+    ParcDyn *dyn = nullptr;           // owned; the dynamics step (parc_dynamics_host.hpp), null when cfg.enable_dynamics is 0.  Same lifetime as `mem`
     DevTables h_tab;
     DevTables *d_tab = nullptr;
     unsigned row_mul = 0;  // j / (B - 1) == (j * row_mul) >> 16 for every joint item j (parc_rowmap.hpp, checked at create): host only, what
@@ -1651,6 +1610,7 @@ struct ParcEnv {
     ParcEnv &operator=(const ParcEnv &) = delete;
     ~ParcEnv() {
         (void)hipSetDevice(cfg.device);
+        parc_dyn_destroy(dyn);
         mem.release(); motions.release(); terrain.release(); scene.release();
         if (h_health) (void)hipHostFree(h_health);
         for (hipEvent_t x : tev) if (x) (void)hipEventDestroy(x);
@@ -1783,71 +1743,16 @@ extern "C" int parc_env_create(const ParcEnvConfig *cfg, ParcEnv **out) {
         e->grid_waves = prop.multiProcessorCount * 16; // persistent waves; each strides over envs
         e->num_cus = prop.multiProcessorCount;
     }
-    if (cfg->enable_dynamics) {
-        memset(&e->h_dyn, 0, sizeof(e->h_dyn));
-        parcdyn::fill_dyn_model(e->h_dyn, cfg->model, cfg->dynamics, cfg->action_low, cfg->action_high);
-        if (e->h_dyn.truncated > 0 || cfg->dynamics.num_geoms > PARC_MAX_GEOMS) // a silently shortened collision set would depend on the geom order
-            return fail(PARC_ERR_INVALID, "dynamics: " + std::to_string(e->h_dyn.truncated) + " collision point(s) / segment(s) / geom(s) do not fit the model tables (DYN_MAXC " +
-                        std::to_string(DYN_MAXC) + ", DYN_MAXS " + std::to_string(DYN_MAXS) + ", " + std::to_string(PARC_MAX_GEOMS) + " geoms)");
-        { // control mode (ig_char_env.py:21-26, 95)
-            const int cm = cfg->dynamics.control_mode;
-            bool all_1d = true;
-            for (int b = 1; b < cfg->model.num_bodies; ++b) all_1d = all_1d && cfg->model.joint_type[b] != parcdyn::DJ_SPHERICAL;
-            if (cm < PARC_CTRL_PD || cm > PARC_CTRL_PD_1D || (cm == PARC_CTRL_PD_1D && !all_1d))
-                return fail(PARC_ERR_INVALID, cm == PARC_CTRL_PD_1D ? "control_mode pd_1d only supports characters whose joints all have one dof (the reference asserts it, ig_char_env.py:246-250)"
-                                                                     : "unknown control_mode " + std::to_string(cm));
-        }
-        // developer switches for ablation measurements (ParcEnvConfig::dev_options; the product never sets them)
-        {
-            const std::string mode = dev_opt(cfg, "segments"); // "none": collision points only; "capsules": drop the sole edges of boxes
-            if (!mode.empty()) {
-                parcdyn::DynModel &dm = e->h_dyn;
-                int keep = 0;
-                for (int k = 0; k < dm.nseg; ++k) {
-                    const bool drop = mode == "none" || (mode == "capsules" && dm.seg_r[k] <= 0.011f);
-                    if (drop) continue;
-                    dm.seg_body[keep] = dm.seg_body[k]; dm.seg_r[keep] = dm.seg_r[k];
-                    for (int a = 0; a < 3; ++a) { dm.seg_a[keep][a] = dm.seg_a[k][a]; dm.seg_b[keep][a] = dm.seg_b[k][a]; }
-                    ++keep;
-                }
-                dm.nseg = keep;
-            }
-            const std::string dt_ = dev_opt(cfg, "dtang");
-            if (!dt_.empty()) e->h_dyn.dtang = (float)atof(dt_.c_str());
-            const std::string mp_ = dev_opt(cfg, "man_period"); // contact discovery every n substeps (1 = every substep, the round-3 behaviour)
-            if (!mp_.empty() && atoi(mp_.c_str()) >= 1) {
-                e->h_dyn.man_period = atoi(mp_.c_str());
-                e->h_dyn.spec_tv = 1.5f * (float)(e->h_dyn.man_period - 1) * e->h_dyn.dt;
-            }
-        }
-        PARC_TRY(mem.alloc(e->d_dyn, 1, &e->h_dyn));
-        // Kernel choice by tree shape: wave-per-limb (a trunk chain + <= 4 limb chains of <= 3 bodies, the humanoid),
-        // else chain-parallel (<= 8 chains of <= 4 bodies), else thread-per-env.  PARC_DYN_KERNEL=coop|thread forces
-        // one of the more general kernels (they are kept as fallbacks for other trees and as cross-checks).
-        const std::string want = dev_opt(cfg, "kernel");
-        const bool coop_ok = parcdyn::build_coop_tables(e->h_dyn, e->h_coop);
-        const bool wave_ok = coop_ok && parcdyn::build_wave_tables(e->h_dyn, e->h_coop, e->h_wave);
-        e->wave_rejected = !wave_ok; // the tree / the collision tables do not fit k_dynamics_wave (parc_env_describe says so: the fallbacks are several times slower)
-        e->use_wave = wave_ok && want != "coop" && want != "thread";
-        e->use_coop = coop_ok && !e->use_wave && want != "thread";
-        if (e->use_wave) {
-            PARC_TRY(mem.alloc(e->d_wave, 1, &e->h_wave));
-            if (dev_opt(cfg, "no_residual").empty()) // (developer switch: the precision test measures the drift without it)
-                PARC_TRY(mem.alloc_fill(e->d_root_shadow, 6 * N, 0xff)); // NaN: matches no buffer value
-            const int epb = wave_envs_per_block((int)N, e->num_cus);
-            // overflow area of the contact-plane lists (never read before it is written)
-            PARC_TRY(mem.alloc(e->d_man_ovf, (N + epb - 1) / epb * WV_MAXLIMB * WV_MAN_OVF * 8 * 64));
-            HIPCHK(hipFuncSetAttribute(cfg->dynamics.control_mode == PARC_CTRL_PD ? (const void *)parcdyn::k_dynamics_wave : (const void *)parcdyn::k_dynamics_wave_ff,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, parcdyn::wv_lds_floats() * (int)sizeof(float)));
-        } else if (e->use_coop) {
-            PARC_TRY(mem.alloc(e->d_coop, 1, &e->h_coop));
-        }
-    }
+    if (cfg->enable_dynamics) PARC_TRY(parc_dyn_create(cfg, e->N, e->num_cus, &e->dyn));
     e->force_ema_leader = !dev_opt(cfg, "ema_leader").empty();
     e->force_two_launch_curriculum = !dev_opt(cfg, "curriculum_two_launches").empty();
     if (hipHostMalloc((void **)&e->h_health, 2 * sizeof(unsigned int), hipHostMallocMapped) == hipSuccess) {
         e->h_health[0] = 0u; e->h_health[1] = 0u;
         if (hipHostGetDevicePointer((void **)&e->d_health, e->h_health, 0) != hipSuccess) e->d_health = nullptr;
+    }
+    if (e->dyn && e->d_health) {
+        e->health.words = e->d_health;
+        PARC_TRY(parc_dyn_counters(&e->health.from));
     }
     PARC_TRY(e->ev.create());
     sp.tables = e->d_tab; sp.ray_points = e->d_ray; sp.env_offsets = e->d_env_off;
@@ -1982,41 +1887,21 @@ static int check_ready(ParcEnv *e) {
 }
 
 static int launch_dynamics(ParcEnv *e, const float *action_dev, hipStream_t st) {
-    if (!e->cfg.enable_dynamics) return PARC_OK;
-    if (!action_dev) return fail(PARC_ERR_INVALID, "action is required when enable_dynamics is set");
-    parcdyn::DynTerrain T;
-    T.hf = e->d_hf; T.X = e->sp.X; T.Y = e->sp.Y; T.min_x = e->sp.min_x; T.min_y = e->sp.min_y; T.dx = e->sp.dx; T.dy = e->sp.dy;
-    if (e->use_wave) {
-        const int epb = wave_envs_per_block(e->N, e->num_cus);
-        if (e->cfg.dynamics.control_mode == PARC_CTRL_PD)
-            hipLaunchKernelGGL(parcdyn::k_dynamics_wave, dim3((e->N + epb - 1) / epb), dim3(256), parcdyn::wv_lds_floats() * sizeof(float), st,
-                               (const parcdyn::DynModel *)e->d_dyn, (const parcdyn::WaveTables *)e->d_wave, T, e->sp.buf, action_dev,
-                               (const float *)e->d_env_off, e->d_root_shadow, e->d_prep, e->d_man_ovf, e->N, epb);
-        else // control modes vel / torque / pd_exp / pd_1d: the instantiation with the feed-forward joint torques
-            hipLaunchKernelGGL(parcdyn::k_dynamics_wave_ff, dim3((e->N + epb - 1) / epb), dim3(256), parcdyn::wv_lds_floats() * sizeof(float), st,
-                               (const parcdyn::DynModel *)e->d_dyn, (const parcdyn::WaveTables *)e->d_wave, T, e->sp.buf, action_dev,
-                               (const float *)e->d_env_off, e->d_root_shadow, e->d_prep, e->d_man_ovf, e->N, epb);
-    }
-    else if (e->use_coop)
-        hipLaunchKernelGGL(parcdyn::k_dynamics_coop, dim3((e->N + CO_ENVS - 1) / CO_ENVS), dim3(64), 0, st, (const parcdyn::DynModel *)e->d_dyn,
-                           (const parcdyn::CoopTables *)e->d_coop, T, e->sp.buf, action_dev, (const float *)e->d_env_off, e->N);
-    else
-        hipLaunchKernelGGL(k_dynamics, dim3((e->N + 63) / 64), dim3(64), 0, st, (const parcdyn::DynModel *)e->d_dyn, T, e->sp.buf, action_dev,
-                           (const float *)e->d_env_off, e->N);
-    HIPCHK(hipGetLastError());
-    return PARC_OK;
+    if (!e->dyn) return PARC_OK;
+    const ParcDynTerrain T = {e->d_hf, e->sp.X, e->sp.Y, e->sp.min_x, e->sp.min_y, e->sp.dx, e->sp.dy};
+    return parc_dyn_launch(e->dyn, T, e->sp.buf, action_dev, e->d_env_off, e->d_prep, st);
 }
 
 static int launch_curriculum(ParcEnv *e, hipStream_t st) {
     e->done_list_fresh = true;
     if (e->M <= 64 && !e->force_ema_leader && e->N <= CURRICULUM_ONE_LAUNCH_MAX && (e->N & 7) == 0 && !e->force_two_launch_curriculum) {
         hipLaunchKernelGGL(k_curriculum_small, dim3(e->nchunks + e->M), dim3(1024), 0, st, e->d_ema, e->sp.buf.motion_ids, e->N, e->d_done_list,
-                           e->d_done_key, e->d_reset_count, e->sp.never_done, e->nchunks, e->d_fail, e->M, e->cfg.fail_rate_ema_weight, e->d_health);
+                           e->d_done_key, e->d_reset_count, e->sp.never_done, e->nchunks, e->d_fail, e->M, e->cfg.fail_rate_ema_weight, e->health);
         HIPCHK(hipGetLastError());
         return PARC_OK;
     }
     hipLaunchKernelGGL(k_done_scatter, dim3(e->nchunks), dim3(1024), 0, st, e->d_ema, e->sp.buf.motion_ids, e->N, e->d_done_list,
-                       e->d_done_key, e->d_reset_count, e->sp.never_done, e->d_health);
+                       e->d_done_key, e->d_reset_count, e->sp.never_done, e->health);
     if (e->M <= 64 && !e->force_ema_leader) {
         hipLaunchKernelGGL(k_fail_rate_ema, dim3(e->M), dim3(1024), 0, st, e->d_done_key, e->d_reset_count, e->d_fail, e->M,
                            e->cfg.fail_rate_ema_weight);
@@ -2042,7 +1927,7 @@ static int launch_post(ParcEnv *e, int mode, const int64_t *ids, int count, hipS
     if (count <= 0) return PARC_OK;
     const int grid = (count + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
     const size_t lds = e->lds_bytes * ENVS_PER_BLOCK;
-    if (mode == MODE_STEP && e->cfg.enable_dynamics && e->use_wave) prep_done = true; // k_dynamics_wave wrote the prep records with the state
+    if (mode == MODE_STEP && e->dyn && parc_dyn_writes_prep(e->dyn)) prep_done = true; // k_dynamics_wave wrote the prep records with the state
     if (!prep_done) hipLaunchKernelGGL(k_env_prep, dim3((count + 3) / 4), dim3(64), 0, st, e->sp, ids, ids32, count_dev, count);
     const bool mirror = wants_mirror(e->sp.buf);
     if (obs_variant(e->cfg)) { // a non-default observation layout -- instantiated for the general (MIRROR) form only
@@ -2105,124 +1990,7 @@ extern "C" int parc_env_set_episode_length(ParcEnv *e, float seconds) {
     return PARC_OK;
 }
 
-__global__ void k_td_lambda(const float *__restrict__ r, const float *__restrict__ nv, const int *__restrict__ done, float g, float lam0, int T, int N,
-                            float *__restrict__ ret) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= N) return;
-    size_t o = (size_t)(T - 1) * N + e;
-    float acc = r[o] + g * nv[o];
-    ret[o] = acc;
-    for (int i = T - 2; i >= 0; --i) {
-        o -= N;
-        const float reset = done[o] != PARC_DONE_NULL ? 1.0f : 0.0f;
-        const float lam = lam0 * (1.0f - reset);
-        acc = r[o] + g * ((1.0f - lam) * nv[o] + lam * acc);
-        ret[o] = acc;
-    }
-}
-
-extern "C" int parc_td_lambda_return(const float *reward, const float *next_vals, const int32_t *done, float discount, float td_lambda,
-                                     int32_t T, int32_t N, float *ret_out, void *stream) {
-    if (!reward || !next_vals || !done || !ret_out || T < 1 || N < 0) return fail(PARC_ERR_INVALID, "bad argument");
-    if (N == 0) return PARC_OK;
-    hipLaunchKernelGGL(k_td_lambda, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, reward, next_vals, done, discount, td_lambda, T, N, ret_out);
-    HIPCHK(hipGetLastError());
-    return PARC_OK;
-}
-
-__global__ __launch_bounds__(256) void k_normalize_record(const float *__restrict__ x, const float *__restrict__ mean, const float *__restrict__ sd,
-                                                          float clip, float *__restrict__ norm_out, float *__restrict__ copy_out, long long total, int dim) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int c = (int)(i % dim);
-    const float v = x[i];
-    float y = (v - mean[c]) / sd[c];
-    y = fminf(fmaxf(y, -clip), clip);
-    norm_out[i] = y;
-    if (copy_out) copy_out[i] = v;
-}
-
-extern "C" int parc_normalize_record(const float *x, const float *mean, const float *sd, float clip, float *norm_out, float *copy_out,
-                                     int64_t n, int32_t dim, void *stream) {
-    if (!x || !mean || !sd || !norm_out || n < 0 || dim < 1) return fail(PARC_ERR_INVALID, "bad argument");
-    const long long total = (long long)n * dim;
-    if (total == 0) return PARC_OK;
-    hipLaunchKernelGGL(k_normalize_record, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, mean, sd, clip, norm_out,
-                       copy_out, total, dim);
-    HIPCHK(hipGetLastError());
-    return PARC_OK;
-}
-
 // Recorder: one 128-thread block per env appends that env's row (see include/parc_env.h).
-// ---------------------------------------------------------------------------------------------------------------------------------
-// Minibatch gather (experience_buffer.py:81-89): block = 256 sampled rows.  Narrow buffers (a scalar or a few values per sample: reward,
-// done, advantage ...): thread t copies row t.  Wide buffers (observations 5 248 B, actions 112 B): the block's four waves walk its 256 rows,
-// a wavefront per row, 16 bytes per lane where source and destination rows are 16-byte aligned (else 4 / 1 bytes).  HBM-bound: 2 x the
-// minibatch's bytes; bit-identical to index_select by construction (a byte copy).
-struct GatherArgs {
-    const char *src[PARC_MAX_GATHER_BUFFERS];
-    char *dst[PARC_MAX_GATHER_BUFFERS];
-    long long row_bytes[PARC_MAX_GATHER_BUFFERS];
-    int nb;
-};
-
-__global__ __launch_bounds__(256) void k_gather_rows(const GatherArgs A, const long long *__restrict__ idx, long long n, long long count) {
-    __shared__ long long s_row[256];
-    const long long r0 = (long long)blockIdx.x * 256;
-    const int t = threadIdx.x;
-    long long mine = -1;
-    if (r0 + t < n) {
-        long long i = idx[r0 + t] % count;   // torch.remainder(idx, sample_count): idx >= 0
-        if (i < 0) i += count;
-        mine = i;
-    }
-    s_row[t] = mine;
-    __syncthreads();
-    const int lane = t & 63, w = t >> 6;
-    for (int b = 0; b < A.nb; ++b) {
-        const long long rb = A.row_bytes[b];
-        if (rb < 64) { // narrow: one thread per row
-            if (mine >= 0) {
-                const char *s = A.src[b] + mine * rb;
-                char *d = A.dst[b] + (r0 + t) * rb;
-                if ((rb & 3) == 0 && ((((uintptr_t)s) | ((uintptr_t)d)) & 3) == 0) for (long long k = 0; k < rb; k += 4) *(int *)(d + k) = *(const int *)(s + k);
-                else for (long long k = 0; k < rb; ++k) d[k] = s[k];
-            }
-        } else {       // wide: one wavefront per row, rows w, w + 4, ... of the block
-            for (int q = w; q < 256; q += 4) {
-                const long long i = s_row[q];
-                if (i < 0) break; // rows past n (only at the end of the last block)
-                const char *s = A.src[b] + i * rb;
-                char *d = A.dst[b] + (r0 + q) * rb;
-                if ((rb & 15) == 0 && ((((uintptr_t)s) | ((uintptr_t)d)) & 15) == 0) {
-                    for (long long k = 16ll * lane; k < rb; k += 1024) *(float4 *)(d + k) = *(const float4 *)(s + k);
-                } else if ((rb & 3) == 0 && ((((uintptr_t)s) | ((uintptr_t)d)) & 3) == 0) {
-                    for (long long k = 4ll * lane; k < rb; k += 256) *(int *)(d + k) = *(const int *)(s + k);
-                } else {
-                    for (long long k = lane; k < rb; k += 64) d[k] = s[k];
-                }
-            }
-        }
-    }
-}
-
-extern "C" int parc_gather_rows(int32_t num_buffers, const void *const *src_dev, void *const *dst_dev, const int64_t *row_bytes, const int64_t *idx_dev,
-                                int64_t n, int64_t count, void *stream) {
-    if (num_buffers < 1 || num_buffers > PARC_MAX_GATHER_BUFFERS) return fail(PARC_ERR_INVALID, "parc_gather_rows: 1..16 buffers");
-    if (!src_dev || !dst_dev || !row_bytes || !idx_dev || n < 0 || count < 1) return fail(PARC_ERR_INVALID, "parc_gather_rows: bad argument");
-    if (n == 0) return PARC_OK;
-    GatherArgs A;
-    memset(&A, 0, sizeof(A));
-    A.nb = num_buffers;
-    for (int b = 0; b < num_buffers; ++b) {
-        if (!src_dev[b] || !dst_dev[b] || row_bytes[b] < 1) return fail(PARC_ERR_INVALID, "parc_gather_rows: null buffer or empty row");
-        A.src[b] = (const char *)src_dev[b]; A.dst[b] = (char *)dst_dev[b]; A.row_bytes[b] = row_bytes[b];
-    }
-    hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A, (const long long *)idx_dev, (long long)n, (long long)count);
-    HIPCHK(hipGetLastError());
-    return PARC_OK;
-}
-
 __global__ __launch_bounds__(128) void k_record(const DevTables *__restrict__ T, ParcEnvBuffers buf, int N, int B, int D, int obs_dim, float *frames,
                                                 float *obs_out, int cap, int *count, unsigned char *writing, int *n_writing, int use_ref) {
     const int e = blockIdx.x, tid = threadIdx.x;
@@ -2586,11 +2354,6 @@ extern "C" int parc_test_quat_op(int32_t op, const float *a, const float *b, con
     return PARC_OK;
 }
 
-#ifndef PARC_BUILD_FLAGS
-#define PARC_BUILD_FLAGS "unknown"
-#endif
-extern "C" const char *parc_build_flags(void) { return PARC_BUILD_FLAGS; }
-
 extern "C" int parc_env_get_frame_vel_tables(ParcEnv *e, float *root_vel, float *root_ang_vel, float *dof_vel) {
     if (!e || !e->have_motions) return fail(PARC_ERR_STATE, "load_motions first");
     HIPCHK(hipSetDevice(e->cfg.device));
@@ -2610,22 +2373,7 @@ extern "C" const unsigned int *parc_env_health_words(ParcEnv *e) { return (e && 
 extern "C" const char *parc_env_describe(ParcEnv *e) {
     if (!e) return "";
     char b[1024];
-    std::string d;
-    const bool ctrl_ff = e->cfg.enable_dynamics && e->cfg.dynamics.control_mode != PARC_CTRL_PD;
-    const char *dk = !e->cfg.enable_dynamics ? "none" : (e->use_wave ? (ctrl_ff ? "k_dynamics_wave_ff" : "k_dynamics_wave") : (e->use_coop ? "k_dynamics_coop" : "k_dynamics"));
-    snprintf(b, sizeof(b), "dynamics_kernel=%s;", dk); d += b;
-    if (e->cfg.enable_dynamics) {
-        const parcdyn::DynModel &m = e->h_dyn;
-        static const char *const ctrl_names[] = {"pd", "vel", "torque", "pd_exp", "pd_1d"};
-        snprintf(b, sizeof(b), "control_mode=%s;", ctrl_names[m.ctrl]); d += b;
-        snprintf(b, sizeof(b), "envs_per_block=%d;substeps=%d;substep_dt=%.9g;collision_points=%d;collision_segments=%d;kn=%g;dn=%g;dtang=%g;mu=%g;pen_cap=%g;"
-                 "manifold_period=%d;spec_m0=%g;spec_tv=%g;spec_max=%g;root_residual=%d;", e->use_wave ? wave_envs_per_block(e->N, e->num_cus) : (e->use_coop ? CO_ENVS : 64),
-                 m.nsub, (double)m.dt, m.ncol, m.nseg, (double)m.kn, (double)m.dn, (double)m.dtang, (double)m.mu, (double)m.pen_cap, m.man_period, (double)m.spec_m0,
-                 (double)m.spec_tv, (double)m.spec_max, e->d_root_shadow ? 1 : 0);
-        d += b;
-        if (e->wave_rejected) d += "note=the model does not fit k_dynamics_wave (tree shape or > 32 candidates on a body): general fallback kernel;";
-        if (e->use_wave) { snprintf(b, sizeof(b), "manifold_lds_slots=%d+%d+%d+%d;manifold_overflow_slots=%d;", e->h_wave.man_cap[0], e->h_wave.man_cap[1], e->h_wave.man_cap[2], e->h_wave.man_cap[3], WV_MAN_OVF); d += b; }
-    }
+    std::string d = e->dyn ? parc_dyn_describe(e->dyn) : "dynamics_kernel=none;";
     const bool small = e->M <= 64 && !e->force_ema_leader && e->N <= CURRICULUM_ONE_LAUNCH_MAX && (e->N & 7) == 0 && !e->force_two_launch_curriculum;
     snprintf(b, sizeof(b), "curriculum=%s;post_kernel=%s;dev_options=%s", small ? "k_curriculum_small" : ((e->M <= 64 && !e->force_ema_leader) ? "k_done_scatter+k_fail_rate_ema" : "k_done_scatter+k_ema_first+k_ema_leader"),
              e->bound ? parc_env_post_kernel(e) : "unbound", e->dev_options_s.empty() ? "none" : e->dev_options_s.c_str());
@@ -2634,31 +2382,23 @@ extern "C" const char *parc_env_describe(ParcEnv *e) {
     return e->describe_s.c_str();
 }
 
+// The process-wide counters of k_dynamics_wave on the env's device (parc_dynamics_host.hpp): both must stay 0.
 extern "C" int parc_env_dynamics_timeouts(ParcEnv *e) {
     if (!e) return fail(PARC_ERR_INVALID, "null env");
-    unsigned int v = 0;
     HIPCHK(hipSetDevice(e->cfg.device));
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpyFromSymbol(&v, HIP_SYMBOL(parcdyn::g_wave_timeouts), sizeof(v)));
-    return (int)(v > 0x7fffffffu ? 0x7fffffffu : v);
+    return parc_dyn_read_counter(false);
 }
 
-// Contact planes k_dynamics_wave had no room for (the per-lane list's LDS share + overflow area were full; parc_dynamics_wave.hpp,
-// WvMan): must stay 0 -- a dropped plane is a contact the substeps after a discovery do not see.
 extern "C" int parc_env_dynamics_manifold_drops(ParcEnv *e) {
     if (!e) return fail(PARC_ERR_INVALID, "null env");
-    unsigned int v = 0;
     HIPCHK(hipSetDevice(e->cfg.device));
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpyFromSymbol(&v, HIP_SYMBOL(parcdyn::g_wave_man_drops), sizeof(v)));
-    return (int)(v > 0x7fffffffu ? 0x7fffffffu : v);
+    return parc_dyn_read_counter(true);
 }
 
 extern "C" float parc_env_last_dynamics_ms(ParcEnv *e) { return e ? e->last_dyn_ms : 0.f; }
 
 extern "C" const char *parc_env_dynamics_kernel(ParcEnv *e) {
-    if (!e || !e->cfg.enable_dynamics) return "";
-    return e->use_wave ? "k_dynamics_wave" : (e->use_coop ? "k_dynamics_coop" : "k_dynamics");
+    return (e && e->dyn) ? parc_dyn_kernel_name(e->dyn) : "";
 }
 
 extern "C" const char *parc_env_post_kernel(ParcEnv *e) {
@@ -2805,59 +2545,6 @@ extern "C" int parc_env_debug_stamps(ParcEnv *e, double *mean8) {
     std::vector<unsigned> h((size_t)e->N * 8);
     HIPCHK(hipMemcpy(h.data(), e->sp.stamp_out, h.size() * 4, hipMemcpyDeviceToHost));
     for (int k = 0; k < 8; ++k) { double a = 0; for (int i = 0; i < e->N; ++i) a += h[(size_t)i * 8 + k]; mean8[k] = a / e->N; }
-    return PARC_OK;
-}
-
-// Diagnostic: cycles per phase of k_dynamics_coop summed over all waves since the last call (then cleared).
-extern "C" int parc_env_debug_dyn_stamps(double *out16) {
-    unsigned long long h[16], z[16] = {0};
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpyFromSymbol(h, HIP_SYMBOL(parcdyn::g_dyn_stamps), sizeof(h)));
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(parcdyn::g_dyn_stamps), z, sizeof(z)));
-    for (int i = 0; i < 16; ++i) out16[i] = (double)h[i];
-    return PARC_OK;
-}
-
-// Diagnostic: cycles per segment of k_dynamics_wave, per wave role [4][16], summed over all blocks since the last call.
-extern "C" int parc_env_debug_wave_stamps(double *out64) {
-    unsigned long long h[64], z[64] = {0};
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpyFromSymbol(h, HIP_SYMBOL(parcdyn::g_wave_stamps), sizeof(h)));
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(parcdyn::g_wave_stamps), z, sizeof(z)));
-    for (int i = 0; i < 64; ++i) out64[i] = (double)h[i];
-    return PARC_OK;
-}
-
-// Diagnostic: contact-cull statistics of k_dynamics_wave per body [16][8] (see g_wave_cnt), cleared by the call.
-extern "C" int parc_env_debug_wave_counts(double *out128) {
-    unsigned long long h[128], z[128] = {0};
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpyFromSymbol(h, HIP_SYMBOL(parcdyn::g_wave_cnt), sizeof(h)));
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(parcdyn::g_wave_cnt), z, sizeof(z)));
-    for (int i = 0; i < 128; ++i) out128[i] = (double)h[i];
-    return PARC_OK;
-}
-#endif
-
-#ifdef PARC_STAMPS
-// Diagnostic: manifold-size histograms of k_dynamics_wave [16][4][16] (see g_wave_hist; -DPARC_COUNTS builds fill them), cleared by the call.
-extern "C" int parc_env_debug_wave_hist(double *out1024) {
-    static unsigned long long h[1024], z[1024];
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpyFromSymbol(h, HIP_SYMBOL(parcdyn::g_wave_hist), sizeof(h)));
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(parcdyn::g_wave_hist), z, sizeof(z)));
-    for (int i = 0; i < 1024; ++i) out1024[i] = (double)h[i];
-    return PARC_OK;
-}
-#endif
-
-#ifdef PARC_TIMELINE
-// Diagnostic (-DPARC_TIMELINE builds): absolute cycle counter at the hand-off points of one substep of block 0, [wave][event]
-extern "C" int parc_env_debug_wave_timeline(double *out64) {
-    unsigned long long h[64];
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpyFromSymbol(h, HIP_SYMBOL(parcdyn::g_wave_tl), sizeof(h)));
-    for (int i = 0; i < 64; ++i) out64[i] = (double)h[i];
     return PARC_OK;
 }
 #endif

@@ -1,4 +1,5 @@
-// parc_tools.hip -- the stage-2 motion tools of include/parc_env.h as one translation unit, apart from the env (parc_env.hip).
+// parc_tools.hip -- the stage-2 motion tools and the learner's kernels of include/parc_env.h as one translation unit, apart from the env
+// (parc_env.hip) and the dynamics (parc_dynamics.hip).
 // Every header includes what it uses; the order below does not matter.
 #include "parc_clip_batch.hpp"       // host code the motion-tool handles share: mopt::Model setup, clip-batch validation and upload
 #include "parc_motion_opt.hpp"       // parc_mopt_*: the batched kinematic motion optimiser (defines mopt::Model / mopt::Clips)
@@ -7,3 +8,4 @@
 #include "parc_path_planner.hpp"     // parc_pathplan_*: stage 2's batched A* terrain path planner
 #include "parc_terrain_gen.hpp"      // parc_tgen_*: stage 2's BOXES / PATHS / STAIRS terrain generators, batched
 #include "parc_motion_aug.hpp"       // parc_maug_*: stage 0's motion-terrain augmenter and the mirrored copies, batched
+#include "parc_learner.hpp"          // parc_td_lambda_return, parc_normalize_record, parc_gather_rows: the learner's kernels

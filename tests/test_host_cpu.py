@@ -318,7 +318,8 @@ def test_dynamics_kernel_of_the_built_library_uses_no_scratch(tmp_path):
     """k_dynamics_wave keeps every body of a chain in registers: that needs its body loops fully unrolled (build flag
     -pragma-unroll-threshold, __graft_entry__.py) -- with the loops rolled the per-body arrays turn into ~1 KB of scratch per lane and the
     kernel is several times slower, silently.  Read from the code objects of the library as built (one per translation unit): private
-    segment 0, 1 wave per SIMD; and no motion-tool kernel shares the code object, i.e. the translation unit, of k_dynamics_wave."""
+    segment 0, 1 wave per SIMD; and the code object, i.e. the translation unit, of k_dynamics_wave holds the dynamics kernels and nothing
+    of the env or the motion tools."""
     import re
     import shutil
     import subprocess
@@ -329,8 +330,8 @@ def test_dynamics_kernel_of_the_built_library_uses_no_scratch(tmp_path):
     so = tmp_path / "lib.so"
     shutil.copy(L.LIB_PATH, so)
     subprocess.check_call([objdump, "--offloading", str(so)], cwd=str(tmp_path), stdout=subprocess.DEVNULL)
-    co = sorted(f for f in os.listdir(tmp_path) if "gfx950" in f)   # one code object per translation unit: the env, the motion tools
-    assert co, os.listdir(tmp_path)
+    co = sorted(f for f in os.listdir(tmp_path) if "gfx950" in f)   # one code object per translation unit: the env, the dynamics, the motion tools
+    assert len(co) == 3, os.listdir(tmp_path)
     kern, home = {}, {}
     for c in co:
         notes = subprocess.check_output([readelf, "--notes", str(tmp_path / c)], text=True)
@@ -352,3 +353,28 @@ def test_dynamics_kernel_of_the_built_library_uses_no_scratch(tmp_path):
     tools = [k for k in kern if re.match(r"_ZN(4mopt|5mterr|5msamp|5pplan|4tgen)\d", k)]
     assert len(env_co) == 1 and len(tools) >= 5, (env_co, tools)
     assert not [k for k in tools if home[k] in env_co], [k for k in tools if home[k] in env_co]
+    # and so are the dynamics (parc_dynamics.hip): its code object holds the three kernels (four entry points) and no kernel of the env
+    dyn = {k for k in kern if home[k] in env_co}
+    for name in ("k_dynamicsPK", "k_dynamics_coop", "k_dynamics_waveE", "k_dynamics_wave_ff"):
+        assert len([k for k in dyn if name in k]) == 1, (name, sorted(dyn))
+    others = [k for k in dyn if re.search(r"k_env_post|k_env_prep|k_reset_with|k_done_scatter|k_fail_rate_ema|k_curriculum_small|k_ema_first|k_ema_leader|k_build_cdf", k)]
+    assert not others and len(dyn) == 4, sorted(dyn)
+    env = {home[k] for k in kern if re.search(r"k_env_post|k_env_prep|k_reset_with|k_curriculum_small", k)}
+    assert len(env) == 1 and not (env & env_co), (env, env_co)
+
+
+def test_env_and_dynamics_units_do_not_include_each_other():
+    """What the split of the dynamics into a unit of its own is for: an edit on one side rebuilds only that side.  Read from the depfiles
+    build() leaves beside the objects: the env unit names no dynamics kernel header, the dynamics unit none of the env's tables."""
+    obj = os.path.join(REPO, "parc_amd", "_obj")
+    if not os.path.exists(os.path.join(obj, "parc_env.d")):
+        pytest.skip("no depfile of the env unit: the library was not built by build() here")
+    with open(os.path.join(obj, "parc_env.d")) as f:
+        env = f.read()
+    with open(os.path.join(obj, "parc_dynamics.d")) as f:
+        dyn = f.read()
+    assert "parc_env.hip" in env and "parc_dynamics_host.hpp" in env and "parc_dynamics.hip" in dyn and "parc_dynamics_wave.hpp" in dyn
+    for h in ("parc_dynamics.hpp", "parc_dynamics_coop.hpp", "parc_dynamics_wave.hpp"):
+        assert h not in env, h
+    for h in ("parc_lanetab.hpp", "parc_rowmap.hpp"):
+        assert h not in dyn, h

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Register / scratch / LDS usage of the library's main kernels (hipcc -Rpass-analysis=kernel-resource-usage); no GPU needed.
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -fno-slp-vectorize -mllvm -amdgpu-sched-strategy=iterative-maxocc -mllvm -pragma-unroll-threshold=1048576"
-/opt/rocm/bin/hipcc $FLAGS "$@" -Rpass-analysis=kernel-resource-usage -o /tmp/parc_ru.so "$(dirname "$0")/../parc_amd/csrc/parc_env.hip" "$(dirname "$0")/../parc_amd/csrc/parc_tools.hip" 2>&1 | \
+/opt/rocm/bin/hipcc $FLAGS "$@" -Rpass-analysis=kernel-resource-usage -o /tmp/parc_ru.so "$(dirname "$0")/../parc_amd/csrc/parc_env.hip" "$(dirname "$0")/../parc_amd/csrc/parc_dynamics.hip" "$(dirname "$0")/../parc_amd/csrc/parc_tools.hip" 2>&1 | \
   python3 -c "
 import re, sys
 cur = None
