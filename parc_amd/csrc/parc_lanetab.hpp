@@ -21,7 +21,7 @@
 //       (parc_lt_ray_off).  They state which of the lane's loads are its own, for the host test and for a reader of a dumped table.
 #pragma once
 
-#include "parc_rowmap.hpp"
+#include "parc_rowmap.hpp"   // PARC_ROWMAP_HD (with the HIP runtime it needs under hipcc), parc_rowmap_item
 
 #define PARC_LANETAB_WORDS 4
 #define PARC_LANETAB_TILE_CELLS 5 // per lane: 5 x 64 = the 320 floats the tile may take

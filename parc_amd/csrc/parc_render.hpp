@@ -1,5 +1,5 @@
 // parc_render.hpp — headless ray-cast renderer of the env scene (parc_env_render; the reference's viewer, ig_parkour_env.py:417-441,
-// :1046-1064, :1123-1132, drawn without a display).  Included by parc_env.hip after the FK helpers it reuses (joint_dof_to_rot,
+// :1046-1064, :1123-1132, drawn without a display).  It reuses the FK helpers of the env's operators (joint_dof_to_rot,
 // fk_thread); nothing of the step path calls into this file.
 //
 // Scene = exactly what the physics collides with:
@@ -19,6 +19,15 @@
 // joint rotations and FK of both characters and the camera-relative primitives + one bounding sphere per character in LDS (~3 KB); then
 // every thread casts its pixel's primary ray and (shadows on) one shadow ray toward the sun with the same intersection code.
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/parc_env.h"
+#include "parc_env_ops.hpp"      // fk_thread
+#include "parc_env_tables.hpp"   // DevTables, joint_dof_to_rot
+#include "parc_math.hpp"
 
 #define RENDER_MAX_PRIMS (2 * PARC_MAX_GEOMS)
 #define RENDER_TILE 16

@@ -1,6 +1,6 @@
 // parc_render_scene.hpp — scene render (parc_env_render_scene): one image of the terrain and the characters of many envs, every
 // character at state + env_offsets in the one world, as the reference's viewer draws the whole sim (ig_parkour_env.py:409-441).
-// Included by parc_env.hip right after parc_render.hpp, whose camera, terrain DDA and intersection functions it reuses unchanged.
+// On top of parc_render.hpp, whose camera, terrain DDA and intersection functions it reuses unchanged.
 //
 // Launch sequence (all on the caller's stream, no host sync; `slot` = one character: list entry i, kind 0 simulated / 1 reference):
 //   k_scene_init     1 block: zero the bin counters, reset the reductions, the pose-independent radius of a character about its root.
@@ -21,6 +21,16 @@
 // ties as in k_render.  The walk stops once the next bin starts beyond the best t, so the result is the minimum over every character
 // that can reach it whatever order the atomics filled the bins in.  Every loop is bounded by a count.
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/parc_env.h"
+#include "parc_env_ops.hpp"      // fk_thread
+#include "parc_env_tables.hpp"   // DevTables, joint_dof_to_rot
+#include "parc_math.hpp"
+#include "parc_render.hpp"       // RenderArgs, RenderGeoms, the camera, the terrain DDA, the primitive intersections
 
 #define SCENE_BINS_SIDE 64
 #define SCENE_MAX_BINS (SCENE_BINS_SIDE * SCENE_BINS_SIDE)

@@ -11,6 +11,7 @@
 #pragma once
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #define PARC_ROWMAP_HD __host__ __device__ __forceinline__
 #else
 #define PARC_ROWMAP_HD inline

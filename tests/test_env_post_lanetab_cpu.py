@@ -38,7 +38,7 @@ extern "C" int lanetab_ray_off(int lane, int R, int i) {
 }
 """
 NFIELDS = 12 + 15 + 1
-REC_F4, REC_Q_CONTACT, REC_Q_VEL = 32, 16, 20   # parc_env.hip: a frame record = 32 float4; #16..19 contacts, #20.. root_vel, root_ang_vel, dof_vel
+REC_F4, REC_Q_CONTACT, REC_Q_VEL = 32, 16, 20   # parc_env_tables.hpp: a frame record = 32 float4; #16..19 contacts, #20.. root_vel, root_ang_vel, dof_vel
 
 
 @pytest.fixture(scope="module")

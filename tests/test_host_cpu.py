@@ -205,7 +205,7 @@ def test_build_terrain_wide_matches_reference():
 
 
 def test_ray_division_shortcut_is_exact():
-    """cell_index_rcp (parc_env.hip) == IEEE division for the grid spacings in use: every float numerator between 2^-7 and
+    """cell_index_rcp (parc_env_tables.hpp) == IEEE division for the grid spacings in use: every float numerator between 2^-7 and
     2^13 metres, both signs (the ray loop's numerators are point - terrain min, within +-8 km)."""
     import subprocess
     here = os.path.join(REPO, "oracle")
@@ -376,5 +376,25 @@ def test_env_and_dynamics_units_do_not_include_each_other():
     assert "parc_env.hip" in env and "parc_dynamics_host.hpp" in env and "parc_dynamics.hip" in dyn and "parc_dynamics_wave.hpp" in dyn
     for h in ("parc_dynamics.hpp", "parc_dynamics_coop.hpp", "parc_dynamics_wave.hpp"):
         assert h not in env, h
-    for h in ("parc_lanetab.hpp", "parc_rowmap.hpp"):
+    for h in ("parc_lanetab.hpp", "parc_rowmap.hpp", "parc_env_tables.hpp", "parc_env_post.hpp", "parc_curriculum.hpp", "parc_env_ops.hpp",
+              "parc_reset.hpp", "parc_render.hpp", "parc_render_scene.hpp"):
         assert h not in dyn, h
+
+
+CSRC_HEADERS = sorted(f for f in os.listdir(os.path.join(REPO, "parc_amd", "csrc")) if f.endswith(".hpp"))
+
+
+@pytest.mark.parametrize("header", CSRC_HEADERS)
+def test_every_header_compiles_when_included_first(header, tmp_path):
+    """Every header under parc_amd/csrc includes what it uses: a source that is nothing but its include passes hipcc's front end (host
+    and gfx950 passes), so the order of the includes in the three units does not matter."""
+    import shutil
+    import subprocess
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not (os.path.exists(hipcc) or shutil.which(hipcc)):
+        pytest.skip("hipcc not present")
+    src = tmp_path / "first.hip"
+    src.write_text('#include "%s"\n' % header)
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-I", os.path.join(REPO, "parc_amd", "csrc"), str(src)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
