@@ -849,6 +849,94 @@ int parc_maug_plan_status(ParcMotionAug *h, void *stream, int32_t *status);
 /* Device time (hipEvents; waits for the last event), ms: the last draw_plan, then layout + scan, frames + scan, terrain of the last run. */
 int parc_maug_kernel_times(ParcMotionAug *h, float *ms4);
 
+/* ---- motion generator inference: the MDM denoiser and its reverse-diffusion loop (parc_mdm_*) ------------------
+ * Inference of the reference's MDMTransformer (motion_generator/mdm_transformer.py) in eval mode and fp32, with the sampling loops of
+ * motion_generator/mdm.py (ddim_inference :932, reverse_diffusion :855, predict_x0 :836, project_dofs :990).  Three kernels:
+ * k_mdm_cond (embed_conds, once per generation), k_mdm_forward (one workgroup per sample from tokens to x_0; with guidance both passes
+ * of a step are one launch over 2 B rows) and k_mdm_update (guidance combine, project_dofs, the DDIM / DDPM step).  A sample's result
+ * does not depend on its batch.  Shapes outside the limits below are refused by parc_mdm_create, never computed. */
+#define PARC_MDM_MAX_LAYERS 8
+#define PARC_MDM_MAX_HIDDEN 8                    /* hidden widths of one MLP list */
+#define PARC_MDM_MAX_WIDTH 1024                  /* an MLP hidden width */
+#define PARC_MDM_MAX_DIM 512                     /* d_hid (a multiple of 16) */
+#define PARC_MDM_MAX_D_MODEL 416                 /* d_model (a multiple of 16): the residual stream [tokens][d_model + 4] and the score tiles share 160 KB
+                                                  * of LDS, so the limit falls with seq_len: 416 at 1 frame, 352 at 15, 208 at 64; create names the bytes */
+#define PARC_MDM_MAX_SEQ 64
+#define PARC_MDM_MAX_STEPS 4096                  /* timesteps of one parc_mdm_sample */
+#define PARC_MDM_GRID 31                         /* the tokenizer cnn_31xy_4layer_c64_out64: 31 x 31 heights -> 64 tokens of 256 */
+#define PARC_MDM_DDIM 0
+#define PARC_MDM_DDPM 1
+/* parc_mdm_forward variants (predict_x0 :836-852) */
+#define PARC_MDM_PASS_PLAIN 0                    /* fast_forward on the cached tokens, mask and indicator */
+#define PARC_MDM_PASS_GUIDED 1                   /* guidance, first pass: cached tokens and mask, the indicator forced true for the overwrite */
+#define PARC_MDM_PASS_UNCOND 2                   /* guidance, second pass: indicator row 0, previous-state tokens masked, no overwrite */
+typedef struct ParcMdm ParcMdm;
+typedef struct {
+    uint32_t struct_size;                    /* sizeof(ParcMdmParams) */
+    int32_t device;
+    ParcCharModel model;                     /* the tables parc_env_create takes (fk_paths unused) */
+    int32_t d_model, num_heads, d_hid, num_layers;
+    int32_t seq_len, num_prev_states, diffusion_timesteps;
+    int32_t frame_dim;                       /* 3 + 3 + 3 (B - 1) + dof_size + B: ROOT_POS, ROOT_ROT, JOINT_POS, JOINT_ROT, CONTACTS */
+    int32_t target_dim;                      /* 2 (XY_DIR) */
+    int32_t num_target_hidden, num_in_hidden, num_out_hidden;
+    int32_t target_hidden[PARC_MDM_MAX_HIDDEN], in_hidden[PARC_MDM_MAX_HIDDEN], out_hidden[PARC_MDM_MAX_HIDDEN];
+    int32_t max_batch;                       /* the largest B of parc_mdm_embed_conds / parc_mdm_sample */
+    /* the weights, fp32, as one flat host buffer and num_tensors + 1 offsets (floats) into it, in this order (torch layouts):
+     * conv 1..4 (weight, bias); _obs_embed (w, b); the indicator embedding [2][d]; the timestep table [timesteps][d]; the positional
+     * table [tokens][d]; time_embed.0 (w, b), time_embed.2 (w, b); per layer in_proj (w, b), out_proj (w, b), linear1 (w, b),
+     * linear2 (w, b), norm1 (w, b), norm2 (w, b); the linears (w, b) of the target MLP, of _in_mlp_gen_seq, of _out_mlp */
+    const float *weights_host;
+    const int64_t *weight_offsets_host;
+    int32_t num_tensors;
+    const float *mean_host, *std_host;       /* [seq_len][frame_dim] */
+    /* DiffusionRates, [diffusion_timesteps] each */
+    const float *sqrt_alphas_cumprod_host, *sqrt_one_minus_alphas_cumprod_host, *posterior_mean_coef1_host, *posterior_mean_coef2_host,
+                *posterior_std_host;
+} ParcMdmParams;
+typedef struct {                             /* device arrays of one batch of conditions (MDMKeyType) */
+    int32_t n;
+    const float *hf;                         /* [n][31][31], clamped and divided by max_h */
+    const float *target;                     /* [n][2] */
+    const float *prev_state;                 /* [n][num_prev_states][frame_dim], standardised */
+    const int32_t *obs_flag, *target_flag, *prev_state_flag, *noise_ind;   /* [n] 0 / 1 */
+} ParcMdmConds;
+typedef struct {
+    int32_t mode;                            /* PARC_MDM_DDIM / PARC_MDM_DDPM */
+    int32_t num_steps;
+    const int32_t *timesteps_host;           /* [num_steps], descending; a step at t = 0 returns the projected x_0 */
+    int32_t stride;                          /* DDIM: next_t = t - stride */
+    int32_t use_guidance;
+    float guidance_scale;
+    float *x;                                /* [n][seq_len][frame_dim] device: x_T in (unless draw), the sample out */
+    const float *noise;                      /* DDPM, injected: [num_steps][n][seq_len][frame_dim] device, or NULL */
+    int32_t draw;                            /* x_T (and the DDPM noise when `noise` is NULL) from Philox4x32-10 + Box-Muller keyed by */
+    uint64_t seed, first_index;              /*   (seed, first_index + sample, step): independent of the batch */
+    float *keep;                             /* [num_steps][n][seq_len][frame_dim] device: x after every step, or NULL */
+} ParcMdmSampleArgs;
+int parc_mdm_create(const ParcMdmParams *p, ParcMdm **out);
+void parc_mdm_destroy(ParcMdm *h);
+/* MDMTransformer.embed_conds: the condition tokens and the flags of the batch, cached in the handle.  tokens_out [n][65][d_model]
+ * (64 heightfield tokens, the target token) and mask_out [n] uint64 x 3 (bit j of the key-padding mask) may be NULL.  No host sync. */
+int parc_mdm_embed_conds(ParcMdm *h, const ParcMdmConds *c, float *tokens_out, uint64_t *mask_out, void *stream);
+/* One pass on the cached conditions at timestep t: x [n][seq_len][frame_dim] (its first num_prev_states frames overwritten in place
+ * where the pass's indicator is set), x0_out [n][seq_len][frame_dim].  No host sync. */
+int parc_mdm_forward(ParcMdm *h, float *x, int32_t t, int32_t pass, float *x0_out, void *stream);
+/* k_mdm_update on its own: x0 (+ guidance_scale (x0_uncond - x0) when x0_uncond is given), project_dofs, then
+ * x = c0 x0 + ct x (+ cn noise); `last` != 0 stores the projected x0 instead.  x0_proj_out may be NULL. */
+int parc_mdm_update(ParcMdm *h, int32_t n, const float *x0, const float *x0_uncond, float guidance_scale, float *x, int32_t last, float c0,
+                    float ct, float cn, const float *noise, float *x0_proj_out, void *stream);
+/* embed_conds, then num_steps x (forward, update): 1 + 2 num_steps launches, never a host sync. */
+int parc_mdm_sample(ParcMdm *h, const ParcMdmConds *c, const ParcMdmSampleArgs *a, void *stream);
+/* The standard-normal draws of (seed, first_index + sample, step) as out [n][seq_len][frame_dim]: step 0 is the x_T that parc_mdm_sample
+ * draws, step i + 1 the DDPM noise of its step i. */
+int parc_mdm_draw_noise(ParcMdm *h, int32_t n, uint64_t seed, uint64_t first_index, uint32_t step, float *out, void *stream);
+/* Device time (hipEvents; waits for the last event), ms: k_mdm_cond, the k_mdm_forward launches and the k_mdm_update launches of the
+ * last parc_mdm_sample (summed). */
+int parc_mdm_kernel_times(ParcMdm *h, float *ms3);
+/* VGPRs are the compiler's; this is what the handle chose: dynamic LDS bytes of k_mdm_forward, its grid (resident slots), scratch floats per slot. */
+int parc_mdm_describe(ParcMdm *h, int64_t *out3);
+
 #ifdef __cplusplus
 }
 #endif

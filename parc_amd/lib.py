@@ -230,6 +230,34 @@ BUFFER_FIELDS = [
 ]
 
 
+MDM_MAX_LAYERS, MDM_MAX_HIDDEN, MDM_MAX_WIDTH, MDM_MAX_DIM, MDM_MAX_SEQ, MDM_MAX_STEPS, MDM_GRID = 8, 8, 1024, 512, 64, 4096, 31   # PARC_MDM_*
+MDM_DDIM, MDM_DDPM = 0, 1
+MDM_PASS_PLAIN, MDM_PASS_GUIDED, MDM_PASS_UNCOND = 0, 1, 2
+
+
+class ParcMdmParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("model", ParcCharModel),
+                ("d_model", C.c_int32), ("num_heads", C.c_int32), ("d_hid", C.c_int32), ("num_layers", C.c_int32),
+                ("seq_len", C.c_int32), ("num_prev_states", C.c_int32), ("diffusion_timesteps", C.c_int32),
+                ("frame_dim", C.c_int32), ("target_dim", C.c_int32),
+                ("num_target_hidden", C.c_int32), ("num_in_hidden", C.c_int32), ("num_out_hidden", C.c_int32),
+                ("target_hidden", C.c_int32 * MDM_MAX_HIDDEN), ("in_hidden", C.c_int32 * MDM_MAX_HIDDEN), ("out_hidden", C.c_int32 * MDM_MAX_HIDDEN),
+                ("max_batch", C.c_int32), ("weights_host", f32p), ("weight_offsets_host", i64p), ("num_tensors", C.c_int32),
+                ("mean_host", f32p), ("std_host", f32p), ("sqrt_alphas_cumprod_host", f32p), ("sqrt_one_minus_alphas_cumprod_host", f32p),
+                ("posterior_mean_coef1_host", f32p), ("posterior_mean_coef2_host", f32p), ("posterior_std_host", f32p)]
+
+
+class ParcMdmConds(C.Structure):
+    _fields_ = [("n", C.c_int32), ("hf", C.c_void_p), ("target", C.c_void_p), ("prev_state", C.c_void_p), ("obs_flag", C.c_void_p),
+                ("target_flag", C.c_void_p), ("prev_state_flag", C.c_void_p), ("noise_ind", C.c_void_p)]
+
+
+class ParcMdmSampleArgs(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("num_steps", C.c_int32), ("timesteps_host", i32p), ("stride", C.c_int32), ("use_guidance", C.c_int32),
+                ("guidance_scale", C.c_float), ("x", C.c_void_p), ("noise", C.c_void_p), ("draw", C.c_int32), ("seed", C.c_uint64),
+                ("first_index", C.c_uint64), ("keep", C.c_void_p)]
+
+
 class ParcEnvBuffers(C.Structure):
     _fields_ = [(n, {"f": f32p, "i": i32p, "l": i64p}[t]) for n, t in BUFFER_FIELDS]
 
@@ -366,6 +394,16 @@ def load():
     lib.parc_maug_get_result.argtypes = [vp, C.POINTER(ParcMotionAugOutputs), vp]
     lib.parc_maug_plan_status.argtypes = [vp, vp, i32p]
     lib.parc_maug_kernel_times.argtypes = [vp, f32p]
+    lib.parc_mdm_create.argtypes = [C.POINTER(ParcMdmParams), C.POINTER(vp)]
+    lib.parc_mdm_destroy.argtypes = [vp]
+    lib.parc_mdm_destroy.restype = None
+    lib.parc_mdm_embed_conds.argtypes = [vp, C.POINTER(ParcMdmConds), vp, vp, vp]
+    lib.parc_mdm_forward.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp]
+    lib.parc_mdm_update.argtypes = [vp, C.c_int32, vp, vp, C.c_float, vp, C.c_int32, C.c_float, C.c_float, C.c_float, vp, vp, vp]
+    lib.parc_mdm_sample.argtypes = [vp, C.POINTER(ParcMdmConds), C.POINTER(ParcMdmSampleArgs), vp]
+    lib.parc_mdm_draw_noise.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp]
+    lib.parc_mdm_kernel_times.argtypes = [vp, f32p]
+    lib.parc_mdm_describe.argtypes = [vp, i64p]
     _lib = lib
     return lib
 
@@ -390,6 +428,8 @@ EXPORTED_SYMBOLS = [
     "parc_tgen_create", "parc_tgen_destroy", "parc_tgen_draw_plan", "parc_tgen_generate_with", "parc_tgen_generate", "parc_tgen_kernel_times",
     "parc_maug_create", "parc_maug_destroy", "parc_maug_set_clips", "parc_maug_draw_plan", "parc_maug_augment_with", "parc_maug_augment",
     "parc_maug_get_result", "parc_maug_plan_status", "parc_maug_kernel_times",
+    "parc_mdm_create", "parc_mdm_destroy", "parc_mdm_embed_conds", "parc_mdm_forward", "parc_mdm_update", "parc_mdm_sample",
+    "parc_mdm_draw_noise", "parc_mdm_kernel_times", "parc_mdm_describe",
 ]
 
 # parc_test_quat_op selectors (include/parc_env.h)
