@@ -898,7 +898,7 @@ typedef struct {                             /* device arrays of one batch of co
     int32_t n;
     const float *hf;                         /* [n][31][31], clamped and divided by max_h */
     const float *target;                     /* [n][2] */
-    const float *prev_state;                 /* [n][num_prev_states][frame_dim], standardised */
+    const float *prev_state;                 /* [n][num_prev_states][frame_dim], standardised; may be null when num_prev_states is 0 */
     const int32_t *obs_flag, *target_flag, *prev_state_flag, *noise_ind;   /* [n] 0 / 1 */
 } ParcMdmConds;
 typedef struct {

@@ -653,7 +653,8 @@ extern "C" int parc_mdm_create(const ParcMdmParams *p, ParcMdm **out) {
 static int mdm_check_conds(ParcMdm *h, const ParcMdmConds *c) {
     if (!h || !c) return fail(PARC_ERR_INVALID, "mdm: null argument");
     if (c->n < 1 || c->n > h->params.max_batch) return fail(PARC_ERR_INVALID, "mdm: the batch must be 1 .. max_batch = " + std::to_string(h->params.max_batch));
-    if (!c->hf || !c->target || !c->prev_state || !c->obs_flag || !c->target_flag || !c->prev_state_flag || !c->noise_ind)
+    // with num_prev_states = 0 the previous state is [n][0][D]: nothing reads it, and an empty tensor's pointer is null
+    if (!c->hf || !c->target || (!c->prev_state && h->params.num_prev_states > 0) || !c->obs_flag || !c->target_flag || !c->prev_state_flag || !c->noise_ind)
         return fail(PARC_ERR_INVALID, "mdm: null condition array");
     return PARC_OK;
 }

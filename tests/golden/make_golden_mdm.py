@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""Generate the motion-generator fixtures (``mdm_weights.npz``, ``mdm_cases.npz``) from the REAL reference.
+"""Generate the motion-generator fixtures from the REAL reference: ``mdm_weights.npz`` / ``mdm_cases.npz`` (shape ``default``) and
+``mdm_edge.npz`` (shape ``edge``, weights and cases in one file).
 
 Run where the reference checkout is available (the tests only read the fixtures it writes):
 
-    python tests/golden/make_golden_mdm.py
+    python tests/golden/make_golden_mdm.py [default | edge]
 
-The reference's ``MDM`` / ``MDMTransformer`` are instantiated on the CPU as ``make_golden_motion_sampler.py`` drives its sampler (a
+Shape ``default``.  The reference's ``MDM`` / ``MDMTransformer`` are instantiated on the CPU as ``make_golden_motion_sampler.py`` drives its sampler (a
 ``parc`` package alias, empty module stubs) from the reference's default generator config at a small size: d_model 64, 4 heads, d_hid 64,
 2 layers, MLP lists [32] / [64] / [64], 15 frames, 21 timesteps.  ``in_proj_weight`` is multiplied by 4 so that the attention is far from
 uniform; the feature mean is random, the std in [0.5, 2].  Six rows cover every flag: heightfield off, target off, previous state masked,
@@ -15,6 +16,13 @@ tensor (``name_err32``), the yardstick and the unit of the tests' bounds: embed_
 guidance, project_dofs (of step_noise[0] / 4), ddim_inference and the steps of reverse_diffusion (denoise_one_timestep) at the timesteps [20, 10, 0] with injected x_T and noise (every
 intermediate x), gen_sequence with and without guidance; and the reference's ``DiffusionRates`` tables (``rates_*``, fp32).  The script asserts that fp32 and float64 agree to 1e-4 on every tensor (an
 exp-map round trip can sit on a branch cut: pick another SEED until it does).
+
+Shape ``edge`` pins the restatement off that shape: d_model 32, 2 heads, d_hid 48 (not d_model), 2 layers, 20 frames (two row tiles of
+frames), 3 previous states, MLP lists [] / [40, 24] / [24] (no hidden layer, two, one; widths that are no multiple of 16).  It records
+the tokens and the mask, fast_forward at t = 20 (the last row of the timestep table) and t = 0, predict_x0 with guidance at t = 20 and
+guided ddim_inference at [20, 10, 0] (every step), in the same format; its state dict is stored under ``sd/`` keys of the same file.
+The tokenizer's convolutions alone are 310 KB of the file, so to stay under the size of ``mdm_weights.npz`` two of the computed tensors
+are checked but not stored: fast_forward at t = 0 and predict_x0, whose arithmetic the loop's last and first step contain.
 """
 import os
 import sys
@@ -50,25 +58,35 @@ N = 6
 TS3 = [20, 10, 0]
 STRIDE = 10
 SCALE = 1.5
+# per shape: the overrides of the reference's default config, the two timesteps of fast_forward, the timestep of predict_x0, what is
+# recorded beyond the network ("loops": project_dofs, both loops plain and guided, gen_sequence; "ddim_guided": that loop only)
+SHAPES = {
+    "default": dict(cfg=dict(seq_len=15, d_model=64, num_heads=4, d_hid=64, num_layers=2, target_mlp_layers=[32], in_mlp_layers=[64], out_mlp_layers=[64]),
+                    forward_ts=(10, 0), guided_t=10, record="loops", seed=0),
+    "edge": dict(cfg=dict(seq_len=20, num_prev_states=3, d_model=32, num_heads=2, d_hid=48, num_layers=2, target_mlp_layers=[], in_mlp_layers=[40, 24],
+                          out_mlp_layers=[24]),
+                 forward_ts=(20, 0), guided_t=20, record="ddim_guided", seed=0, drop=("forward_t0", "predict_x0")),
+}
 FLAGS = [(1, 1, 1, 1), (0, 1, 1, 1), (1, 0, 1, 0), (1, 1, 0, 1), (0, 0, 0, 0), (1, 1, 1, 0)]   # obs, target, prev, indicator
 
 
-def build(dtype):
+def build(dtype, shape):
     with open(os.path.join(REF, "data/configs/parc_1_train_gen_default.yaml")) as f:
         cfg = yaml.safe_load(f)
-    cfg.update(device="cpu", use_wandb=False, char_file=os.path.join(REPO, "data/assets/humanoid.xml"), seq_len=15, d_model=64, num_heads=4,
-               d_hid=64, num_layers=2, target_mlp_layers=[32], in_mlp_layers=[64], out_mlp_layers=[64])
-    torch.manual_seed(SEED)
+    cfg.update(device="cpu", use_wandb=False, char_file=os.path.join(REPO, "data/assets/humanoid.xml"))
+    cfg.update(shape["cfg"])
+    T = cfg["seq_len"]
+    torch.manual_seed(shape["seed"])
     m = ref_mdm.MDM(cfg)
     m._denoise_model.eval()
     with torch.no_grad():
         for k, v in m._denoise_model.state_dict().items():
             if k.endswith("in_proj_weight"):
                 v.mul_(4.0)
-    g = torch.Generator().manual_seed(SEED + 1)
+    g = torch.Generator().manual_seed(shape["seed"] + 1)
     D = m._motion_frame_dof
-    m._mdm_features_mean = torch.randn((15, D), generator=g) * 0.3
-    m._mdm_features_std = torch.rand((15, D), generator=g) * 1.5 + 0.5
+    m._mdm_features_mean = torch.randn((T, D), generator=g) * 0.3
+    m._mdm_features_std = torch.rand((T, D), generator=g) * 1.5 + 0.5
     if dtype == torch.float64:
         m._denoise_model.double()
         m._mdm_features_mean, m._mdm_features_std = m._mdm_features_mean.double(), m._mdm_features_std.double()
@@ -88,8 +106,8 @@ def build(dtype):
     return m, cfg
 
 
-def inputs(D):
-    g = torch.Generator().manual_seed(SEED + 2)
+def inputs(D, T, nprev, seed):
+    g = torch.Generator().manual_seed(seed + 2)
     fl = torch.tensor(FLAGS, dtype=torch.bool)
     hf = torch.randn((N, 31, 31), generator=g) * 1.2
     hf[0, :4] = 4.5                                                # beyond +-max_h = 3
@@ -97,8 +115,8 @@ def inputs(D):
     tgt = torch.randn((N, 2), generator=g)
     tgt = tgt / tgt.norm(dim=-1, keepdim=True)
     h16 = lambda a: a.half().float()                               # stored as fp16, exactly
-    return dict(hf_m=h16(hf), target=tgt, prev=h16(torch.randn((N, 2, D), generator=g) * 0.5), flags=fl, x=h16(torch.randn((N, 15, D), generator=g)),
-                step_noise=h16(torch.randn((3, N, 15, D), generator=g)))
+    return dict(hf_m=h16(hf), target=tgt, prev=h16(torch.randn((N, nprev, D), generator=g) * 0.5), flags=fl, x=h16(torch.randn((N, T, D), generator=g)),
+                step_noise=h16(torch.randn((3, N, T, D), generator=g)))
 
 
 def conds(m, inp, dtype, scale=None):
@@ -113,7 +131,7 @@ def conds(m, inp, dtype, scale=None):
     return c
 
 
-def record(m, inp, dtype):
+def record(m, inp, dtype, shape):
     out = {}
     net = m._denoise_model
     n = N
@@ -122,7 +140,7 @@ def record(m, inp, dtype):
         mask = net.create_key_padding_mask(n, "cpu")
         tokens = net.embed_conds(c, mask)
         out["tokens"], out["mask"] = torch.cat(tokens, dim=1), mask
-        for t in (10, 0):
+        for t in shape["forward_ts"]:
             x = inp["x"].clone().to(dtype)
             tt = t * torch.ones((n, 1, 1), dtype=torch.int64)
             out[f"forward_t{t}"] = net.fast_forward(x, c, tt, tokens, mask)
@@ -131,8 +149,13 @@ def record(m, inp, dtype):
         mask = net.create_key_padding_mask(n, "cpu")
         tokens = net.embed_conds(c, mask)
         x = inp["x"].clone().to(dtype)
-        out["predict_x0"] = m.predict_x0(x, c, 10 * torch.ones((n, 1, 1), dtype=torch.int64), tokens, mask)
+        out["predict_x0"] = m.predict_x0(x, c, shape["guided_t"] * torch.ones((n, 1, 1), dtype=torch.int64), tokens, mask)
         out["predict_x0_x"] = x
+        if shape["record"] == "ddim_guided":
+            c = conds(m, inp, dtype, SCALE)
+            c["timesteps"] = TS3
+            out["ddim_guided"] = torch.stack(m.ddim_inference(c, noise=inp["x"].clone().to(dtype), stride=STRIDE, keep_all_samples=True)[1:])
+            return out
         out["project_dofs"] = m.project_dofs((inp["step_noise"][0] * 0.25).to(dtype))   # an input both precisions hold exactly
         for name, scale in (("plain", None), ("guided", SCALE)):
             c = conds(m, inp, dtype, scale)
@@ -172,12 +195,13 @@ def record(m, inp, dtype):
     return out
 
 
-def main():
-    m32, cfg = build(torch.float32)
-    m64, _ = build(torch.float64)
-    D = m32._motion_frame_dof
-    inp = inputs(D)
-    r32, r64 = record(m32, inp, torch.float32), record(m64, inp, torch.float64)
+def main(name="default", out_dir=HERE):
+    shape = SHAPES[name]
+    m32, cfg = build(torch.float32, shape)
+    m64, _ = build(torch.float64, shape)
+    D, T, nprev = m32._motion_frame_dof, cfg["seq_len"], cfg["num_prev_states"]
+    inp = inputs(D, T, nprev, shape["seed"])
+    r32, r64 = record(m32, inp, torch.float32, shape), record(m64, inp, torch.float64, shape)
     worst = 0.0
     for k in r32:
         if r32[k].dtype == torch.bool:
@@ -190,12 +214,12 @@ def main():
     # x after a pass is the input with the clean previous state where the pass's indicator is set: asserted here, rebuilt by the tests
     ind = inp["flags"][:, 3]
     want = inp["x"].clone()
-    want[ind, :2] = inp["prev"][ind]
-    assert torch.equal(r32["forward_t10_x"], want) and torch.equal(r32["forward_t0_x"], want)
-    want[:, :2] = inp["prev"]
+    want[ind, :nprev] = inp["prev"][ind]
+    assert all(torch.equal(r32[f"forward_t{t}_x"], want) for t in shape["forward_ts"])
+    want[:, :nprev] = inp["prev"]
     assert torch.equal(r32["predict_x0_x"], want)
     sd = {k: v.detach().cpu().numpy() for k, v in m32._denoise_model.state_dict().items()}
-    np.savez_compressed(os.path.join(HERE, "mdm_weights.npz"), features_mean=m32._mdm_features_mean.numpy(), features_std=m32._mdm_features_std.numpy(), **sd)
+    weights = dict(features_mean=m32._mdm_features_mean.numpy(), features_std=m32._mdm_features_std.numpy())
     arrs = {"hf_m": inp["hf_m"].numpy(), "target": inp["target"].numpy(), "prev": inp["prev"].numpy(), "flags": inp["flags"].numpy(),
             "x": inp["x"].numpy(), "step_noise": inp["step_noise"].numpy(), "timesteps": np.asarray(TS3, np.int32), "stride": np.int32(STRIDE),
             "scale": np.float32(SCALE), "max_h": np.float32(m32._max_h)}
@@ -219,11 +243,26 @@ def main():
             "out_mlp_layers", "features", "use_heightmap_obs", "use_target_obs", "target_type", "predict_mode", "heightmap", "cnn")
     import json
     arrs["cfg_json"] = np.frombuffer(json.dumps({k: cfg[k] for k in keep}).encode(), dtype=np.uint8)
-    np.savez_compressed(os.path.join(HERE, "mdm_cases.npz"), **arrs)
-    for f in ("mdm_weights.npz", "mdm_cases.npz"):
-        print(f, os.path.getsize(os.path.join(HERE, f)), "bytes")
+    if name == "default":
+        np.savez_compressed(os.path.join(out_dir, "mdm_weights.npz"), **weights, **sd)
+        np.savez_compressed(os.path.join(out_dir, "mdm_cases.npz"), **arrs)
+        files = ("mdm_weights.npz", "mdm_cases.npz")
+    else:                                                          # one file: the cases, the feature statistics, the state dict under sd/
+        # left out: the input no recorded tensor reads, the rate tables (the default file holds the same 21 rows) and the tensors the
+        # shape drops to stay under the size of mdm_weights.npz (their fp32-vs-float64 check above still ran)
+        for k in [k for k in arrs if k == "step_noise" or k.startswith("rates_") or k.rsplit("_", 1)[0] in shape["drop"]]:
+            del arrs[k]
+        np.savez_compressed(os.path.join(out_dir, "mdm_%s.npz" % name), **arrs, **weights, **{"sd/" + k: v for k, v in sd.items()})
+        files = ("mdm_%s.npz" % name,)
+    for f in files:
+        print(f, os.path.getsize(os.path.join(out_dir, f)), "bytes")
+        # a regenerated fixture is the committed one byte for byte (written elsewhere: compared; written in place: git shows it)
+        if os.path.abspath(out_dir) != HERE and os.path.exists(os.path.join(HERE, f)):
+            with open(os.path.join(out_dir, f), "rb") as a, open(os.path.join(HERE, f), "rb") as b:
+                assert a.read() == b.read(), f + " differs from the committed fixture"
+            print(f, "is the committed file byte for byte")
     print("worst fp32 vs float64: %.3e" % worst)
 
 
 if __name__ == "__main__":
-    main()
+    main(*sys.argv[1:3])

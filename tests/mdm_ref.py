@@ -207,27 +207,33 @@ def to_keys(c):
             "PREV_STATE_FLAG_KEY": c["prev_flag"], "PREV_STATE_NOISE_IND_KEY": c["ind"]}
 
 
-# ---- the fixture of tests/golden/make_golden_mdm.py -------------------------------------------------------------------------------------
+# ---- the fixtures of tests/golden/make_golden_mdm.py ------------------------------------------------------------------------------------
 class Fixture:
-    """``mdm_weights.npz`` / ``mdm_cases.npz``: the config, the state dict, the inputs, and per recorded tensor the reference's float64
-    values (``ref64[name]``, from fixed point) and the largest difference of the reference's own fp32 run from them (``err32[name]``)."""
+    """A record of the reference: the config, the state dict, the inputs, and per recorded tensor the reference's float64 values
+    (``ref64[name]``, from fixed point) and the largest difference of the reference's own fp32 run from them (``err32[name]``).
+    ``cases`` / ``weights`` name the files: ``mdm_cases.npz`` / ``mdm_weights.npz`` (the default shape), or one file for both, which
+    holds its state dict under ``sd/`` keys (``mdm_edge.npz``)."""
 
-    def __init__(self, golden_dir):
+    def __init__(self, golden_dir, cases="mdm_cases.npz", weights="mdm_weights.npz"):
         import json
         import os
-        w = np.load(os.path.join(golden_dir, "mdm_weights.npz"))
-        c = np.load(os.path.join(golden_dir, "mdm_cases.npz"))
+        w = np.load(os.path.join(golden_dir, weights))
+        c = np.load(os.path.join(golden_dir, cases))
         self.cfg = dict(json.loads(bytes(c["cfg_json"]).decode()), char_file="data/assets/humanoid.xml")
         self.mean, self.std = torch.from_numpy(w["features_mean"]), torch.from_numpy(w["features_std"])
-        self.sd = {k: torch.from_numpy(w[k]) for k in w.files if k not in ("features_mean", "features_std")}
+        if weights == cases:
+            self.sd = {k[3:]: torch.from_numpy(w[k]) for k in w.files if k.startswith("sd/")}
+        else:
+            self.sd = {k: torch.from_numpy(w[k]) for k in w.files if k not in ("features_mean", "features_std")}
         self.max_h, self.scale, self.stride = float(c["max_h"]), float(c["scale"]), int(c["stride"])
         self.timesteps = [int(t) for t in c["timesteps"]]
-        self.hf_m, self.prev, self.x, self.step_noise = [torch.from_numpy(c[k].astype(np.float32)) for k in ("hf_m", "prev", "x", "step_noise")]
+        self.hf_m, self.prev, self.x = [torch.from_numpy(c[k].astype(np.float32)) for k in ("hf_m", "prev", "x")]
+        self.step_noise = torch.from_numpy(c["step_noise"].astype(np.float32)) if "step_noise" in c.files else None
         self.target, self.flags, self.mask = torch.from_numpy(c["target"]), torch.from_numpy(c["flags"]), torch.from_numpy(c["mask"])
         self.ref64 = {k[:-4]: torch.from_numpy(c[k].astype(np.float64) / 2.0 ** 28) for k in c.files if k.endswith("_q28")}
         self.err32 = {k[:-6]: float(c[k]) for k in c.files if k.endswith("_err32")}
         self.n = self.x.shape[0]
-        self.rates = {k[6:]: torch.from_numpy(c[k]) for k in c.files if k.startswith("rates_")}   # the reference's DiffusionRates(21), fp32
+        self.rates = {k[6:]: torch.from_numpy(c[k]) for k in c.files if k.startswith("rates_")}   # the reference's DiffusionRates(21), fp32 (the default shape's file)
 
     def conds(self, scale=None):
         f = self.flags

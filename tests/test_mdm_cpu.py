@@ -92,6 +92,29 @@ def test_positional_tables_bit_for_bit(fx):
         assert torch.equal(mg.positional_table(want.shape[1], want.shape[2]), want), key
 
 
+def test_ref_against_the_edge_record():
+    """``mdm_ref`` off the default shape, against the reference's record at d_model 32, d_hid 48, 20 frames, 3 previous states and MLP
+    lists [] / [40, 24] / [24] (``mdm_edge.npz``): the ``model.{3 i}`` keys of zero, two and one hidden layer, the positional table at
+    another length and width, the mask range of three previous states, the last row of the timestep table."""
+    fx = R.Fixture(os.path.join(REPO, "tests/golden"), "mdm_edge.npz", "mdm_edge.npz")
+    cfg = fx.cfg
+    assert (cfg["d_model"], cfg["d_hid"], cfg["seq_len"], cfg["num_prev_states"]) == (32, 48, 20, 3)
+    assert (cfg["target_mlp_layers"], cfg["in_mlp_layers"], cfg["out_mlp_layers"]) == ([], [40, 24], [24])
+    assert set(fx.ref64) == {"tokens", "forward_t20", "ddim_guided"} and fx.timesteps == [20, 10, 0]
+    ref64 = R.MdmRef(cfg, fx.sd, fx.mean, fx.std, torch.float64)
+    tokens, mask = ref64.embed_conds(fx.conds())
+    assert torch.equal(mask, fx.mask) and mask.shape == (fx.n, 87)
+    near("tokens", tokens, fx)
+    x = fx.x.clone().double()
+    near("forward_t20", ref64.fast_forward(x, fx.conds(), 20, tokens, mask), fx)
+    assert torch.equal(x.float(), fx.x_after(False))
+    near("ddim_guided", fx.as_recorded(ref64.ddim(fx.conds(fx.scale), fx.x, fx.stride, fx.timesteps), True), fx)
+    for key in ("_in_pos_encoding.pe", "_embed_t.sequence_pos_encoder.pe"):
+        want = fx.sd[key]
+        assert torch.equal(mg.positional_table(want.shape[1], want.shape[2]), want), key
+    assert fx.sd["_in_pos_encoding.pe"].shape == (1, 87, 32) and mg.tensor_order(cfg) == [k for k in mg.tensor_order(cfg) if k in fx.sd]
+
+
 def test_checkpoint_loader_reads_the_reference_layout(fx, tmp_path):
     ema = {k: v + 1 for k, v in fx.sd.items()}
     ck = {"cfg": fx.cfg, "model": fx.sd, "ema_model": ema, "optimizer": {},
