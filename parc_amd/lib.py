@@ -79,6 +79,9 @@ class ParcRenderParams(C.Structure):
                 ("draw_ref", C.c_int32), ("shadows", C.c_int32), ("debug_visuals", C.c_int32)]
 
 
+MOPT_NUM_TERMS, MOPT_MAX_POINTS = 9, 512   # PARC_MOPT_*
+
+
 class ParcMotionOptParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("model", ParcCharModel), ("num_points", C.c_int32),
                 ("points_host", f32p), ("point_body_host", i32p), ("geom0_type", C.c_int32 * MAX_BODIES),
@@ -105,6 +108,9 @@ class ParcMotionOptClips(C.Structure):
 
 
 MSAMP_MAX_FRAMES, MSAMP_MAX_GRID, MSAMP_MAX_TERRAIN_CELLS, MSAMP_MAX_BOXES, MSAMP_BOX_FLOATS = 64, 32, 512 * 512, 64, 6   # PARC_MSAMP_*
+MSAMP_RELATIVE_Z = {"RELATIVE_TO_ROOT": 0, "RELATIVE_TO_ROOT_FLOOR": 1}                               # PARC_MSAMP_RELATIVE_TO_*
+MSAMP_AUG_MODE = {"NOISE": 0, "MAXPOOL_AND_BOXES": 1, "NONE": 2}                                    # PARC_MSAMP_AUG_*
+MSAMP_POOL_NONE, MSAMP_POOL_2D, MSAMP_POOL_1D_X, MSAMP_POOL_1D_Y = 0, 1, 2, 3                       # PARC_MSAMP_POOL_*
 MSAMP_STATUS = {1: "motion_id outside the library", 2: "num_boxes outside [0, max_num_boxes]", 4: "pool kind or size out of range"}
 
 
@@ -262,6 +268,144 @@ class ParcEnvBuffers(C.Structure):
     _fields_ = [(n, {"f": f32p, "i": i32p, "l": i64p}[t]) for n, t in BUFFER_FIELDS]
 
 
+def _signatures():
+    """``name -> (restype, argtypes)`` of every function ``include/parc_env.h`` declares, in the header's order and sections.  ``load()``
+    applies it, and a name without a row fails the export check, so no function is left to ctypes' defaults by accident."""
+    P = C.POINTER
+    vp, i32, i64, u32, u64, f32, cstr = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_char_p
+    rc = C.c_int   # the return code that check() reads (the counts that three getters return are ints too)
+    u8p, u32p = P(C.c_uint8), P(u32)
+    plan_s, out_s = P(ParcMotionSamplerPlan), P(ParcMotionSamplerOutputs)
+    return {
+        # version
+        "parc_last_error": (cstr, []),
+        "parc_abi_version": (rc, []),
+        # env: lifecycle, loads, buffers
+        "parc_env_create": (rc, [P(ParcEnvConfig), P(vp)]),
+        "parc_env_destroy": (None, [vp]),
+        "parc_env_obs_dim": (rc, [vp]),
+        "parc_env_load_motions": (rc, [vp, P(ParcMotionClips)]),
+        "parc_env_load_terrain": (rc, [vp, f32p, i32, i32, f32, f32, f32, f32, f32p, i32, i32]),
+        "parc_env_bind_buffers": (rc, [vp, P(ParcEnvBuffers)]),
+        "parc_env_get_buffers": (rc, [vp, P(ParcEnvBuffers)]),
+        # env: step and resets
+        "parc_env_step": (rc, [vp, vp, vp]),
+        "parc_env_reset": (rc, [vp, vp, i32, vp]),
+        "parc_env_reset_with": (rc, [vp, vp, i32, vp, vp, vp, vp, vp]),
+        "parc_env_reset_done": (rc, [vp, vp]),
+        "parc_env_compute_obs": (rc, [vp, vp, i32, vp]),
+        # env: curriculum and reset settings
+        "parc_env_get_fail_rates": (rc, [vp, f32p, i32]),
+        "parc_env_set_fail_rates": (rc, [vp, f32p, i32]),
+        "parc_env_get_motion_info": (rc, [vp, f32p, f32p, i32]),
+        "parc_env_set_never_done": (rc, [vp, i32]),
+        "parc_env_set_rand_reset": (rc, [vp, i32, i32, f32]),
+        "parc_env_set_start_time_fraction": (rc, [vp, vp]),
+        # device ops on the env's character and motion library
+        "parc_dof_to_rot": (rc, [vp, vp, vp, i32, vp]),
+        "parc_rot_to_dof": (rc, [vp, vp, vp, i32, vp]),
+        "parc_forward_kinematics": (rc, [vp, vp, vp, vp, vp, vp, i32, vp]),
+        "parc_calc_motion_frame": (rc, [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "parc_test_quat_op": (rc, [i32, vp, vp, vp, i32, vp, vp]),
+        # build and diagnostics
+        "parc_build_flags": (cstr, []),
+        "parc_env_get_frame_vel_tables": (rc, [vp, f32p, f32p, f32p]),
+        "parc_env_profile_step": (rc, [vp, vp, vp, i32, f32p, f32p]),
+        "parc_env_describe": (cstr, [vp]),
+        "parc_env_dynamics_timeouts": (rc, [vp]),
+        "parc_env_health_words": (u32p, [vp]),
+        "parc_env_dynamics_manifold_drops": (rc, [vp]),
+        "parc_env_last_dynamics_ms": (f32, [vp]),
+        "parc_env_set_episode_length": (rc, [vp, f32]),
+        # captured step + reset
+        "parc_env_bind_action": (rc, [vp, vp]),
+        "parc_env_step_reset_graph": (rc, [vp, vp]),
+        # learner kernels
+        "parc_td_lambda_return": (rc, [vp, vp, vp, f32, f32, i32, i32, vp, vp]),
+        "parc_normalize_record": (rc, [vp, vp, vp, f32, vp, vp, i64, i32, vp]),
+        "parc_gather_rows": (rc, [i32, P(vp), P(vp), i64p, vp, i64, i64, vp]),
+        # recording
+        "parc_env_record_bind": (rc, [vp, vp, vp, i32, vp, vp, vp, i32]),
+        "parc_env_record_frame": (rc, [vp, vp]),
+        # kernel timing and kernel names
+        "parc_env_set_kernel_timing": (rc, [vp, i32]),
+        "parc_env_get_kernel_timing": (rc, [vp, f64p, f64p, P(i32)]),
+        "parc_env_get_kernel_timing_samples": (rc, [vp, f32p, f32p, f32p, i32, P(i32)]),
+        "parc_env_dynamics_kernel": (cstr, [vp]),
+        "parc_env_post_kernel": (cstr, [vp]),
+        # render
+        "parc_env_render": (rc, [vp, P(ParcRenderParams), vp, i32, vp, vp, vp, vp]),
+        "parc_env_render_scene": (rc, [vp, P(ParcRenderParams), i32, vp, i32, vp, vp, vp, vp, vp]),
+        # motion optimiser
+        "parc_mopt_create": (rc, [P(ParcMotionOptParams), P(vp)]),
+        "parc_mopt_destroy": (None, [vp]),
+        "parc_mopt_set_clips": (rc, [vp, P(ParcMotionOptClips)]),
+        "parc_mopt_set_constraint_points": (rc, [vp, f32p]),
+        "parc_mopt_set_params": (rc, [vp, f32p]),
+        "parc_mopt_get_params": (rc, [vp, f32p]),
+        "parc_mopt_loss_and_grad": (rc, [vp, f32p, f32p]),
+        "parc_mopt_step": (rc, [vp, i32, f32p]),
+        "parc_mopt_get_frames": (rc, [vp, f32p, f32p, f32p]),
+        "parc_mopt_get_source_body": (rc, [vp, f32p, f32p]),
+        "parc_mopt_build_constraints": (rc, [vp, i32, i32p, f32p, i32, f32]),
+        "parc_mopt_kernel_times": (rc, [vp, f32p]),
+        # motion-terrain analysis
+        "parc_mterr_create": (rc, [P(ParcMotionTerrainParams), P(vp)]),
+        "parc_mterr_destroy": (None, [vp]),
+        "parc_mterr_set_clips": (rc, [vp, P(ParcMotionOptClips)]),
+        "parc_mterr_run": (rc, [vp, f32p, i32p, f32p, P(i64)]),
+        "parc_mterr_get_mask_inds": (rc, [vp, i32p]),
+        "parc_mterr_get_min_heights": (rc, [vp, f32p, i32p]),
+        "parc_mterr_point_sdf": (rc, [vp, i64, i32, f32p, f32p]),
+        "parc_mterr_kernel_times": (rc, [vp, f32p]),
+        # motion-window sampler
+        "parc_msamp_create": (rc, [P(ParcMotionSamplerParams), P(vp)]),
+        "parc_msamp_destroy": (None, [vp]),
+        "parc_msamp_set_clips": (rc, [vp, P(ParcMotionOptClips), P(ParcMotionSamplerClipInfo)]),
+        "parc_msamp_sample_with": (rc, [vp, plan_s, out_s, vp]),
+        "parc_msamp_draw_plan": (rc, [vp, u64, plan_s, vp]),
+        "parc_msamp_sample": (rc, [vp, u64, plan_s, out_s, vp]),
+        "parc_msamp_enumerate": (rc, [vp, i32, out_s, vp]),
+        "parc_msamp_plan_status": (rc, [vp, vp, i32p]),
+        "parc_msamp_kernel_times": (rc, [vp, f32p]),
+        # path planner
+        "parc_pathplan_create": (rc, [P(ParcPathPlanParams), P(vp)]),
+        "parc_pathplan_destroy": (None, [vp]),
+        "parc_pathplan_run": (rc, [vp, i32, f32p, i32p, i32p, u64, u64, P(ParcPathPlanOutputs)]),
+        "parc_pathplan_get_graph": (rc, [vp, i32, i32, u8p, u8p, u32p]),
+        "parc_pathplan_kernel_times": (rc, [vp, f32p]),
+        # terrain generator
+        "parc_tgen_create": (rc, [P(ParcTerrainGenParams), P(vp)]),
+        "parc_tgen_destroy": (None, [vp]),
+        "parc_tgen_draw_plan": (rc, [vp, u64, u64, P(ParcTerrainGenPlan), vp]),
+        "parc_tgen_generate_with": (rc, [vp, P(ParcTerrainGenPlan), vp, i32, vp]),
+        "parc_tgen_generate": (rc, [vp, i32, u64, u64, vp, vp]),
+        "parc_tgen_kernel_times": (rc, [vp, f32p]),
+        # motion-terrain augmenter
+        "parc_maug_create": (rc, [P(ParcMotionAugParams), P(vp)]),
+        "parc_maug_destroy": (None, [vp]),
+        "parc_maug_set_clips": (rc, [vp, P(ParcMotionOptClips), P(ParcMotionAugClipInfo)]),
+        "parc_maug_draw_plan": (rc, [vp, u64, u64, i32, P(ParcMotionAugPlan), vp]),
+        "parc_maug_augment_with": (rc, [vp, P(ParcMotionAugPlan), i32, vp, P(ParcMotionAugSizes)]),
+        "parc_maug_augment": (rc, [vp, i32, u64, u64, i32, vp, P(ParcMotionAugSizes)]),
+        "parc_maug_get_result": (rc, [vp, P(ParcMotionAugOutputs), vp]),
+        "parc_maug_plan_status": (rc, [vp, vp, i32p]),
+        "parc_maug_kernel_times": (rc, [vp, f32p]),
+        # motion generator
+        "parc_mdm_create": (rc, [P(ParcMdmParams), P(vp)]),
+        "parc_mdm_destroy": (None, [vp]),
+        "parc_mdm_embed_conds": (rc, [vp, P(ParcMdmConds), vp, vp, vp]),
+        "parc_mdm_forward": (rc, [vp, vp, i32, i32, vp, vp]),
+        "parc_mdm_update": (rc, [vp, i32, vp, vp, f32, vp, i32, f32, f32, f32, vp, vp, vp]),
+        "parc_mdm_sample": (rc, [vp, P(ParcMdmConds), P(ParcMdmSampleArgs), vp]),
+        "parc_mdm_draw_noise": (rc, [vp, i32, u64, u64, u32, vp, vp]),
+        "parc_mdm_kernel_times": (rc, [vp, f32p]),
+        "parc_mdm_describe": (rc, [vp, i64p]),
+    }
+
+
+SIGNATURES = _signatures()
+EXPORTED_SYMBOLS = tuple(SIGNATURES)
 _lib = None
 
 
@@ -285,152 +429,12 @@ def load():
         raise RuntimeError(f"{LIB_PATH} is a test-only build ('{flags}'): the product never loads it")
     if missing:  # an SLP-vectorised k_dynamics_wave computes wrong inertias; contraction breaks the 1e-5 parity
         raise RuntimeError(f"{LIB_PATH} was built with '{flags}': missing {missing}; rebuild with __graft_entry__.build()")
-    lib.parc_last_error.restype = C.c_char_p
-    vp = C.c_void_p
-    lib.parc_env_create.argtypes = [C.POINTER(ParcEnvConfig), C.POINTER(vp)]
-    lib.parc_env_destroy.argtypes = [vp]
-    lib.parc_env_destroy.restype = None
-    lib.parc_env_obs_dim.argtypes = [vp]
-    lib.parc_env_load_motions.argtypes = [vp, C.POINTER(ParcMotionClips)]
-    lib.parc_env_load_terrain.argtypes = [vp, f32p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
-                                          f32p, C.c_int32, C.c_int32]
-    lib.parc_env_bind_buffers.argtypes = [vp, C.POINTER(ParcEnvBuffers)]
-    lib.parc_env_step.argtypes = [vp, vp, vp]
-    lib.parc_env_reset.argtypes = [vp, vp, C.c_int32, vp]
-    lib.parc_env_reset_with.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp]
-    lib.parc_env_compute_obs.argtypes = [vp, vp, C.c_int32, vp]
-    lib.parc_env_reset_done.argtypes = [vp, vp]
-    lib.parc_env_get_fail_rates.argtypes = [vp, f32p, C.c_int32]
-    lib.parc_env_set_fail_rates.argtypes = [vp, f32p, C.c_int32]
-    lib.parc_env_get_motion_info.argtypes = [vp, f32p, f32p, C.c_int32]
-    lib.parc_env_set_rand_reset.argtypes = [vp, C.c_int32, C.c_int32, C.c_float]
-    lib.parc_env_set_start_time_fraction.argtypes = [vp, vp]
-    lib.parc_dof_to_rot.argtypes = [vp, vp, vp, C.c_int32, vp]
-    lib.parc_rot_to_dof.argtypes = [vp, vp, vp, C.c_int32, vp]
-    lib.parc_forward_kinematics.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int32, vp]
-    lib.parc_calc_motion_frame.argtypes = [vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.parc_env_get_frame_vel_tables.argtypes = [vp, f32p, f32p, f32p]
-    lib.parc_env_profile_step.argtypes = [vp, vp, vp, C.c_int32, f32p, f32p]
-    lib.parc_env_last_dynamics_ms.argtypes = [vp]
-    lib.parc_env_last_dynamics_ms.restype = C.c_float
-    lib.parc_env_get_buffers.argtypes = [vp, C.POINTER(ParcEnvBuffers)]
-    lib.parc_env_bind_action.argtypes = [vp, vp]
-    lib.parc_env_step_reset_graph.argtypes = [vp, vp]
-    lib.parc_normalize_record.argtypes = [vp, vp, vp, C.c_float, vp, vp, C.c_int64, C.c_int32, vp]
-    lib.parc_td_lambda_return.argtypes = [vp, vp, vp, C.c_float, C.c_float, C.c_int32, C.c_int32, vp, vp]
-    lib.parc_env_set_episode_length.argtypes = [vp, C.c_float]
-    lib.parc_env_record_bind.argtypes = [vp, vp, vp, C.c_int32, vp, vp, vp, C.c_int32]
-    lib.parc_env_record_frame.argtypes = [vp, vp]
-    lib.parc_env_set_kernel_timing.argtypes = [vp, C.c_int32]
-    lib.parc_env_get_kernel_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
-    lib.parc_env_dynamics_kernel.argtypes = [vp]
-    lib.parc_env_set_never_done.argtypes = [vp, C.c_int32]
-    lib.parc_env_dynamics_timeouts.argtypes = [vp]
-    lib.parc_env_describe.argtypes = [vp]
-    lib.parc_gather_rows.argtypes = [C.c_int32, C.POINTER(vp), C.POINTER(vp), i64p, vp, C.c_int64, C.c_int64, vp]
-    lib.parc_env_health_words.argtypes = [vp]
-    lib.parc_env_health_words.restype = C.POINTER(C.c_uint32)
-    lib.parc_env_get_kernel_timing_samples.argtypes = [vp, f32p, f32p, f32p, C.c_int32, C.POINTER(C.c_int32)]
-    lib.parc_env_describe.restype = C.c_char_p
-    lib.parc_env_dynamics_manifold_drops.argtypes = [vp]
-    lib.parc_test_quat_op.argtypes = [C.c_int32, vp, vp, vp, C.c_int32, vp, vp]
-    lib.parc_env_dynamics_kernel.restype = C.c_char_p
-    lib.parc_env_post_kernel.argtypes = [vp]
-    lib.parc_env_post_kernel.restype = C.c_char_p
-    lib.parc_env_render.argtypes = [vp, C.POINTER(ParcRenderParams), vp, C.c_int32, vp, vp, vp, vp]
-    lib.parc_env_render_scene.argtypes = [vp, C.POINTER(ParcRenderParams), C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
-    lib.parc_mopt_create.argtypes = [C.POINTER(ParcMotionOptParams), C.POINTER(vp)]
-    lib.parc_mopt_destroy.argtypes = [vp]
-    lib.parc_mopt_destroy.restype = None
-    lib.parc_mopt_set_clips.argtypes = [vp, C.POINTER(ParcMotionOptClips)]
-    lib.parc_mopt_set_constraint_points.argtypes = [vp, f32p]
-    lib.parc_mopt_set_params.argtypes = [vp, f32p]
-    lib.parc_mopt_get_params.argtypes = [vp, f32p]
-    lib.parc_mopt_loss_and_grad.argtypes = [vp, f32p, f32p]
-    lib.parc_mopt_step.argtypes = [vp, C.c_int32, f32p]
-    lib.parc_mopt_get_frames.argtypes = [vp, f32p, f32p, f32p]
-    lib.parc_mopt_get_source_body.argtypes = [vp, f32p, f32p]
-    lib.parc_mopt_build_constraints.argtypes = [vp, C.c_int32, i32p, f32p, C.c_int32, C.c_float]
-    lib.parc_mopt_kernel_times.argtypes = [vp, f32p]
-    lib.parc_mterr_create.argtypes = [C.POINTER(ParcMotionTerrainParams), C.POINTER(vp)]
-    lib.parc_mterr_destroy.argtypes = [vp]
-    lib.parc_mterr_destroy.restype = None
-    lib.parc_mterr_set_clips.argtypes = [vp, C.POINTER(ParcMotionOptClips)]
-    lib.parc_mterr_run.argtypes = [vp, f32p, i32p, f32p, C.POINTER(C.c_int64)]
-    lib.parc_mterr_get_mask_inds.argtypes = [vp, i32p]
-    lib.parc_mterr_get_min_heights.argtypes = [vp, f32p, i32p]
-    lib.parc_mterr_point_sdf.argtypes = [vp, C.c_int64, C.c_int32, f32p, f32p]
-    lib.parc_mterr_kernel_times.argtypes = [vp, f32p]
-    lib.parc_msamp_create.argtypes = [C.POINTER(ParcMotionSamplerParams), C.POINTER(vp)]
-    lib.parc_msamp_destroy.argtypes = [vp]
-    lib.parc_msamp_destroy.restype = None
-    lib.parc_msamp_set_clips.argtypes = [vp, C.POINTER(ParcMotionOptClips), C.POINTER(ParcMotionSamplerClipInfo)]
-    lib.parc_msamp_sample_with.argtypes = [vp, C.POINTER(ParcMotionSamplerPlan), C.POINTER(ParcMotionSamplerOutputs), vp]
-    lib.parc_msamp_draw_plan.argtypes = [vp, C.c_uint64, C.POINTER(ParcMotionSamplerPlan), vp]
-    lib.parc_msamp_sample.argtypes = [vp, C.c_uint64, C.POINTER(ParcMotionSamplerPlan), C.POINTER(ParcMotionSamplerOutputs), vp]
-    lib.parc_msamp_enumerate.argtypes = [vp, C.c_int32, C.POINTER(ParcMotionSamplerOutputs), vp]
-    lib.parc_msamp_plan_status.argtypes = [vp, vp, i32p]
-    lib.parc_msamp_kernel_times.argtypes = [vp, f32p]
-    lib.parc_pathplan_create.argtypes = [C.POINTER(ParcPathPlanParams), C.POINTER(vp)]
-    lib.parc_pathplan_destroy.argtypes = [vp]
-    lib.parc_pathplan_destroy.restype = None
-    lib.parc_pathplan_run.argtypes = [vp, C.c_int32, f32p, i32p, i32p, C.c_uint64, C.c_uint64, C.POINTER(ParcPathPlanOutputs)]
-    lib.parc_pathplan_get_graph.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)]
-    lib.parc_pathplan_kernel_times.argtypes = [vp, f32p]
-    lib.parc_tgen_create.argtypes = [C.POINTER(ParcTerrainGenParams), C.POINTER(vp)]
-    lib.parc_tgen_destroy.argtypes = [vp]
-    lib.parc_tgen_destroy.restype = None
-    lib.parc_tgen_draw_plan.argtypes = [vp, C.c_uint64, C.c_uint64, C.POINTER(ParcTerrainGenPlan), vp]
-    lib.parc_tgen_generate_with.argtypes = [vp, C.POINTER(ParcTerrainGenPlan), vp, C.c_int32, vp]
-    lib.parc_tgen_generate.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, vp, vp]
-    lib.parc_tgen_kernel_times.argtypes = [vp, f32p]
-    lib.parc_maug_create.argtypes = [C.POINTER(ParcMotionAugParams), C.POINTER(vp)]
-    lib.parc_maug_destroy.argtypes = [vp]
-    lib.parc_maug_destroy.restype = None
-    lib.parc_maug_set_clips.argtypes = [vp, C.POINTER(ParcMotionOptClips), C.POINTER(ParcMotionAugClipInfo)]
-    lib.parc_maug_draw_plan.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_int32, C.POINTER(ParcMotionAugPlan), vp]
-    lib.parc_maug_augment_with.argtypes = [vp, C.POINTER(ParcMotionAugPlan), C.c_int32, vp, C.POINTER(ParcMotionAugSizes)]
-    lib.parc_maug_augment.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, vp, C.POINTER(ParcMotionAugSizes)]
-    lib.parc_maug_get_result.argtypes = [vp, C.POINTER(ParcMotionAugOutputs), vp]
-    lib.parc_maug_plan_status.argtypes = [vp, vp, i32p]
-    lib.parc_maug_kernel_times.argtypes = [vp, f32p]
-    lib.parc_mdm_create.argtypes = [C.POINTER(ParcMdmParams), C.POINTER(vp)]
-    lib.parc_mdm_destroy.argtypes = [vp]
-    lib.parc_mdm_destroy.restype = None
-    lib.parc_mdm_embed_conds.argtypes = [vp, C.POINTER(ParcMdmConds), vp, vp, vp]
-    lib.parc_mdm_forward.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp]
-    lib.parc_mdm_update.argtypes = [vp, C.c_int32, vp, vp, C.c_float, vp, C.c_int32, C.c_float, C.c_float, C.c_float, vp, vp, vp]
-    lib.parc_mdm_sample.argtypes = [vp, C.POINTER(ParcMdmConds), C.POINTER(ParcMdmSampleArgs), vp]
-    lib.parc_mdm_draw_noise.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp]
-    lib.parc_mdm_kernel_times.argtypes = [vp, f32p]
-    lib.parc_mdm_describe.argtypes = [vp, i64p]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
-
-EXPORTED_SYMBOLS = [
-    "parc_last_error", "parc_abi_version", "parc_env_create", "parc_env_destroy", "parc_env_obs_dim",
-    "parc_env_load_motions", "parc_env_load_terrain", "parc_env_bind_buffers", "parc_env_step", "parc_env_reset",
-    "parc_env_reset_with", "parc_env_reset_done", "parc_env_compute_obs", "parc_env_get_fail_rates", "parc_env_set_fail_rates",
-    "parc_env_get_motion_info", "parc_env_set_rand_reset", "parc_env_set_start_time_fraction", "parc_dof_to_rot",
-    "parc_rot_to_dof", "parc_forward_kinematics", "parc_calc_motion_frame", "parc_env_get_frame_vel_tables",
-    "parc_env_profile_step", "parc_env_last_dynamics_ms", "parc_env_dynamics_kernel", "parc_env_set_kernel_timing", "parc_env_get_kernel_timing", "parc_env_record_bind", "parc_env_record_frame", "parc_env_set_episode_length", "parc_td_lambda_return", "parc_normalize_record", "parc_env_bind_action", "parc_env_get_buffers", "parc_env_step_reset_graph",
-    "parc_test_quat_op", "parc_build_flags", "parc_env_set_never_done", "parc_env_dynamics_timeouts", "parc_env_dynamics_manifold_drops", "parc_env_describe", "parc_env_get_kernel_timing_samples", "parc_env_health_words", "parc_gather_rows",
-    "parc_env_post_kernel", "parc_env_render", "parc_env_render_scene",
-    "parc_mopt_create", "parc_mopt_destroy", "parc_mopt_set_clips", "parc_mopt_set_constraint_points", "parc_mopt_set_params",
-    "parc_mopt_get_params", "parc_mopt_loss_and_grad", "parc_mopt_step", "parc_mopt_get_frames", "parc_mopt_get_source_body",
-    "parc_mopt_build_constraints", "parc_mopt_kernel_times",
-    "parc_mterr_create", "parc_mterr_destroy", "parc_mterr_set_clips", "parc_mterr_run", "parc_mterr_get_mask_inds",
-    "parc_mterr_get_min_heights", "parc_mterr_point_sdf", "parc_mterr_kernel_times",
-    "parc_msamp_create", "parc_msamp_destroy", "parc_msamp_set_clips", "parc_msamp_sample_with", "parc_msamp_draw_plan",
-    "parc_msamp_sample", "parc_msamp_enumerate", "parc_msamp_plan_status", "parc_msamp_kernel_times",
-    "parc_pathplan_create", "parc_pathplan_destroy", "parc_pathplan_run", "parc_pathplan_get_graph", "parc_pathplan_kernel_times",
-    "parc_tgen_create", "parc_tgen_destroy", "parc_tgen_draw_plan", "parc_tgen_generate_with", "parc_tgen_generate", "parc_tgen_kernel_times",
-    "parc_maug_create", "parc_maug_destroy", "parc_maug_set_clips", "parc_maug_draw_plan", "parc_maug_augment_with", "parc_maug_augment",
-    "parc_maug_get_result", "parc_maug_plan_status", "parc_maug_kernel_times",
-    "parc_mdm_create", "parc_mdm_destroy", "parc_mdm_embed_conds", "parc_mdm_forward", "parc_mdm_update", "parc_mdm_sample",
-    "parc_mdm_draw_noise", "parc_mdm_kernel_times", "parc_mdm_describe",
-]
 
 # parc_test_quat_op selectors (include/parc_env.h)
 QOP = {"mul": 0, "rotate": 1, "conj": 2, "pos": 3, "normalize3": 4, "to_axis_angle": 5, "aa_to_quat": 6, "exp_map_to_quat": 7,

@@ -18,13 +18,15 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
+from parc_amd import lib as L
 from parc_amd.char_model import CharModel
-from parc_amd.lib import destroy_handle
+from parc_amd.tool_handle import PlanCodec, ToolHandle, fill_struct
+from parc_amd.util import path_loader
 
-MODES = ("HEIGHT_SCALE", "BOXES_ALONG_PATH", "NONE")      # TerrainAugmentationType (run_simple_augment_motions.py:19-22)
-MAX_DIM, MAX_BOXES, BOX_FLOATS = 128, 16, 4                # PARC_MAUG_* (include/parc_env.h)
-STATUS_CLAMPED, STATUS_NOT_FINITE = 1, 2
-KERNELS = ("draw", "layout", "frames", "terrain")
+MODES = L.MAUG_MODES                                       # TerrainAugmentationType (run_simple_augment_motions.py:19-22)
+MAX_DIM, MAX_BOXES, BOX_FLOATS = L.MAUG_MAX_DIM, L.MAUG_MAX_BOXES, L.MAUG_BOX_FLOATS
+STATUS_CLAMPED, STATUS_NOT_FINITE = L.MAUG_STATUS_CLAMPED, L.MAUG_STATUS_NOT_FINITE
+KERNELS = ("draw", "layout", "frames", "terrain")          # draw_plan, and the three phases of a run
 # the keys of the reference script's config that belong to the optimiser and the driver, not to the augmenter
 DRIVER_KEYS = ("motions_yaml_path", "device", "char_model", "num_new_motions", "output_folder_path", "num_iters", "step_size", "w_root_pos",
                "w_root_rot", "w_joint_rot", "w_smoothness", "w_penetration", "w_contact", "w_sliding", "w_body_constraints", "w_jerk", "max_jerk",
@@ -110,9 +112,7 @@ class MotionAugSettings:
 
 
 def load_config(path) -> dict:
-    import yaml
-    with open(path) as f:
-        cfg = yaml.safe_load(f)
+    cfg = path_loader.load_config(path)
     if not isinstance(cfg, dict):
         raise ValueError(f"{path}: not a mapping")
     return cfg
@@ -147,7 +147,6 @@ def swap_tables(char_model: CharModel):
 
 def plan_fields() -> Dict[str, tuple]:
     """``name -> (dtype char "i" / "f", per-variation shape)`` of the plan's arrays, in the order of ``ParcMotionAugPlan``."""
-    from parc_amd import lib as L
     return {n: (t, s) for n, t, s in L.MAUG_PLAN_FIELDS}
 
 
@@ -194,13 +193,12 @@ class AugResult:
         return clips
 
 
-class MotionAugmenter:
+class MotionAugmenter(ToolHandle):
     """See the module docstring.  ``clips`` are ``OptClip`` s (``motion_opt.clip_from_ms``); ``settings`` a ``MotionAugSettings`` or a
     config mapping.  ``hf_maxmin`` rides along when every clip carries one."""
+    PREFIX, KERNELS = "parc_maug", KERNELS
 
     def __init__(self, char_file: str, clips, settings=None, device="cuda:0"):
-        import torch
-        from parc_amd import lib as L
         from parc_amd.motion_opt import clip_struct, pack_clips
         if settings is None:
             settings = MotionAugSettings()
@@ -209,7 +207,6 @@ class MotionAugmenter:
         settings.check()
         self.settings = settings
         self.mode = settings.terrain_aug_type
-        self._h = None
         self.char_file = char_file
         self.char_model = CharModel(char_file)
         self.B = self.char_model.get_num_bodies()
@@ -217,13 +214,11 @@ class MotionAugmenter:
         if not self.clips:
             raise ValueError("no clips")
         self.clip_names = [c.name or f"clip{i}" for i, c in enumerate(self.clips)]
-        self._L, self._lib = L, L.load()
-        self.device = torch.device(device)
-        self.device_index = L.device_index(self.device)
+        super().__init__(device)
+        self._codec = PlanCodec(L.MAUG_PLAN_FIELDS, L.ParcMotionAugPlan)
         self.joint_swap, self.contact_swap = swap_tables(self.char_model)
         s = settings
         p = L.ParcMotionAugParams()
-        p.struct_size = C.sizeof(L.ParcMotionAugParams)
         p.device = self.device_index
         p.model = L.make_char_model(self.char_model)
         for b in range(L.MAX_BODIES):
@@ -238,9 +233,7 @@ class MotionAugmenter:
         p.min_num_boxes, p.max_num_boxes = int(s.min_num_boxes), int(s.max_num_boxes)
         p.min_len, p.max_len, p.min_angle, p.max_angle, p.min_h, p.max_h = (float(v) for v in (s.min_len, s.max_len, s.min_angle, s.max_angle,
                                                                                                  s.min_h, s.max_h))
-        h = C.c_void_p()
-        L.check(self._lib.parc_maug_create(C.byref(p), C.byref(h)))
-        self._h = h
+        self._create_handle(p)
         pk = pack_clips(self.clips, self.B, self.char_model.get_dof_size())
         st = clip_struct(pk, len(self.clips))
         self.has_maxmin = all(c.hf_maxmin is not None for c in self.clips)
@@ -253,74 +246,30 @@ class MotionAugmenter:
         fps = np.array([int(c.fps) for c in self.clips], np.int32)
         self.max_frames = np.array([int(round(int(c.fps) * float(s.max_motion_len))) for c in self.clips], np.int32)   # :152
         info.fps_host, info.max_frames_host = L.np_i32p(fps), L.np_i32p(self.max_frames)
-        L.check(self._lib.parc_maug_set_clips(self._h, C.byref(st), C.byref(info)))
+        self._call("set_clips", C.byref(st), C.byref(info))
         self.num_frames = np.diff(pk["frame_off"]).astype(np.int64)
         w = (self.num_frames / fps).astype(np.float32) if s.sample_weight_by_length else np.ones(len(self.clips), np.float32)
         self.weights = w.astype(np.float64) / w.astype(np.float64).sum()
-
-    def __del__(self):
-        destroy_handle(self, "parc_maug_destroy")
 
     # ------------------------------------------------------------------ plans
     plan_fields = staticmethod(plan_fields)
 
     def empty_plan(self, n: int, zero: bool = True):
-        import torch
-        make = torch.zeros if zero else torch.empty
-        return {k: make((int(n),) + s, dtype=torch.int32 if t == "i" else torch.float32, device=self.device) for k, (t, s) in plan_fields().items()}
+        return self._codec.empty(n, self.device, zero)
 
     def plan_from_numpy(self, arrays: Dict[str, np.ndarray]):
         """A plan from host arrays ``[n, ...]``.  ``src_clip``, ``start_frame``, ``num_frames`` are required; a missing ``heading`` is 0,
         ``scale`` 1, ``mirror`` 0, ``height_scale`` 1, and no boxes."""
-        import torch
-        for k in ("src_clip", "start_frame", "num_frames"):
-            if k not in arrays:
-                raise ValueError(f"plan: {k} is missing")
-        unknown = sorted(set(arrays) - set(plan_fields()))
-        if unknown:
-            raise ValueError(f"plan: unknown field(s) {unknown}")
-        n = int(np.asarray(arrays["src_clip"]).shape[0])
-        plan = self.empty_plan(n)
-        plan["scale"].fill_(1.0); plan["height_scale"].fill_(1.0)
-        for k, (t, s) in plan_fields().items():
-            if k in arrays:
-                a = np.ascontiguousarray(arrays[k], np.int32 if t == "i" else np.float32)
-                if a.shape != (n,) + s:
-                    raise ValueError(f"plan: {k} must have shape {(n,) + s}, got {a.shape}")
-                plan[k] = torch.from_numpy(a).to(self.device)
-        return plan
+        return self._codec.from_numpy(arrays, self.device, required=("src_clip", "start_frame", "num_frames"),
+                                      defaults=dict(scale=1.0, height_scale=1.0), reject_unknown=True)
 
     def _plan_struct(self, plan):
-        import torch
-        fields = plan_fields()
-        if "src_clip" not in plan:
-            raise ValueError("plan: src_clip is missing")
-        n = int(plan["src_clip"].shape[0])
-        st = self._L.ParcMotionAugPlan()
-        st.n = n
-        for k, (t, s) in fields.items():
-            x = plan.get(k)
-            if x is None:
-                raise ValueError(f"plan: {k} is missing")
-            dt = torch.int32 if t == "i" else torch.float32
-            if tuple(x.shape) != (n,) + s or x.dtype != dt:
-                raise ValueError(f"plan: {k} must be {dt} {(n,) + s}, got {x.dtype} {tuple(x.shape)}")
-            if x.device != self.device or not x.is_contiguous():
-                raise ValueError(f"plan: {k} must be contiguous on {self.device}")
-            setattr(st, k, x.data_ptr())
-        return st, n
-
-    def _stream(self):
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return self._codec.struct(plan, self.device)
 
     def draw_plan(self, n: int, seed: int, first: int = 0, mirror: bool = False):
-        import torch
         plan = self.empty_plan(n, zero=False)
         st, _ = self._plan_struct(plan)
-        with torch.cuda.device(self.device):
-            self._L.check(self._lib.parc_maug_draw_plan(self._h, C.c_uint64(int(seed)), C.c_uint64(int(first)), int(bool(mirror)), C.byref(st),
-                                                        self._stream()))
+        self._call("draw_plan", C.c_uint64(int(seed)), C.c_uint64(int(first)), int(bool(mirror)), C.byref(st), self._stream())
         return plan
 
     # ------------------------------------------------------------------ augmentation
@@ -332,10 +281,7 @@ class MotionAugmenter:
                       canon_z=((n,), f32), root_pos=((F, 3), f32), root_rot=((F, 4), f32), joint_rot=((F, J, 4), f32), contacts=((F, self.B), f32),
                       hf=((cells,), f32), hf_maxmin=((cells, 2), f32))
         t = {k: torch.empty(s, dtype=d, device=self.device) for k, (s, d) in shapes.items() if k != "hf_maxmin" or sizes.has_maxmin}
-        o = self._L.ParcMotionAugOutputs()
-        for k, x in t.items():
-            setattr(o, k, x.data_ptr())
-        self._L.check(self._lib.parc_maug_get_result(self._h, C.byref(o), self._stream()))
+        self._call("get_result", C.byref(fill_struct(L.ParcMotionAugOutputs, t)), self._stream())
         t.setdefault("hf_maxmin", None)
         return AugResult(t, self.clips, self.clip_names)
 
@@ -343,22 +289,17 @@ class MotionAugmenter:
         """The variations of ``plan``.  ``validate`` runs a pass over the plan first: a non-finite or out-of-range entry raises, naming
         the field, and nothing is launched.  Without it a bad index is clamped into its range (``status()`` tells) and a non-finite
         value stays inside its own variation."""
-        import torch
         st, _ = self._plan_struct(plan)
-        sizes = self._L.ParcMotionAugSizes()
-        with torch.cuda.device(self.device):
-            self._L.check(self._lib.parc_maug_augment_with(self._h, C.byref(st), int(bool(validate)), self._stream(), C.byref(sizes)))
-            return self._result(sizes)
+        sizes = L.ParcMotionAugSizes()
+        self._call("augment_with", C.byref(st), int(bool(validate)), self._stream(), C.byref(sizes))
+        return self._result(sizes)
 
     def augment(self, n: int, seed: int, first: int = 0, mirror: bool = False) -> AugResult:
-        import torch
         if int(n) < 1:
             raise ValueError("n must be >= 1")
-        sizes = self._L.ParcMotionAugSizes()
-        with torch.cuda.device(self.device):
-            self._L.check(self._lib.parc_maug_augment(self._h, int(n), C.c_uint64(int(seed)), C.c_uint64(int(first)), int(bool(mirror)), self._stream(),
-                                                      C.byref(sizes)))
-            return self._result(sizes)
+        sizes = L.ParcMotionAugSizes()
+        self._call("augment", int(n), C.c_uint64(int(seed)), C.c_uint64(int(first)), int(bool(mirror)), self._stream(), C.byref(sizes))
+        return self._result(sizes)
 
     def mirror_clips(self, clips):
         """``mirror_clips(clips, ...)`` with this augmenter's character and device."""
@@ -367,14 +308,8 @@ class MotionAugmenter:
     def status(self) -> int:
         """The OR of ``STATUS_CLAMPED`` / ``STATUS_NOT_FINITE`` since the last call (synchronises)."""
         v = np.zeros(1, np.int32)
-        self._L.check(self._lib.parc_maug_plan_status(self._h, self._stream(), self._L.np_i32p(v)))
+        self._call("plan_status", self._stream(), L.np_i32p(v))
         return int(v[0])
-
-    def kernel_times(self):
-        """Device ms of the last ``draw_plan`` and of the three phases of the last run (0 = not run)."""
-        ms = np.zeros(4, np.float32)
-        self._L.check(self._lib.parc_maug_kernel_times(self._h, self._L.np_f32p(ms)))
-        return dict(zip(KERNELS, ms.tolist()))
 
 
 def mirror_plan(num_frames: Sequence[int]) -> Dict[str, np.ndarray]:

@@ -19,12 +19,13 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
+from parc_amd import lib as L
 from parc_amd.char_model import CharModel, JointType
-from parc_amd.lib import destroy_handle
+from parc_amd.tool_handle import ToolHandle
 
 FRAME_COMPONENTS = ("ROOT_POS", "ROOT_ROT", "JOINT_POS", "JOINT_ROT", "CONTACTS")
 TOKENIZER = "cnn_31xy_4layer_c64_out64"
-GRID = 31
+GRID = L.MDM_GRID
 KERNELS = ("cond", "forward", "update")
 _REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -295,16 +296,14 @@ def _mode(mode) -> str:
     raise ValueError(f"mode {name!r}: DDIM (MODE_DDIM) or DDPM (MODE_REVERSE_DIFFUSION)")
 
 
-class MDMGenerator:
+class MDMGenerator(ToolHandle):
     """See the module docstring."""
+    PREFIX, KERNELS = "parc_mdm", KERNELS
 
     def __init__(self, cfg: dict, state_dict: Dict[str, torch.Tensor], features_mean, features_std, device="cuda:0", max_batch: int = 64):
-        from parc_amd import lib as L
         check_config(cfg)
-        self._L, self._lib = L, L.load()
-        self._h = None
+        super().__init__(device)
         self.cfg = cfg
-        self.device = torch.device(device)
         self.char_model = CharModel(_char_path(cfg))
         self.T, self.nprev, self.timesteps = int(cfg["seq_len"]), int(cfg["num_prev_states"]), int(cfg["diffusion_timesteps"])
         self.d_model = int(cfg["d_model"])
@@ -331,8 +330,7 @@ class MDMGenerator:
         offsets[1:] = np.cumsum([a.size for a in flat])
         weights = np.ascontiguousarray(np.concatenate(flat), np.float32)
         p = L.ParcMdmParams()
-        p.struct_size = C.sizeof(L.ParcMdmParams)
-        p.device = L.device_index(self.device)
+        p.device = self.device_index
         p.model = L.make_char_model(self.char_model)
         p.d_model, p.num_heads, p.d_hid, p.num_layers = self.d_model, int(cfg["num_heads"]), int(cfg["d_hid"]), int(cfg["num_layers"])
         p.seq_len, p.num_prev_states, p.diffusion_timesteps = self.T, self.nprev, self.timesteps
@@ -351,13 +349,8 @@ class MDMGenerator:
         tables = {k: np.ascontiguousarray(v.numpy(), np.float32) for k, v in self.rates.items()}
         for k in ("sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod", "posterior_mean_coef1", "posterior_mean_coef2", "posterior_std"):
             setattr(p, k + "_host", L.np_f32p(tables[k]))
-        h = C.c_void_p()
-        L.check(self._lib.parc_mdm_create(C.byref(p), C.byref(h)))
-        self._h = h
+        self._create_handle(p)
         self.mean, self.std = mean.to(self.device), std.to(self.device)
-
-    def __del__(self):
-        destroy_handle(self, "parc_mdm_destroy")
 
     # ------------------------------------------------------------------ construction
     @classmethod
@@ -395,9 +388,6 @@ class MDMGenerator:
                 "JOINT_ROT": joint_dof_to_rot(self.char_model, f[..., s["JOINT_ROT"]]), "CONTACTS": f[..., s["CONTACTS"]]}
 
     # ------------------------------------------------------------------ the handle's calls
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _f32(self, t, shape, what):
         t = torch.as_tensor(t, device=self.device).to(torch.float32).contiguous()
         if tuple(t.shape) != tuple(shape):
@@ -416,7 +406,7 @@ class MDMGenerator:
         prev = self._f32(prev[:, :self.nprev], (n, self.nprev, self.D), "PREV_STATE_KEY")
         flags = [torch.as_tensor(c[k], device=self.device).reshape(n).to(torch.int32).contiguous()
                  for k in ("OBS_FLAG_KEY", "TARGET_FLAG_KEY", "PREV_STATE_FLAG_KEY", "PREV_STATE_NOISE_IND_KEY")]
-        st = self._L.ParcMdmConds()
+        st = L.ParcMdmConds()
         st.n, st.hf, st.target, st.prev_state = n, hf.data_ptr(), tgt.data_ptr(), prev.data_ptr()
         st.obs_flag, st.target_flag, st.prev_state_flag, st.noise_ind = [f.data_ptr() for f in flags]
         return st, (hf, tgt, prev, flags)
@@ -428,8 +418,7 @@ class MDMGenerator:
         n = st.n
         tokens = torch.empty((n, 65, self.d_model), dtype=torch.float32, device=self.device)
         bits = torch.zeros((n, 3), dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            self._L.check(self._lib.parc_mdm_embed_conds(self._h, C.byref(st), tokens.data_ptr(), bits.data_ptr(), self._stream()))
+        self._call("embed_conds", C.byref(st), tokens.data_ptr(), bits.data_ptr(), self._stream())
         self._n = n
         j = torch.arange(67 + self.T, device=self.device)
         mask = ((bits[:, j // 64] >> (j % 64)) & 1).to(torch.bool)
@@ -441,8 +430,7 @@ class MDMGenerator:
         pass's indicator is set.  Returns x_0."""
         self._check_x(x, self._n)
         out = torch.empty_like(x)
-        with torch.cuda.device(self.device):
-            self._L.check(self._lib.parc_mdm_forward(self._h, x.data_ptr(), int(t), int(pass_kind), out.data_ptr(), self._stream()))
+        self._call("forward", x.data_ptr(), int(t), int(pass_kind), out.data_ptr(), self._stream())
         return out
 
     def _check_x(self, x, n):
@@ -453,9 +441,9 @@ class MDMGenerator:
     def predict_x0(self, x, t: int, guidance_scale: Optional[float] = None):
         """``MDM.predict_x0`` (mdm.py:836-852) on the cached conditions."""
         if guidance_scale is None:
-            return self.forward(x, t, self._L.MDM_PASS_PLAIN)
-        a = self.forward(x, t, self._L.MDM_PASS_GUIDED)
-        b = self.forward(x, t, self._L.MDM_PASS_UNCOND)
+            return self.forward(x, t, L.MDM_PASS_PLAIN)
+        a = self.forward(x, t, L.MDM_PASS_GUIDED)
+        b = self.forward(x, t, L.MDM_PASS_UNCOND)
         return a + float(guidance_scale) * (b - a)
 
     def project_dofs(self, x0):
@@ -463,9 +451,7 @@ class MDMGenerator:
         n = x0.shape[0]
         self._check_x(x0, n)
         out, work = torch.empty_like(x0), torch.empty_like(x0)
-        with torch.cuda.device(self.device):
-            self._L.check(self._lib.parc_mdm_update(self._h, n, x0.data_ptr(), None, 0.0, work.data_ptr(), 1, 0.0, 0.0, 0.0, None, out.data_ptr(),
-                                                    self._stream()))
+        self._call("update", n, x0.data_ptr(), None, 0.0, work.data_ptr(), 1, 0.0, 0.0, 0.0, None, out.data_ptr(), self._stream())
         return out
 
     def sample(self, conds: dict, mode: str, timesteps: Sequence[int], stride: int = 1, guidance_scale: Optional[float] = None, noise=None,
@@ -473,7 +459,6 @@ class MDMGenerator:
         """The reverse-diffusion loop on conditions in the network's units.  ``noise`` is x_T [B, T, D] (copied, not changed);
         ``step_noise`` [steps, B, T, D] the DDPM noise of every step; with ``seed`` both are drawn on the device from
         ``(seed, first_index + sample, step)``.  Returns x [B, T, D], or with ``keep_all_samples`` the list after every step."""
-        L = self._L
         st, keep = self._conds_struct(conds)
         n = st.n
         ts = np.ascontiguousarray(list(timesteps), np.int32)
@@ -504,8 +489,7 @@ class MDMGenerator:
         kept = torch.empty((len(ts), n, self.T, self.D), dtype=torch.float32, device=self.device) if keep_all_samples else None
         if kept is not None:
             a.keep = kept.data_ptr()
-        with torch.cuda.device(self.device):
-            L.check(self._lib.parc_mdm_sample(self._h, C.byref(st), C.byref(a), self._stream()))
+        self._call("sample", C.byref(st), C.byref(a), self._stream())
         self._n = n
         del keep, sn
         return list(kept) if keep_all_samples else x
@@ -556,18 +540,12 @@ class MDMGenerator:
         """The standard-normal array [n, T, D] that ``sample`` draws for ``(seed, first_index + sample, step)``: step 0 is x_T, step
         i + 1 the DDPM noise of step i."""
         out = torch.empty((n, self.T, self.D), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            self._L.check(self._lib.parc_mdm_draw_noise(self._h, int(n), int(seed), int(first_index), int(step), out.data_ptr(), self._stream()))
+        self._call("draw_noise", int(n), int(seed), int(first_index), int(step), out.data_ptr(), self._stream())
         return out
-
-    def kernel_times(self) -> Dict[str, float]:
-        out = np.zeros(3, np.float32)
-        self._L.check(self._lib.parc_mdm_kernel_times(self._h, self._L.np_f32p(out)))
-        return dict(zip(KERNELS, out.tolist()))
 
     def describe(self) -> Dict[str, int]:
         out = np.zeros(3, np.int64)
-        self._L.check(self._lib.parc_mdm_describe(self._h, out.ctypes.data_as(self._L.i64p)))
+        self._call("describe", out.ctypes.data_as(L.i64p))
         return {"forward_lds_bytes": int(out[0]), "forward_grid": int(out[1]), "scratch_floats_per_slot": int(out[2])}
 
 

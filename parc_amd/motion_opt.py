@@ -19,8 +19,9 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
+from parc_amd import lib as L
 from parc_amd.char_model import CharModel, GeomType
-from parc_amd.lib import destroy_handle
+from parc_amd.tool_handle import ToolHandle
 
 
 class LossType(enum.Enum):  # motion_optimization.py:15-25 (LOOPING_LOSS is never computed)
@@ -35,13 +36,14 @@ class LossType(enum.Enum):  # motion_optimization.py:15-25 (LOOPING_LOSS is neve
     JERK_LOSS = 8
 
 
-NUM_TERMS = 9
+NUM_TERMS = L.MOPT_NUM_TERMS
+KERNELS = ("fk", "patch", "points", "grad", "reduce", "adam")
 # order of ParcMotionOptParams.weights: the LossType order
 WEIGHT_KEYS = ("w_root_pos", "w_root_rot", "w_joint_rot", "w_smoothness", "w_penetration", "w_contact", "w_sliding",
                "w_body_constraints", "w_jerk")
 SAMPLER_KEYS = ("sphere_num_subdivisions", "box_num_slices", "box_dim_x", "box_dim_y", "capsule_num_circle_points",
                 "capsule_num_sphere_subdivisions", "capsule_num_cylinder_slices")
-MAX_POINTS = 512          # PARC_MOPT_MAX_POINTS
+MAX_POINTS = L.MOPT_MAX_POINTS
 CONSTRAINT_BODIES = ("left_foot", "right_foot", "left_hand", "right_hand")  # compute_approx_body_constraints order
 CONTACT_THRESHOLD = 0.9
 CONSTRAINT_SGD_STEPS = 1000
@@ -233,7 +235,6 @@ def pack_clips(clips: Sequence[OptClip], num_bodies: int, dof_size: int):
 
 def clip_struct(pk, num_clips):
     """``ParcMotionOptClips`` over the arrays of ``pack_clips`` (the caller keeps ``pk`` alive)."""
-    from parc_amd import lib as L
     st = L.ParcMotionOptClips()
     st.num_clips = int(num_clips)
     i64 = lambda a: a.ctypes.data_as(L.i64p)  # noqa: E731
@@ -248,7 +249,6 @@ def clip_struct(pk, num_clips):
 
 def model_points_params(p, char_model: CharModel, flat_points, point_body, device: int):
     """The head that ``ParcMotionOptParams`` and ``ParcMotionTerrainParams`` share: size, device, character and sample points."""
-    from parc_amd import lib as L
     p.struct_size = C.sizeof(type(p))
     p.device = int(device)
     p.model = L.make_char_model(char_model)
@@ -264,7 +264,6 @@ def model_points_params(p, char_model: CharModel, flat_points, point_body, devic
 def optimizer_params(char_model: CharModel, flat_points, point_body, weights: Dict[str, float], max_jerk: float, step_size: float,
                      device: int = 0):
     """``ParcMotionOptParams`` for the character, the sample points and the loss weights (keys ``WEIGHT_KEYS``)."""
-    from parc_amd import lib as L
     p = model_points_params(L.ParcMotionOptParams(), char_model, flat_points, point_body, device)
     for b in range(char_model.get_num_bodies()):
         geoms = char_model._geoms[b]
@@ -290,17 +289,15 @@ def optimizer_params(char_model: CharModel, flat_points, point_body, weights: Di
     return p
 
 
-class MotionOptimizer:
+class MotionOptimizer(ToolHandle):
     """``MotionOptimizer(char_file, device, cfg).optimize(clips, iters, log_every)``: the reference's ``motion_contact_optimization``
     for a whole batch of clips.  ``cfg`` holds the loss weights (``WEIGHT_KEYS``), ``max_jerk``, ``step_size`` and optionally
     ``char_point_samples`` (``SAMPLER_KEYS``; the stage-2 sampler when absent)."""
+    PREFIX, KERNELS, DEVICE_CONTEXT = "parc_mopt", KERNELS, False
 
     def __init__(self, char_file: str, device="cuda:0", cfg: Optional[dict] = None):
-        import torch  # noqa: F401  (one HIP runtime: torch's, loaded before the library)
-        from parc_amd import lib as L
         cfg = dict(cfg or {})
-        self._L = L
-        self._lib = L.load()
+        super().__init__(device)
         self.char_model = CharModel(char_file)
         sampler = dict(sphere_num_subdivisions=0, box_num_slices=2, box_dim_x=3, box_dim_y=6, capsule_num_circle_points=4,
                        capsule_num_sphere_subdivisions=0, capsule_num_cylinder_slices=4)
@@ -310,26 +307,19 @@ class MotionOptimizer:
             raise ValueError(f"unknown char_point_samples keys: {sorted(unknown)}")
         self.body_points, self.points, self.point_body = char_point_samples(self.char_model, **sampler)
         self.cfg = cfg
-        self.device_index = L.device_index(device)
-        params = optimizer_params(self.char_model, self.points, self.point_body, cfg, float(cfg.get("max_jerk", 1000.0)),
-                                  float(cfg.get("step_size", 1e-3)), self.device_index)
-        h = C.c_void_p()
-        L.check(self._lib.parc_mopt_create(C.byref(params), C.byref(h)))
-        self._h = h
+        self._create_handle(optimizer_params(self.char_model, self.points, self.point_body, cfg, float(cfg.get("max_jerk", 1000.0)),
+                                             float(cfg.get("step_size", 1e-3)), self.device_index))
         self.B = self.char_model.get_num_bodies()
         self.D = self.char_model.get_dof_size()
         self.NP = 6 + self.D
         self._clips: List[OptClip] = []
         self._packed = None
 
-    def __del__(self):
-        destroy_handle(self, "parc_mopt_destroy")
-
     # ------------------------------------------------------------------ batch
     def set_clips(self, clips: Sequence[OptClip]):
         pk = pack_clips(clips, self.B, self.D)
         st = clip_struct(pk, len(clips))
-        self._L.check(self._lib.parc_mopt_set_clips(self._h, C.byref(st)))
+        self._call("set_clips", C.byref(st))
         self._clips = list(clips)
         self._packed = pk
         return pk
@@ -344,37 +334,32 @@ class MotionOptimizer:
 
     def get_params(self) -> np.ndarray:
         out = np.zeros((self.num_frames_total, self.NP), np.float32)
-        self._L.check(self._lib.parc_mopt_get_params(self._h, self._L.np_f32p(out)))
+        self._call("get_params", L.np_f32p(out))
         return out
 
     def set_params(self, params: np.ndarray):
         p = np.ascontiguousarray(params, np.float32)
         if p.shape != (self.num_frames_total, self.NP):
             raise ValueError(f"params must be [{self.num_frames_total}, {self.NP}], got {p.shape}")
-        self._L.check(self._lib.parc_mopt_set_params(self._h, self._L.np_f32p(p)))
+        self._call("set_params", L.np_f32p(p))
 
     def loss_and_grad(self):
         """(terms [num_clips, 9], gradient of the weighted total [F, NP]) at the current iterate."""
         terms = np.zeros((len(self._clips), NUM_TERMS), np.float32)
         grad = np.zeros((self.num_frames_total, self.NP), np.float32)
-        self._L.check(self._lib.parc_mopt_loss_and_grad(self._h, self._L.np_f32p(terms), self._L.np_f32p(grad)))
+        self._call("loss_and_grad", L.np_f32p(terms), L.np_f32p(grad))
         return terms, grad
 
     def step(self, n_iters: int):
         """n Adam iterations; returns the terms [n, num_clips, 9] each iteration's gradient came from."""
         terms = np.zeros((max(int(n_iters), 0), len(self._clips), NUM_TERMS), np.float32)
-        self._L.check(self._lib.parc_mopt_step(self._h, int(n_iters), self._L.np_f32p(terms) if n_iters > 0 else None))
+        self._call("step", int(n_iters), L.np_f32p(terms) if n_iters > 0 else None)
         return terms
-
-    def kernel_times(self):
-        out = np.zeros(6, np.float32)
-        self._L.check(self._lib.parc_mopt_kernel_times(self._h, self._L.np_f32p(out)))
-        return dict(zip(("fk", "patch", "points", "grad", "reduce", "adam"), out.tolist()))
 
     def get_frames(self):
         F, J = self.num_frames_total, self.B - 1
         rp, rr, jr = np.zeros((F, 3), np.float32), np.zeros((F, 4), np.float32), np.zeros((F, J, 4), np.float32)
-        self._L.check(self._lib.parc_mopt_get_frames(self._h, self._L.np_f32p(rp), self._L.np_f32p(rr), self._L.np_f32p(jr)))
+        self._call("get_frames", L.np_f32p(rp), L.np_f32p(rr), L.np_f32p(jr))
         return rp, rr, jr
 
     # ------------------------------------------------------------------ constraints
@@ -386,7 +371,7 @@ class MotionOptimizer:
         F = self.num_frames_total
         bp = np.zeros((F, self.B, 3), np.float32)
         br = np.zeros((F, self.B, 4), np.float32)
-        self._L.check(self._lib.parc_mopt_get_source_body(self._h, self._L.np_f32p(bp), self._L.np_f32p(br)))
+        self._call("get_source_body", L.np_f32p(bp), L.np_f32p(br))
         off = self._packed["frame_off"]
         out, all_clip, all_pts = [], [], []
         for ci, c in enumerate(clips):
@@ -411,8 +396,7 @@ class MotionOptimizer:
         if all_pts:
             pts = np.ascontiguousarray(np.array(all_pts, np.float32).reshape(-1, 3))
             cl = np.array(all_clip, np.int32)
-            self._L.check(self._lib.parc_mopt_build_constraints(self._h, len(cl), self._L.np_i32p(cl), self._L.np_f32p(pts),
-                                                                 CONSTRAINT_SGD_STEPS, CONSTRAINT_SGD_LR))
+            self._call("build_constraints", len(cl), L.np_i32p(cl), L.np_f32p(pts), CONSTRAINT_SGD_STEPS, CONSTRAINT_SGD_LR)
             k = 0
             for nc in out:
                 n = len(nc.cons_body)

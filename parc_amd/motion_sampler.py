@@ -20,20 +20,18 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
+from parc_amd import lib as L
 from parc_amd.char_model import CharModel
-from parc_amd.lib import destroy_handle
+from parc_amd.tool_handle import PlanCodec, ToolHandle, fill_struct
 
 FRAME_COMPONENTS = ("ROOT_POS", "ROOT_ROT", "JOINT_POS", "JOINT_ROT", "CONTACTS", "FLOOR_HEIGHTS")   # MDMFrameType (JOINT_VEL: unused)
-RELATIVE_Z = {"RELATIVE_TO_ROOT": 0, "RELATIVE_TO_ROOT_FLOOR": 1}
-AUG_MODE = {"NOISE": 0, "MAXPOOL_AND_BOXES": 1, "NONE": 2}
-POOL_NONE, POOL_2D, POOL_1D_X, POOL_1D_Y = 0, 1, 2, 3
+RELATIVE_Z, AUG_MODE = L.MSAMP_RELATIVE_Z, L.MSAMP_AUG_MODE
+POOL_NONE, POOL_2D, POOL_1D_X, POOL_1D_Y = L.MSAMP_POOL_NONE, L.MSAMP_POOL_2D, L.MSAMP_POOL_1D_X, L.MSAMP_POOL_1D_Y
 KERNELS = ("draw", "window", "heightfield")
-MAX_FRAMES, MAX_GRID, MAX_TERRAIN_CELLS, MAX_BOXES, BOX_FLOATS = 64, 32, 512 * 512, 64, 6   # PARC_MSAMP_* (include/parc_env.h)
+MAX_FRAMES, MAX_GRID, MAX_TERRAIN_CELLS = L.MSAMP_MAX_FRAMES, L.MSAMP_MAX_GRID, L.MSAMP_MAX_TERRAIN_CELLS
+MAX_BOXES, BOX_FLOATS = L.MSAMP_MAX_BOXES, L.MSAMP_BOX_FLOATS
 # the plan: (name, torch dtype, per-sample shape; "mb" = max_num_boxes, "gx" / "gy" = the patch), in the order of ParcMotionSamplerPlan
-PLAN_FIELDS = [("motion_id", torch.int32, ()), ("t0", torch.float32, ()), ("t_future", torch.float32, ()),
-               ("future_pos_noise", torch.float32, (3,)), ("change_height", torch.int32, ()), ("height_value", torch.float32, ()),
-               ("pool_kind", torch.int32, (3,)), ("pool_size", torch.int32, (3,)), ("num_boxes", torch.int32, ()),
-               ("boxes", torch.float32, ("mb", BOX_FLOATS)), ("noise", torch.float32, ("gx", "gy"))]
+PLAN_FIELDS = [(name, torch.int32 if t == "i" else torch.float32, shape) for name, t, shape in L.MSAMP_PLAN_FIELDS]
 
 
 def parse_config(cfg: dict) -> types.SimpleNamespace:
@@ -115,24 +113,19 @@ def check_clip_lengths(names: Sequence[str], num_frames: Sequence[int], T: int):
         raise ValueError(f"clips too short for windows of {T} frames: " + ", ".join(short))
 
 
+def plan_codec(cfg) -> PlanCodec:
+    """The plan of a parsed config: ``noise`` is carried only when the augmentation mode is ``NOISE``."""
+    return PlanCodec(L.MSAMP_PLAN_FIELDS, L.ParcMotionSamplerPlan, {"mb": cfg.max_num_boxes, "gx": cfg.Gx, "gy": cfg.Gy},
+                     optional=() if cfg.aug_mode == AUG_MODE["NOISE"] else ("noise",))
+
+
 def plan_shapes(n: int, cfg) -> Dict[str, tuple]:
-    sub = {"mb": cfg.max_num_boxes, "gx": cfg.Gx, "gy": cfg.Gy}
-    return {name: (n,) + tuple(sub.get(d, d) for d in shape) for name, _, shape in PLAN_FIELDS}
+    return {name: (n,) + shape for name, (_, shape) in plan_codec(cfg).fields.items()}
 
 
 def check_plan(plan: Dict[str, torch.Tensor], cfg) -> int:
     """Lengths and dtypes of a plan's arrays (no device access); returns n."""
-    n = int(plan["motion_id"].shape[0])
-    shapes = plan_shapes(n, cfg)
-    for name, dt, _ in PLAN_FIELDS:
-        t = plan.get(name)
-        if t is None:
-            if name == "noise" and cfg.aug_mode != AUG_MODE["NOISE"]:
-                continue
-            raise ValueError(f"plan: {name} is missing")
-        if tuple(t.shape) != shapes[name] or t.dtype != dt:
-            raise ValueError(f"plan: {name} must be {dt} {shapes[name]}, got {t.dtype} {tuple(t.shape)}")
-    return n
+    return plan_codec(cfg).struct(plan)[1]
 
 
 def assemble_features(motion: Dict[str, torch.Tensor], frame_components: Sequence[str]) -> torch.Tensor:
@@ -178,21 +171,20 @@ def export_batches(sampler, num_batches: int, batch_size: int, out_dir: str, see
     return files
 
 
-class MotionWindowSampler:
+class MotionWindowSampler(ToolHandle):
     """See the module docstring.  ``extra_vals`` (per clip ``dict(hf_mask_inds=[...], hf_maxmin=[X, Y, 2])`` or ``None``) overrides
     what the files hold; ``exclude`` drops clips by name (e.g. ones too short for a window)."""
+    PREFIX, KERNELS = "parc_msamp", KERNELS
 
     def __init__(self, cfg: dict, motion_file: str, char_file: str, device="cuda:0", extra_vals: Optional[Sequence[Optional[dict]]] = None,
                  exclude: Sequence[str] = ()):
-        from parc_amd import lib as L
         from parc_amd import motion_lib, ms_file
-        self._L, self._lib = L, L.load()
+        super().__init__(device)
         self.cfg = parse_config(cfg)
+        self._codec = plan_codec(self.cfg)
         self.char_file = char_file
         self.char_model = CharModel(char_file)
         self.B = self.char_model.get_num_bodies()
-        self.device = torch.device(device)
-        self.device_index = L.device_index(self.device)
         clips = [c for c in motion_lib.load_motion_file(motion_file, verbose=False) if c.name not in set(exclude)]
         if extra_vals is not None and len(extra_vals) != len(clips):
             raise ValueError("extra_vals: one entry per clip")
@@ -221,18 +213,13 @@ class MotionWindowSampler:
             for i, r in zip(missing, res):
                 extra[i] = dict(hf_mask_inds=r["hf_mask_inds"], hf_maxmin=r["hf_maxmin"])
         self.clips, self.extra_vals = clips, extra
-        self._h = None
         self._create()
         self._upload()
 
     # ------------------------------------------------------------------ handle
-    def __del__(self):
-        destroy_handle(self, "parc_msamp_destroy")
-
     def _create(self):
-        L, c = self._L, self.cfg
+        c = self.cfg
         p = L.ParcMotionSamplerParams()
-        p.struct_size = C.sizeof(L.ParcMotionSamplerParams)
         p.device = self.device_index
         p.model = L.make_char_model(self.char_model)
         p.num_frames, p.times_host = c.T, L.np_f32p(c.times)
@@ -244,13 +231,10 @@ class MotionWindowSampler:
         p.max_num_boxes, p.box_min_len, p.box_max_len = c.max_num_boxes, c.box_min_len, c.box_max_len
         p.hf_maxpool_chance, p.hf_max_maxpool_size, p.hf_change_height_chance = c.hf_maxpool_chance, c.hf_max_maxpool_size, c.hf_change_height_chance
         p.future_pos_noise_scale, p.future_window_min, p.future_window_max = c.future_pos_noise_scale, c.future_window_min, c.future_window_max
-        h = C.c_void_p()
-        L.check(self._lib.parc_msamp_create(C.byref(p), C.byref(h)))
-        self._h = h
+        self._create_handle(p)
 
     def _upload(self):
         from parc_amd.motion_opt import OptClip, clip_struct, pack_clips
-        L = self._L
         oc = [OptClip(c.root_pos, c.root_rot, c.joint_rot,
                       c.contacts if c.contacts is not None else np.zeros((c.num_frames, self.B), np.float32),
                       np.asarray(c.terrain.hf, np.float32), np.asarray(c.terrain.min_point, np.float32), float(c.terrain.dx), c.fps, c.name)
@@ -269,7 +253,7 @@ class MotionWindowSampler:
         info.hf_maxmin_host, info.mask_off_host = L.np_f32p(maxmin), mask_off.ctypes.data_as(L.i64p)
         info.mask_cells_host = L.np_i32p(cells) if cells.size else None
         info.fps_host, info.loop_modes_host, info.weights_host = L.np_i32p(fps), L.np_i32p(loop), w.ctypes.data_as(L.f64p)
-        L.check(self._lib.parc_msamp_set_clips(self._h, C.byref(st), C.byref(info)))
+        self._call("set_clips", C.byref(st), C.byref(info))
         self.packed = pk
         self.num_frames = np.diff(pk["frame_off"]).astype(np.int64)
         self.lengths = np.array([np.float32(1.0 / c.fps * (c.num_frames - 1)) for c in self.clips], np.float32)
@@ -279,33 +263,14 @@ class MotionWindowSampler:
     # ------------------------------------------------------------------ plans and outputs
     def empty_plan(self, n: int, zero: bool = True) -> Dict[str, torch.Tensor]:
         """The plan's device arrays; ``zero=False`` leaves them uninitialised (``draw_plan`` writes every entry)."""
-        shapes = plan_shapes(n, self.cfg)
-        make = torch.zeros if zero else torch.empty
-        return {name: make(shapes[name], dtype=dt, device=self.device) for name, dt, _ in PLAN_FIELDS
-                if name != "noise" or self.cfg.aug_mode == AUG_MODE["NOISE"]}
+        return self._codec.empty(n, self.device, zero)
 
     def plan_from_numpy(self, arrays: Dict[str, np.ndarray]) -> Dict[str, torch.Tensor]:
         """A plan from host arrays (missing augmentation fields are zeros = no augmentation step)."""
-        plan = self.empty_plan(int(np.asarray(arrays["motion_id"]).shape[0]))
-        for k, t in plan.items():
-            if k in arrays:
-                a = torch.as_tensor(np.ascontiguousarray(arrays[k])).to(t.dtype)
-                if a.shape != t.shape:
-                    raise ValueError(f"plan: {k} must have shape {tuple(t.shape)}, got {tuple(a.shape)}")
-                t.copy_(a)
-        return plan
+        return self._codec.from_numpy(arrays, self.device, required=("motion_id",))
 
     def _plan_struct(self, plan):
-        n = check_plan(plan, self.cfg)
-        st = self._L.ParcMotionSamplerPlan()
-        st.n = n
-        for name, _, _ in PLAN_FIELDS:
-            t = plan.get(name)
-            if t is not None:
-                if t.device != self.device or not t.is_contiguous():
-                    raise ValueError(f"plan: {name} must be contiguous on {self.device}")
-                setattr(st, name, t.data_ptr())
-        return st, n
+        return self._codec.struct(plan, self.device)
 
     def _outputs(self, n: int, hf: bool, bounds: bool = False):
         c, J = self.cfg, self.B - 1
@@ -317,18 +282,12 @@ class MotionWindowSampler:
                 o["floor_heights"] = z(n, c.T)
             if bounds:
                 o["hf_bounds"] = z(n, c.Gx, c.Gy, 2)
-        st = self._L.ParcMotionSamplerOutputs()
-        for k, t in o.items():
-            setattr(st, k, t.data_ptr())
-        return o, st
+        return o, fill_struct(L.ParcMotionSamplerOutputs, o)
 
     def _motion_dict(self, o):
         names = dict(ROOT_POS="root_pos", ROOT_ROT="root_rot", JOINT_POS="joint_pos", JOINT_ROT="joint_rot", CONTACTS="contacts",
                      FLOOR_HEIGHTS="floor_heights")
         return {k: (o[names[k]].unsqueeze(-1) if k == "FLOOR_HEIGHTS" else o[names[k]]) for k in self.cfg.frame_components if names[k] in o}
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     # ------------------------------------------------------------------ sampling
     def sample_with(self, plan: Dict[str, torch.Tensor], return_bounds: bool = False, validate: bool = False):
@@ -336,8 +295,7 @@ class MotionWindowSampler:
         ``return_bounds`` also the per-window bounds [n, Gx, Gy, 2].  ``validate`` synchronises and raises on a bad plan entry."""
         st, n = self._plan_struct(plan)
         o, ost = self._outputs(n, True, return_bounds)
-        with torch.cuda.device(self.device):
-            self._L.check(self._lib.parc_msamp_sample_with(self._h, C.byref(st), C.byref(ost), self._stream()))
+        self._call("sample_with", C.byref(st), C.byref(ost), self._stream())
         if validate:
             self.check_status()
         ret = (self._motion_dict(o), o["hfs"], o["target_pos"], o["target_rot"])
@@ -346,31 +304,28 @@ class MotionWindowSampler:
     def draw_plan(self, n: int, seed: int) -> Dict[str, torch.Tensor]:
         plan = self.empty_plan(n, zero=False)
         st, _ = self._plan_struct(plan)
-        with torch.cuda.device(self.device):
-            self._L.check(self._lib.parc_msamp_draw_plan(self._h, C.c_uint64(int(seed)), C.byref(st), self._stream()))
+        self._call("draw_plan", C.c_uint64(int(seed)), C.byref(st), self._stream())
         return plan
 
     def sample(self, n: int, seed: int):
         plan = self.empty_plan(n, zero=False)
         st, _ = self._plan_struct(plan)
         o, ost = self._outputs(n, True)
-        with torch.cuda.device(self.device):
-            self._L.check(self._lib.parc_msamp_sample(self._h, C.c_uint64(int(seed)), C.byref(st), C.byref(ost), self._stream()))
+        self._call("sample", C.c_uint64(int(seed)), C.byref(st), C.byref(ost), self._stream())
         return self._motion_dict(o), o["hfs"], o["target_pos"], o["target_rot"]
 
     def check_status(self):
         """Synchronises; raises if a kernel met a bad plan entry (motion id, box count, pool) since the last call."""
         v = C.c_int32()
-        self._L.check(self._lib.parc_msamp_plan_status(self._h, self._stream(), C.byref(v)))
+        self._call("plan_status", self._stream(), C.byref(v))
         if v.value:
-            raise self._L.ParcError("bad plan: " + "; ".join(m for b, m in self._L.MSAMP_STATUS.items() if v.value & b))
+            raise L.ParcError("bad plan: " + "; ".join(m for b, m in L.MSAMP_STATUS.items() if v.value & b))
 
     def motion_sequences_for_id(self, i: int) -> Dict[str, torch.Tensor]:
         """``get_motion_sequences_for_id``: the windows starting at frames 0 .. num_frames - T - 1 of clip ``i`` (motion only)."""
         n = int(self.num_frames[i]) - self.cfg.T
         o, ost = self._outputs(n, False)
-        with torch.cuda.device(self.device):
-            self._L.check(self._lib.parc_msamp_enumerate(self._h, int(i), C.byref(ost), self._stream()))
+        self._call("enumerate", int(i), C.byref(ost), self._stream())
         return self._motion_dict(o)
 
     def assemble_features(self, motion: Dict[str, torch.Tensor]) -> torch.Tensor:
@@ -390,8 +345,3 @@ class MotionWindowSampler:
             mean[:, sl] = 0.0
             std[:, sl] = 1.0
         return mean, torch.clamp(std, min=1e-5)
-
-    def kernel_times(self):
-        out = np.zeros(3, np.float32)
-        self._L.check(self._lib.parc_msamp_kernel_times(self._h, self._L.np_f32p(out)))
-        return dict(zip(KERNELS, out.tolist()))

@@ -14,12 +14,13 @@ from typing import List, Sequence
 
 import numpy as np
 
+from parc_amd import lib as L
 from parc_amd.char_model import CharModel
-from parc_amd.lib import destroy_handle
 from parc_amd.motion_opt import model_points_params
 from parc_amd.motion_opt import OptClip, char_point_samples, clip_from_ms, clip_struct, pack_clips  # noqa: F401  (re-exported for callers)
+from parc_amd.tool_handle import ToolHandle
 
-SDF_PRUNED, SDF_BRUTE = 0, 1
+SDF_PRUNED, SDF_BRUTE = L.MTERR_SDF_PRUNED, L.MTERR_SDF_BRUTE
 Z_BUF, JUMP_BUF, MAX_JERK = 3.0, 0.8, 11666.3906
 CLIP_OUTPUTS = ("pen_loss", "contact_loss", "mean_jerk", "jerk_frac", "max_root_z", "min_hf")
 KERNELS = ("fk", "init", "points", "reduce", "cells", "gather")
@@ -29,7 +30,6 @@ MISSING_POINT_VALUE = 99999.9999   # compute_hf_mask_inds' initial lowest point
 def analyzer_params(char_model: CharModel, flat_points, point_body, z_buf=Z_BUF, jump_buf=JUMP_BUF, max_jerk=MAX_JERK,
                     sdf_mode=SDF_PRUNED, device: int = 0):
     """``ParcMotionTerrainParams``: every body scored with its own contact column (``compute_motion_loss``' ``contacts[..., b]``)."""
-    from parc_amd import lib as L
     p = model_points_params(L.ParcMotionTerrainParams(), char_model, flat_points, point_body, device)
     for b in range(char_model.get_num_bodies()):
         p.contact_body_id[b] = b
@@ -38,62 +38,49 @@ def analyzer_params(char_model: CharModel, flat_points, point_body, z_buf=Z_BUF,
     return p
 
 
-class MotionTerrainAnalyzer:
+class MotionTerrainAnalyzer(ToolHandle):
     """``MotionTerrainAnalyzer(char_file, device).analyze(clips)``: ``compute_hf_extra_vals`` + ``compute_motion_loss`` + jerk
     statistics for a whole batch of clips on the GPU.  ``sdf_mode = SDF_BRUTE`` scans every cell for every point (for tests: the
     default ring-pruned search returns the same bits); ``points`` replaces the sampler's points."""
+    PREFIX, KERNELS, DEVICE_CONTEXT = "parc_mterr", KERNELS, False
 
     def __init__(self, char_file: str, device="cuda:0", sdf_mode: int = SDF_PRUNED, points=None):
-        import torch  # noqa: F401  (one HIP runtime: torch's, loaded before the library)
-        from parc_amd import lib as L
-        self._L = L
-        self._lib = L.load()
+        super().__init__(device)
         self.char_model = CharModel(char_file)
         if points is None:   # get_char_point_samples' defaults
             _, self.points, self.point_body = char_point_samples(self.char_model)
         else:                # (flat [P, 3], body index [P]), e.g. the reference's own samples
             self.points = np.ascontiguousarray(points[0], np.float32)
             self.point_body = np.ascontiguousarray(points[1], np.int32)
-        self.device_index = L.device_index(device)
         self.sdf_mode = int(sdf_mode)
         self.B = self.char_model.get_num_bodies()
         self.D = self.char_model.get_dof_size()
-        self._h = None
         self._key = None
         self._packed = None
-
-    def __del__(self):
-        self._destroy()
-
-    def _destroy(self):
-        destroy_handle(self, "parc_mterr_destroy")
 
     def _handle(self, z_buf, jump_buf, max_jerk):
         key = (float(z_buf), float(jump_buf), float(max_jerk))
         if self._h is None or self._key != key:
             self._destroy()
-            p = analyzer_params(self.char_model, self.points, self.point_body, *key, sdf_mode=self.sdf_mode, device=self.device_index)
-            h = C.c_void_p()
-            self._L.check(self._lib.parc_mterr_create(C.byref(p), C.byref(h)))
-            self._h, self._key = h, key
-        return self._h
+            self._create_handle(analyzer_params(self.char_model, self.points, self.point_body, *key, sdf_mode=self.sdf_mode,
+                                                device=self.device_index))
+            self._key = key
 
     def run(self, clips: Sequence[OptClip], z_buf=Z_BUF, jump_buf=JUMP_BUF, max_jerk=MAX_JERK):
         """The flat outputs of one batched run: ``clip_out`` [C, 6] (``CLIP_OUTPUTS``), ``counts`` [F], ``inds`` int32 [K, 2] in
         frame order, ``hf_maxmin`` [cells, 2] and the packing (``frame_off``, ``hf_off``, ...)."""
-        L = self._L
-        h = self._handle(z_buf, jump_buf, max_jerk)
+        self._handle(z_buf, jump_buf, max_jerk)
         pk = pack_clips(clips, self.B, self.D)
         st = clip_struct(pk, len(clips))
-        L.check(self._lib.parc_mterr_set_clips(h, C.byref(st)))
+        self._call("set_clips", C.byref(st))
         F, ncell = int(pk["frame_off"][-1]), int(pk["hf_off"][-1])
         out = np.zeros((len(clips), len(CLIP_OUTPUTS)), np.float32)
         counts = np.zeros(F, np.int32)
         maxmin = np.zeros((ncell, 2), np.float32)
         total = C.c_int64()
-        L.check(self._lib.parc_mterr_run(h, L.np_f32p(out), L.np_i32p(counts), L.np_f32p(maxmin), C.byref(total)))
+        self._call("run", L.np_f32p(out), L.np_i32p(counts), L.np_f32p(maxmin), C.byref(total))
         inds = np.zeros((int(total.value), 2), np.int32)
-        L.check(self._lib.parc_mterr_get_mask_inds(h, L.np_i32p(inds) if inds.size else None))
+        self._call("get_mask_inds", L.np_i32p(inds) if inds.size else None)
         self._packed = pk
         return dict(packed=pk, clip_out=out, counts=counts, inds=inds, hf_maxmin=maxmin)
 
@@ -120,17 +107,12 @@ class MotionTerrainAnalyzer:
         """(lowest body point per cell [cells], touched flags [cells]) of the last run, cells in packing order."""
         n = int(self._packed["hf_off"][-1])
         mh, tc = np.zeros(n, np.float32), np.zeros(n, np.int32)
-        self._L.check(self._lib.parc_mterr_get_min_heights(self._h, self._L.np_f32p(mh), self._L.np_i32p(tc)))
+        self._call("get_min_heights", L.np_f32p(mh), L.np_i32p(tc))
         return mh, tc
 
     def point_sdf(self, frame0: int, num_frames: int):
         """Raw (ground, air) SDF minima [num_frames, P] of the batch's frames [frame0, frame0 + num_frames)."""
         P = self.points.shape[0]
         g, a = np.zeros((num_frames, P), np.float32), np.zeros((num_frames, P), np.float32)
-        self._L.check(self._lib.parc_mterr_point_sdf(self._h, int(frame0), int(num_frames), self._L.np_f32p(g), self._L.np_f32p(a)))
+        self._call("point_sdf", int(frame0), int(num_frames), L.np_f32p(g), L.np_f32p(a))
         return g, a
-
-    def kernel_times(self):
-        out = np.zeros(6, np.float32)
-        self._L.check(self._lib.parc_mterr_kernel_times(self._h, self._L.np_f32p(out)))
-        return dict(zip(KERNELS, out.tolist()))

@@ -17,11 +17,14 @@ from typing import List, Optional
 
 import numpy as np
 
-from parc_amd.lib import destroy_handle
+from parc_amd import lib as L
+from parc_amd.tool_handle import ToolHandle
+from parc_amd.util import path_loader
 
-FOUND, NO_PATH, OVER_MAX_COST, BUDGET, NO_DRAW = range(5)
-STATUS_NAMES = ("FOUND", "NO_PATH", "OVER_MAX_COST", "BUDGET", "NO_DRAW")
-MAX_DIM, MAX_JUMP_RADIUS, JUMP_WORDS = 64, 8, 8
+STATUS_NAMES = L.PATHPLAN_STATUS
+FOUND, NO_PATH, OVER_MAX_COST, BUDGET, NO_DRAW = range(len(STATUS_NAMES))
+MAX_DIM, MAX_JUMP_RADIUS, JUMP_WORDS = L.PATHPLAN_MAX_DIM, L.PATHPLAN_MAX_JUMP_RADIUS, L.PATHPLAN_JUMP_WORDS
+KERNELS = ("prepare", "search", "graph")   # the two phases of the last plan, and the last graph
 DIRECTIONS = ((-1, 0), (1, 0), (0, -1), (0, 1), (-1, -1), (-1, 1), (1, -1), (1, 1))   # astar.py:112, the bits of the neighbour mask
 
 
@@ -73,9 +76,7 @@ class PlannerConfig:
 
     @classmethod
     def load(cls, path) -> "PlannerConfig":
-        import yaml
-        with open(path) as f:
-            return cls.from_dict(yaml.safe_load(f))
+        return cls.from_dict(path_loader.load_config(path))
 
     def to_dict(self) -> dict:
         d = dataclasses.asdict(self)
@@ -103,7 +104,6 @@ class PathPlan:
 def planner_params(settings: AStarSettings, dim_x, dim_y, dx, dy, min_point=(0.0, 0.0), simplify_terrain=True, max_expansions=65536,
                    max_nodes=None, max_points=None, device: int = 0):
     """``ParcPathPlanParams`` for one grid shape."""
-    from parc_amd import lib as L
     p = L.ParcPathPlanParams()
     p.struct_size = C.sizeof(L.ParcPathPlanParams)
     p.device = int(device)
@@ -149,30 +149,20 @@ def select_first_success(status, num_terrains, num_attempts):
     return np.where(ok.any(axis=1), first, -1).astype(np.int64)
 
 
-class TerrainPathPlanner:
+class TerrainPathPlanner(ToolHandle):
     """``TerrainPathPlanner(device, settings).plan(hfs)``; one handle per grid shape, rebuilt when the shape or ``dx`` changes."""
+    PREFIX, KERNELS, DEVICE_CONTEXT = "parc_pathplan", KERNELS, False
 
     def __init__(self, device="cuda:0", settings: Optional[AStarSettings] = None, simplify_terrain=True, max_expansions=65536,
                  min_point=(0.0, 0.0), max_nodes=None, max_points=None):
-        import torch  # noqa: F401  (one HIP runtime: torch's, loaded before the library)
-        from parc_amd import lib as L
-        self._L = L
-        self._lib = L.load()
+        super().__init__(device)
         self.settings = settings if settings is not None else AStarSettings()
         self.simplify_terrain = bool(simplify_terrain)
         self.max_expansions = int(max_expansions)
         self.min_point = (float(min_point[0]), float(min_point[1]))
         self.max_nodes, self.max_points = max_nodes, max_points
-        self.device_index = L.device_index(device)
-        self._h = None
         self._key = None
         self._params = None
-
-    def __del__(self):
-        self._destroy()
-
-    def _destroy(self):
-        destroy_handle(self, "parc_pathplan_destroy")
 
     def _handle(self, X, Y, dx, dy):
         key = (X, Y, float(np.float32(dx)), float(np.float32(dy)))
@@ -180,20 +170,17 @@ class TerrainPathPlanner:
             self._destroy()
             p = planner_params(self.settings, X, Y, dx, dy, self.min_point, self.simplify_terrain, self.max_expansions, self.max_nodes,
                                self.max_points, self.device_index)
-            h = C.c_void_p()
-            self._L.check(self._lib.parc_pathplan_create(C.byref(p), C.byref(h)))
-            self._h, self._key, self._params = h, key, p
-        return self._h
+            self._create_handle(p)
+            self._key, self._params = key, p
 
     def plan(self, hfs, starts=None, goals=None, seed: int = 0, dx: float = 0.4, dy: Optional[float] = None, first_query: int = 0) -> PathPlan:
         """Plan one path per heightfield of ``hfs`` ``[Q, X, Y]``.  ``starts`` / ``goals`` ``[Q, 2]`` inject the cells; without them
         both are drawn on the device from ``(seed, first_query + q)``."""
-        L = self._L
         hfs = np.ascontiguousarray(hfs, np.float32)
         if hfs.ndim != 3:
             raise ValueError("hfs must be [Q, X, Y]")
         Q, X, Y = hfs.shape
-        h = self._handle(X, Y, dx, dx if dy is None else dy)
+        self._handle(X, Y, dx, dx if dy is None else dy)
         p = self._params
         if (starts is None) != (goals is None):
             raise ValueError("starts and goals go together")
@@ -207,8 +194,8 @@ class TerrainPathPlanner:
         out = L.ParcPathPlanOutputs()
         for n, t in L.PATHPLAN_OUTPUT_FIELDS:
             setattr(out, n, L.np_f32p(arr[n]) if t == "f" else L.np_i32p(arr[n]))
-        L.check(self._lib.parc_pathplan_run(h, Q, L.np_f32p(hfs), L.np_i32p(s) if s is not None else None,
-                                            L.np_i32p(g) if g is not None else None, int(seed), int(first_query), C.byref(out)))
+        self._call("run", Q, L.np_f32p(hfs), L.np_i32p(s) if s is not None else None, L.np_i32p(g) if g is not None else None, int(seed),
+                   int(first_query), C.byref(out))
         nn, npt = arr["num_nodes"], arr["num_points"]
         if nn.max(initial=0) > p.max_nodes or npt.max(initial=0) > p.max_points:
             raise L.ParcError(f"a path has {int(nn.max())} cells / {int(npt.max())} points, above max_nodes = {p.max_nodes} / max_points = "
@@ -225,15 +212,8 @@ class TerrainPathPlanner:
         cliff = np.zeros((n, X, Y), np.uint8)
         jump = np.zeros((n, X, Y, JUMP_WORDS), np.uint32)
         u8 = C.POINTER(C.c_uint8)
-        self._L.check(self._lib.parc_pathplan_get_graph(self._h, int(q0), int(n), nbr.ctypes.data_as(u8), cliff.ctypes.data_as(u8),
-                                                        jump.ctypes.data_as(C.POINTER(C.c_uint32))))
+        self._call("get_graph", int(q0), int(n), nbr.ctypes.data_as(u8), cliff.ctypes.data_as(u8), jump.ctypes.data_as(C.POINTER(C.c_uint32)))
         return nbr, cliff, jump
-
-    def kernel_times(self):
-        """Device ms of the last ``plan``: prepare, search, and the last ``graph``."""
-        ms = np.zeros(3, np.float32)
-        self._L.check(self._lib.parc_pathplan_kernel_times(self._h, self._L.np_f32p(ms)))
-        return dict(zip(("prepare", "search", "graph"), ms.tolist()))
 
     def plan_terrains(self, hfs, num_attempts: int = 10, seed: int = 0, dx: float = 0.4, dy: Optional[float] = None):
         """The reference's retry loop run wide: ``num_attempts`` start / goal draws per terrain, all ``Q x num_attempts`` queries in one

@@ -16,12 +16,14 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from parc_amd.lib import destroy_handle
+from parc_amd import lib as L
+from parc_amd.tool_handle import PlanCodec, ToolHandle
+from parc_amd.util import path_loader
 
-MODES = ("BOXES", "PATHS", "STAIRS")
-MAX_DIM, MAX_BOXES, MAX_PATHS, MAX_STAIRS, MAX_POOL, PATH_POINTS, MAX_STEPS = 64, 64, 64, 16, 8, 1000, 1024   # PARC_TGEN_* (include/parc_env.h)
-BOX_FLOATS, STAIR_FLOATS = 6, 7
-KERNELS = ("draw", "generate")
+MODES = L.TGEN_MODES
+MAX_DIM, MAX_BOXES, MAX_PATHS, MAX_STAIRS, MAX_POOL = L.TGEN_MAX_DIM, L.TGEN_MAX_BOXES, L.TGEN_MAX_PATHS, L.TGEN_MAX_STAIRS, L.TGEN_MAX_POOL
+PATH_POINTS, MAX_STEPS, BOX_FLOATS, STAIR_FLOATS = L.TGEN_PATH_POINTS, L.TGEN_MAX_STEPS, L.TGEN_BOX_FLOATS, L.TGEN_STAIR_FLOATS
+KERNELS = ("draw", "generate")   # draw_plan; generate_with / generate
 
 
 class _Settings:
@@ -97,9 +99,7 @@ class TerrainGenConfig:
 
     @classmethod
     def load(cls, path) -> "TerrainGenConfig":
-        import yaml
-        with open(path) as f:
-            return cls.from_dict(yaml.safe_load(f))
+        return cls.from_dict(path_loader.load_config(path))
 
     def to_dict(self) -> dict:
         return dict(boxes=self.boxes.to_config(), paths=self.paths.to_config(), stairs=self.stairs.to_config())
@@ -137,7 +137,6 @@ def check_limits(mode: str, settings, dim_x: int, dim_y: int):
 
 def generator_params(mode: str, settings, dim_x, dim_y, dx, dy=None, min_point=(0.0, 0.0), device: int = 0):
     """``ParcTerrainGenParams`` of one mode and grid shape (the blocks of the other two modes keep their class defaults)."""
-    from parc_amd import lib as L
     p = L.ParcTerrainGenParams()
     p.struct_size = C.sizeof(L.ParcTerrainGenParams)
     p.device = int(device)
@@ -153,13 +152,12 @@ def generator_params(mode: str, settings, dim_x, dim_y, dx, dy=None, min_point=(
     return p
 
 
-class TerrainGenerator:
+class TerrainGenerator(ToolHandle):
     """See the module docstring.  ``settings`` is the mode's dataclass (class defaults when omitted)."""
+    PREFIX, KERNELS = "parc_tgen", KERNELS
 
     def __init__(self, mode: str, dim_x: int = 16, dim_y: int = 16, dx: float = 0.4, dy: Optional[float] = None, settings=None,
                  device="cuda:0", min_point=(0.0, 0.0)):
-        import torch
-        from parc_amd import lib as L
         if mode not in MODES:
             raise ValueError(f"procgen mode {mode!r}: the generator builds {MODES}")
         self.mode = mode
@@ -169,62 +167,23 @@ class TerrainGenerator:
         self.dim_x, self.dim_y = int(dim_x), int(dim_y)
         self.dx, self.dy = float(dx), float(dx if dy is None else dy)
         self.min_point = (float(min_point[0]), float(min_point[1]))
-        self._h = None
         check_limits(mode, self.settings, self.dim_x, self.dim_y)
-        self._L, self._lib = L, L.load()
-        self.device = torch.device(device)
-        self.device_index = L.device_index(self.device)
+        super().__init__(device)
         self.fields = plan_fields(mode, self.settings)
-        p = generator_params(mode, self.settings, self.dim_x, self.dim_y, self.dx, self.dy, self.min_point, self.device_index)
-        h = C.c_void_p()
-        L.check(self._lib.parc_tgen_create(C.byref(p), C.byref(h)))
-        self._h = h
-
-    def __del__(self):
-        destroy_handle(self, "parc_tgen_destroy")
+        self._codec = PlanCodec([(k, "f", s) for k, s in self.fields.items()], L.ParcTerrainGenPlan)
+        self._create_handle(generator_params(mode, self.settings, self.dim_x, self.dim_y, self.dx, self.dy, self.min_point, self.device_index))
 
     # ------------------------------------------------------------------ plans
     def empty_plan(self, n: int, zero: bool = True):
         """The plan's device arrays; ``zero=False`` leaves them uninitialised (``draw_plan`` writes every entry)."""
-        import torch
-        make = torch.zeros if zero else torch.empty
-        return {k: make((int(n),) + s, dtype=torch.float32, device=self.device) for k, s in self.fields.items()}
+        return self._codec.empty(n, self.device, zero)
 
     def plan_from_numpy(self, arrays: Dict[str, np.ndarray]):
         """A plan from host arrays ``[n, ...]``; every field of the mode is required."""
-        import torch
-        plan = {}
-        for k, s in self.fields.items():
-            if k not in arrays:
-                raise ValueError(f"plan: {k} is missing")
-            a = np.ascontiguousarray(arrays[k], np.float32)
-            if a.shape[1:] != s:
-                raise ValueError(f"plan: {k} must have shape (n,) + {s}, got {a.shape}")
-            plan[k] = torch.from_numpy(a).to(self.device)
-        return plan
+        return self._codec.from_numpy(arrays, self.device, required=tuple(self.fields))
 
     def _plan_struct(self, plan):
-        import torch
-        first = next(iter(self.fields))
-        if first not in plan:
-            raise ValueError(f"plan: {first} is missing")
-        n = int(plan[first].shape[0])
-        st = self._L.ParcTerrainGenPlan()
-        st.n = n
-        for k, s in self.fields.items():
-            t = plan.get(k)
-            if t is None:
-                raise ValueError(f"plan: {k} is missing")
-            if tuple(t.shape) != (n,) + s or t.dtype != torch.float32:
-                raise ValueError(f"plan: {k} must be torch.float32 {(n,) + s}, got {t.dtype} {tuple(t.shape)}")
-            if t.device != self.device or not t.is_contiguous():
-                raise ValueError(f"plan: {k} must be contiguous on {self.device}")
-            setattr(st, k, t.data_ptr())
-        return st, n
-
-    def _stream(self):
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return self._codec.struct(plan, self.device)
 
     def _hf(self, n):
         import torch
@@ -232,35 +191,22 @@ class TerrainGenerator:
 
     # ------------------------------------------------------------------ generation
     def draw_plan(self, n: int, seed: int, first_terrain: int = 0):
-        import torch
         plan = self.empty_plan(n, zero=False)
         st, _ = self._plan_struct(plan)
-        with torch.cuda.device(self.device):
-            self._L.check(self._lib.parc_tgen_draw_plan(self._h, C.c_uint64(int(seed)), C.c_uint64(int(first_terrain)), C.byref(st), self._stream()))
+        self._call("draw_plan", C.c_uint64(int(seed)), C.c_uint64(int(first_terrain)), C.byref(st), self._stream())
         return plan
 
     def generate_with(self, plan, validate: bool = False):
         """``hf [n, X, Y]`` of ``plan``.  ``validate`` runs a pass over the plan first and synchronises: a non-finite entry (or a stair
         of more than ``PARC_TGEN_MAX_STEPS`` steps) raises, naming the field, and the generator is not launched."""
-        import torch
         st, n = self._plan_struct(plan)
         hf = self._hf(n)
-        with torch.cuda.device(self.device):
-            self._L.check(self._lib.parc_tgen_generate_with(self._h, C.byref(st), hf.data_ptr(), int(bool(validate)), self._stream()))
+        self._call("generate_with", C.byref(st), hf.data_ptr(), int(bool(validate)), self._stream())
         return hf
 
     def generate(self, n: int, seed: int, first_terrain: int = 0):
-        import torch
         if int(n) < 1:
             raise ValueError("n must be >= 1")
         hf = self._hf(int(n))
-        with torch.cuda.device(self.device):
-            self._L.check(self._lib.parc_tgen_generate(self._h, int(n), C.c_uint64(int(seed)), C.c_uint64(int(first_terrain)), hf.data_ptr(),
-                                                       self._stream()))
+        self._call("generate", int(n), C.c_uint64(int(seed)), C.c_uint64(int(first_terrain)), hf.data_ptr(), self._stream())
         return hf
-
-    def kernel_times(self):
-        """Device ms of the last ``draw_plan`` and the last ``generate_with`` / ``generate`` (0 = not run)."""
-        ms = np.zeros(2, np.float32)
-        self._L.check(self._lib.parc_tgen_kernel_times(self._h, self._L.np_f32p(ms)))
-        return dict(zip(KERNELS, ms.tolist()))
