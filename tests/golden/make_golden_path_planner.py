@@ -15,6 +15,12 @@ the decision margin.  A candidate is KEPT only if it has zero ties and, for ``w_
 then agree with the reference exactly (edge sets, nodes, fp32 cost bits, verdict) -- asserted here.  Asserted and written down per file:
 at least a third of the queries found and a third not; over all files at least five found paths over a jump edge of three or more
 cells, at least four simplified queries with a start / goal index of 0 and four with an index of dim - 1.  Fixtures hold data only.
+
+A case carries its grid ``(X, Y)``, ``dx``, ``dy`` and ``min_point``.  A case whose ``max_cost`` is ``None`` takes it from the reference's
+own output: a first pass with the class default lists the costs of the kept found paths, a value just under their median (two decimals)
+becomes ``max_cost`` and a second pass with the same draws gives the recorded verdicts; such a file needs at least three FOUND and three
+OVER_MAX_COST queries, and its thirds rule counts OVER_MAX_COST with the found paths.  The square files were written before ``dy`` was
+stored (readers default it to ``dx``); regenerate single cases by name to leave them as they are.
 """
 import json
 import os
@@ -52,12 +58,18 @@ torch.set_num_threads(1)
 TERRAINS = ["TEASER_TERRAIN", "civilization", "sfu"]
 STAGE2 = dict(ref.DEFAULTS, max_jump_z_diff=0.5, min_jump_z_diff=-1.0, w_bumpy=0.0, uniform_cost_max=0.5, min_start_end_xy_dist=5.0)
 DX = 0.4
-# (file, dim, settings, simplify, queries kept, candidates drawn, seed)
-CASES = [("default_16", 16, STAGE2, True, 30, 110, 11),
-         ("nosimplify_16", 16, STAGE2, False, 18, 50, 12),
-         ("bumpy_16", 16, dict(STAGE2, w_bumpy=1.0), True, 18, 50, 13),
-         ("classdefaults_16", 16, dict(ref.DEFAULTS), True, 18, 50, 14),
-         ("default_32", 32, STAGE2, True, 6, 14, 15)]
+ORIGIN = (0.0, 0.0)
+# (file, (X, Y), dx, dy, min_point, settings, simplify, queries kept, candidates drawn, seed)
+CASES = [("default_16", (16, 16), DX, DX, ORIGIN, STAGE2, True, 30, 110, 11),
+         ("nosimplify_16", (16, 16), DX, DX, ORIGIN, STAGE2, False, 18, 50, 12),
+         ("bumpy_16", (16, 16), DX, DX, ORIGIN, dict(STAGE2, w_bumpy=1.0), True, 18, 50, 13),
+         ("classdefaults_16", (16, 16), DX, DX, ORIGIN, dict(ref.DEFAULTS), True, 18, 50, 14),
+         ("default_32", (32, 32), DX, DX, ORIGIN, STAGE2, True, 6, 14, 15),
+         # off the square: a shifted origin, dx != dy in both orders, jump radii 5 and 3; max_cost None = chosen from the reference's costs
+         ("rect_12x20", (12, 20), 0.4, 0.4, (1.7, -2.3),
+          dict(STAGE2, min_start_end_xy_dist=3.0, uniform_cost_min=0.1, uniform_cost_max=0.6, max_cost=None), True, 12, 60, 16),
+         ("aniso_13x17", (13, 17), 0.4, 0.5, (1.7, -2.3), dict(STAGE2, min_start_end_xy_dist=3.0, max_jump_xy_dist=2.0), True, 12, 60, 17),
+         ("aniso_20x11", (20, 11), 0.5, 0.4, (-3.1, 0.9), dict(STAGE2, min_start_end_xy_dist=2.5, max_jump_xy_dist=1.2), True, 12, 60, 18)]
 
 _ctx = {}
 _orig_search = astar.a_star_search
@@ -91,9 +103,9 @@ def settings_obj(d):
     return s
 
 
-def run_candidate(hf_window, settings, simplify, seed, query):
+def run_candidate(hf_window, dx, dy, min_point, settings, simplify, seed, query):
     X, Y = hf_window.shape
-    terrain = terrain_util.SubTerrain("terrain", x_dim=X, y_dim=Y, dx=DX, dy=DX, min_x=0.0, min_y=0.0, device="cpu")
+    terrain = terrain_util.SubTerrain("terrain", x_dim=X, y_dim=Y, dx=dx, dy=dy, min_x=min_point[0], min_y=min_point[1], device="cpu")
     terrain.hf[:, :] = torch.tensor(hf_window)
     start, goal = astar.pick_random_start_end_nodes_on_edges(terrain, min_dist=settings["min_start_end_xy_dist"])
     if simplify:
@@ -113,13 +125,14 @@ def run_candidate(hf_window, settings, simplify, seed, query):
         status = ref.FOUND if out is not False else ref.OVER_MAX_COST
     s, g = tuple(int(v) for v in start), tuple(int(v) for v in goal)
     hf_s = terrain.hf.numpy().astype(np.float32).copy()
-    dxf = float(terrain.dxdy[0].item())
+    dxf, dyf = float(terrain.dxdy[0].item()), float(terrain.dxdy[1].item())
+    origin = terrain.min_point.numpy().astype(np.float32).copy()
     # the restatement: simplification, graph, search, polyline
     mine_hf = ref.simplify(hf_window, s, g) if simplify else hf_window
     assert mine_hf.tobytes() == hf_s.tobytes(), "simplified heightfield differs"
-    gr = ref.build_graph(hf_s, dxf, dxf, (0.0, 0.0), settings)
+    gr = ref.build_graph(hf_s, dxf, dyf, origin, settings)
     assert ref.edge_sets(gr[0], gr[1]) == edges, "edge sets differ"
-    mine = ref.search(hf_s, dxf, dxf, (0.0, 0.0), s, g, settings, seed, query, graph=gr)
+    mine = ref.search(hf_s, dxf, dyf, origin, s, g, settings, seed, query, graph=gr)
     keep = mine["ties"] == 0 and (settings["w_bumpy"] == 0.0 or mine["margin"] > 1e-5)
     rec = dict(hf=hf_window, hf_s=hf_s, start=s, goal=g, edges=edges, status=status, seconds=seconds, pops=mine["pops"], margin=mine["margin"],
                nodes=[], cost=np.float32(np.nan), points=np.zeros((0, 3), np.float32), keep=keep, jump=0)
@@ -138,16 +151,21 @@ def run_candidate(hf_window, settings, simplify, seed, query):
             else:
                 assert abs(float(mine["cost"]) - float(cost)) <= 1e-5
         if status == ref.FOUND:
-            p = ref.polyline(hf_s, dxf, dxf, (0.0, 0.0), rec["nodes"])
+            p = ref.polyline(hf_s, dxf, dyf, origin, rec["nodes"])
             assert p.shape == rec["points"].shape and np.abs(p - rec["points"]).max() <= 2e-6, "polyline differs"
     return rec
 
 
-def select(cands, n, simplify, dim):
-    """n kept candidates: edge-index and long-jump queries first, then found / not found in turn."""
+def on_last(c, shape):
+    """A start / goal index of dim - 1 on its own axis."""
+    return any(cell[a] == shape[a] - 1 for cell in (c["start"], c["goal"]) for a in (0, 1))
+
+
+def select(cands, n, simplify, shape, classes=((ref.FOUND,), (ref.NO_PATH, ref.OVER_MAX_COST))):
+    """n kept candidates: edge-index and long-jump queries first, then the status classes (found / not found) in turn."""
     pool = [c for c in cands if c["keep"]]
     edge0 = [c for c in pool if 0 in c["start"] + c["goal"]]
-    edge1 = [c for c in pool if dim - 1 in c["start"] + c["goal"]]
+    edge1 = [c for c in pool if on_last(c, shape)]
     longj = [c for c in pool if c["status"] == ref.FOUND and c["jump"] >= 3]
     chosen = []
 
@@ -163,12 +181,11 @@ def select(cands, n, simplify, dim):
         take(edge0, min(3, n // 6))
         take(edge1, min(3, n // 6))
     take(longj, min(max(2, n // 5), n // 3))
-    found = [c for c in pool if c["status"] == ref.FOUND]
-    lost = [c for c in pool if c["status"] != ref.FOUND]
+    groups = [[c for c in pool if c["status"] in cls] for cls in classes]
     while len(chosen) < n:
-        nf = sum(c["status"] == ref.FOUND for c in chosen)
+        counts = [sum(c["status"] in cls for c in chosen) for cls in classes]
         before = len(chosen)
-        take(found if nf <= len(chosen) - nf else lost, 1)
+        take(groups[counts.index(min(counts))], 1)          # the class with the fewest so far, the first of equals
         if len(chosen) == before:
             take(pool, 1)
         assert len(chosen) > before, "not enough kept candidates"
@@ -180,28 +197,46 @@ def main():
                 for n in TERRAINS}
     totals = dict(long_jump=0, edge0=0, edge1=0)
     only = sys.argv[1:]
-    for name, dim, settings, simplify, keep_n, draw_n, seed in CASES:
+    for name, shape, dx, dy, min_point, settings, simplify, keep_n, draw_n, seed in CASES:
         if only and name not in only:
             continue
-        random.seed(seed)
-        rng = np.random.RandomState(seed)
-        cands = []
-        for k in range(draw_n):
-            tname = TERRAINS[k % 3]
-            T = terrains[tname]
-            sx = rng.randint(0, T.shape[0] + 1 - dim)
-            sy = rng.randint(0, T.shape[1] + 1 - dim)
-            rec = run_candidate(T[sx:sx + dim, sy:sy + dim].copy(), settings, simplify, seed, k)
-            rec.update(terrain=tname, origin=(sx, sy), query=k)
-            cands.append(rec)
-            print(name, k, tname, "status", rec["status"], "jump", rec["jump"], "pops", rec["pops"], "keep", rec["keep"], f"{rec['seconds']:.2f}s", flush=True)
-        ch = select(cands, keep_n, simplify, dim)
+        X, Y = shape
+        auto_cost = settings["max_cost"] is None
+
+        def draw_all(settings):
+            # the same windows and the same start / goal draws on every pass: both generators restart from the case's seed
+            random.seed(seed)
+            rng = np.random.RandomState(seed)
+            cands = []
+            for k in range(draw_n):
+                tname = TERRAINS[k % 3]
+                T = terrains[tname]
+                sx = rng.randint(0, T.shape[0] + 1 - X)
+                sy = rng.randint(0, T.shape[1] + 1 - Y)
+                rec = run_candidate(T[sx:sx + X, sy:sy + Y].copy(), dx, dy, min_point, settings, simplify, seed, k)
+                rec.update(terrain=tname, origin=(sx, sy), query=k)
+                cands.append(rec)
+                print(name, k, tname, "status", rec["status"], "cost", rec["cost"], "jump", rec["jump"], "pops", rec["pops"], "keep", rec["keep"],
+                      f"{rec['seconds']:.2f}s", flush=True)
+            return cands
+
+        classes = ((ref.FOUND,), (ref.NO_PATH, ref.OVER_MAX_COST))
+        if auto_cost:
+            first = draw_all(dict(settings, max_cost=ref.DEFAULTS["max_cost"]))
+            costs = sorted(float(c["cost"]) for c in first if c["keep"] and c["status"] == ref.FOUND)
+            settings = dict(settings, max_cost=round(costs[len(costs) // 2] - 0.005, 2))     # below the median: it is no path's own cost
+            print(name, "found costs", costs[0], "..", costs[-1], "max_cost", settings["max_cost"], flush=True)
+            classes = ((ref.FOUND,), (ref.OVER_MAX_COST,), (ref.NO_PATH,))
+        cands = draw_all(settings)
+        ch = select(cands, keep_n, simplify, shape, classes)
         nf = sum(c["status"] == ref.FOUND for c in ch)
-        assert 3 * nf >= len(ch) and 3 * (len(ch) - nf) >= len(ch), (name, nf, len(ch))
+        reached = nf + (sum(c["status"] == ref.OVER_MAX_COST for c in ch) if auto_cost else 0)
+        assert 3 * reached >= len(ch) and 3 * (len(ch) - reached) >= len(ch), (name, reached, len(ch))
+        assert not auto_cost or (nf >= 3 and reached - nf >= 3), (name, nf, reached)
         totals["long_jump"] += sum(c["status"] == ref.FOUND and c["jump"] >= 3 for c in ch)
         if simplify:
             totals["edge0"] += sum(0 in c["start"] + c["goal"] for c in ch)
-            totals["edge1"] += sum(dim - 1 in c["start"] + c["goal"] for c in ch)
+            totals["edge1"] += sum(on_last(c, shape) for c in ch)
         edge_off, edge_to, node_off, nodes, point_off, points = [0], [], [0], [], [0], []
         for c in ch:
             for e in c["edges"]:
@@ -213,11 +248,13 @@ def main():
             point_off.append(point_off[-1] + len(c["points"]))
         notes = dict(kept=len(ch), drawn=draw_n, dropped_for_ties_or_margin=sum(not c["keep"] for c in cands), found=nf,
                      min_margin=min(c["margin"] for c in ch), zero_ties=True,
-                     long_jump_paths=int(sum(c["status"] == ref.FOUND and c["jump"] >= 3 for c in ch)))
+                     long_jump_paths=int(sum(c["status"] == ref.FOUND and c["jump"] >= 3 for c in ch)), max_cost=settings["max_cost"])
+        if auto_cost:
+            notes.update(over_max_cost=int(reached - nf), found_costs_first_pass=[costs[0], costs[-1]])
         np.savez_compressed(
             os.path.join(HERE, f"path_planner_{name}.npz"),
-            settings=json.dumps(settings), notes=json.dumps(notes), simplify=np.int32(simplify), seed=np.int64(seed), dx=np.float32(DX),
-            min_point=np.zeros(2, np.float32), terrain=np.array([c["terrain"] for c in ch]), origin=np.array([c["origin"] for c in ch], np.int32),
+            settings=json.dumps(settings), notes=json.dumps(notes), simplify=np.int32(simplify), seed=np.int64(seed), dx=np.float32(dx),
+            dy=np.float32(dy), min_point=np.array(min_point, np.float32), terrain=np.array([c["terrain"] for c in ch]), origin=np.array([c["origin"] for c in ch], np.int32),
             query=np.array([c["query"] for c in ch], np.int64), hf=np.stack([c["hf"] for c in ch]), hf_simplified=np.stack([c["hf_s"] for c in ch]),
             start=np.array([c["start"] for c in ch], np.int32), goal=np.array([c["goal"] for c in ch], np.int32),
             edge_off=np.array(edge_off, np.int64), edge_to=np.array(edge_to, np.int16), status=np.array([c["status"] for c in ch], np.int32),

@@ -12,13 +12,15 @@ import path_planner_ref as ref
 from parc_amd import path_planner as pp
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CASES = ["default_16", "nosimplify_16", "bumpy_16", "classdefaults_16", "default_32"]
+SQUARE_CASES = ["default_16", "nosimplify_16", "bumpy_16", "classdefaults_16", "default_32"]
+CASES = SQUARE_CASES + ["rect_12x20", "aniso_13x17", "aniso_20x11"]
 
 
 def fixture(case):
     z = dict(np.load(os.path.join(REPO, "tests/golden", f"path_planner_{case}.npz")))
     z["settings"] = json.loads(str(z["settings"]))
     z["notes"] = json.loads(str(z["notes"]))
+    z.setdefault("dy", z["dx"])                  # the square fixtures were written before dy was stored
     return z
 
 
@@ -33,15 +35,15 @@ def fixture_edges(z, k):
 def test_restatement_matches_reference(case):
     z = fixture(case)
     s = z["settings"]
-    dx = float(z["dx"])
+    dx, dy = float(z["dx"]), float(z["dy"])
     seed = int(z["seed"])
     for k in range(z["hf"].shape[0]):
         start, goal = tuple(int(v) for v in z["start"][k]), tuple(int(v) for v in z["goal"][k])
         hf = ref.simplify(z["hf"][k], start, goal) if int(z["simplify"]) else z["hf"][k]
         assert hf.tobytes() == z["hf_simplified"][k].tobytes()
-        graph = ref.build_graph(hf, dx, dx, z["min_point"], s)
+        graph = ref.build_graph(hf, dx, dy, z["min_point"], s)
         assert ref.edge_sets(graph[0], graph[1]) == fixture_edges(z, k)
-        r = ref.search(hf, dx, dx, z["min_point"], start, goal, s, seed, int(z["query"][k]), graph=graph)
+        r = ref.search(hf, dx, dy, z["min_point"], start, goal, s, seed, int(z["query"][k]), graph=graph)
         assert r["ties"] == 0 and r["pops"] == z["pops"][k]
         assert r["status"] == z["status"][k]
         want = z["nodes"][z["node_off"][k]:z["node_off"][k + 1]]
@@ -52,17 +54,19 @@ def test_restatement_matches_reference(case):
             else:
                 assert r["margin"] > 1e-5 and abs(float(r["cost"]) - float(z["cost"][k])) <= 1e-5
         if r["status"] == ref.FOUND:
-            pts = ref.polyline(hf, dx, dx, z["min_point"], r["nodes"])
+            pts = ref.polyline(hf, dx, dy, z["min_point"], r["nodes"])
             want_p = z["points"][z["point_off"][k]:z["point_off"][k + 1]]
             assert pts.shape == want_p.shape and np.abs(pts - want_p).max() <= 2e-6
 
 
 def test_fixture_conditions():
-    """What the generator asserted, re-checked on the committed files: found / not found thirds, long jumps, edge-index cells."""
+    """What the generator asserted, re-checked on the committed files: found / not found thirds, long jumps, edge-index cells.  The
+    totals count the square files alone, as before the rectangular ones came; those are checked file by file below."""
     long_jump = edge0 = edge1 = found = total = 0
-    for case in CASES:
+    for case in SQUARE_CASES:
         z = fixture(case)
         dim = z["hf"].shape[1]
+        assert z["hf"].shape[2] == dim and float(z["dy"]) == float(z["dx"]) and not z["min_point"].any()
         ok = z["status"] == ref.FOUND
         found += ok.sum()
         total += len(ok)
@@ -77,6 +81,31 @@ def test_fixture_conditions():
         assert z["notes"]["zero_ties"] and (z["settings"]["w_bumpy"] == 0.0 or z["margin"].min() > 1e-5)
     assert 3 * found >= total and 3 * (total - found) >= total
     assert long_jump >= 5 and edge0 >= 4 and edge1 >= 4
+
+
+@pytest.mark.parametrize("case,shape,dx,dy,min_point,radius", [("rect_12x20", (12, 20), 0.4, 0.4, (1.7, -2.3), 8),
+                                                               ("aniso_13x17", (13, 17), 0.4, 0.5, (1.7, -2.3), 5),
+                                                               ("aniso_20x11", (20, 11), 0.5, 0.4, (-3.1, 0.9), 3)])
+def test_rectangular_fixture_conditions(case, shape, dx, dy, min_point, radius):
+    """The files off the square: 12 queries at the stated grid, spacing, origin and jump radius, a third reached the goal and a third
+    did not, zero ties; rect_12x20's max_cost (chosen from the reference's costs) leaves at least three FOUND and three OVER_MAX_COST."""
+    z = fixture(case)
+    s, notes = z["settings"], z["notes"]
+    assert z["hf"].shape == (12,) + shape and int(z["simplify"]) == 1
+    assert (np.float32(z["dx"]), np.float32(z["dy"])) == (np.float32(dx), np.float32(dy)) and z["min_point"].tobytes() == np.array(min_point, np.float32).tobytes()
+    assert ref.jump_radius(s, float(z["dx"])) == radius
+    assert notes["zero_ties"] and notes["kept"] == 12 and notes["drawn"] >= 12 and "dropped_for_ties_or_margin" in notes and "min_margin" in notes
+    assert notes["max_cost"] == s["max_cost"]
+    found, over = int((z["status"] == ref.FOUND).sum()), int((z["status"] == ref.OVER_MAX_COST).sum())
+    if case == "rect_12x20":
+        assert notes["max_cost"] == s["max_cost"] < 1000.0 and found >= 3 and over >= 3 and (s["uniform_cost_min"], s["uniform_cost_max"]) == (0.1, 0.6)
+        assert 3 * (found + over) >= 12 and 3 * (12 - found - over) >= 12
+        for k in range(12):
+            if len(z["nodes"][z["node_off"][k]:z["node_off"][k + 1]]):
+                assert (z["status"][k] == ref.OVER_MAX_COST) == bool(z["cost"][k] > np.float32(s["max_cost"]))
+                assert (z["point_off"][k + 1] > z["point_off"][k]) == (z["status"][k] == ref.FOUND)
+    else:
+        assert over == 0 and 3 * found >= 12 and 3 * (12 - found) >= 12
 
 
 def test_ring_cells_include_outermost_rows():

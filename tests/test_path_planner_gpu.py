@@ -25,13 +25,13 @@ def planner(settings, simplify, **kw):
 def test_fixture_through_the_c_abi(case):
     z = fixture(case)
     s = z["settings"]
-    dx = float(z["dx"])
-    P = planner(s, bool(int(z["simplify"])))
+    dx, dy = float(z["dx"]), float(z["dy"])
+    P = planner(s, bool(int(z["simplify"])), min_point=tuple(float(v) for v in z["min_point"]))
     R = pp.jump_radius(P.settings, dx)
     Y = z["hf"].shape[2]
     for k in range(z["hf"].shape[0]):
         # a fixture's queries keep the indices the generator drew them under: one query per run, first_query = its index
-        r = P.plan(z["hf"][k:k + 1], z["start"][k:k + 1], z["goal"][k:k + 1], seed=int(z["seed"]), dx=dx, first_query=int(z["query"][k]))
+        r = P.plan(z["hf"][k:k + 1], z["start"][k:k + 1], z["goal"][k:k + 1], seed=int(z["seed"]), dx=dx, dy=dy, first_query=int(z["query"][k]))
         assert r.hf[0].tobytes() == z["hf_simplified"][k].tobytes(), (case, k)
         nbr, cliff, jump = P.graph(0, 1)
         assert pp.edges_from_graph(nbr[0], jump[0], R) == fixture_edges(z, k), (case, k)
