@@ -3,7 +3,8 @@
 
 Run where the reference checkout is available (the GPU tests only read the fixtures it writes):
 
-    python tests/golden/make_golden_motion_opt.py
+    python tests/golden/make_golden_motion_opt.py          # the two per-clip fixtures
+    python tests/golden/make_golden_motion_opt.py terms    # motion_opt_terms.npz, from the committed per-clip fixtures
 
 The reference is driven as in ``make_golden.py`` (a ``parc`` package alias, empty module stubs, our data-only ms-file decoder);
 in addition ``wandb.run`` is ``None`` and ``trimesh.creation.icosphere`` is the normalised icosahedron (subdivision 0 only), the
@@ -16,6 +17,10 @@ Per case (clip, frame stride):
   * loss terms and autograd gradients of ``motion_terrain_contact_loss_localized`` at state a (target = source), b (perturbed)
     and c (20 reference Adam steps from b), plus state b with ``w_contact = 0``, ``w_sliding = 0`` and no constraints;
   * the loss dict at each of the 20 steps, and (stride-1 case) after 300 steps.
+
+Mode ``terms`` writes ``motion_opt_terms.npz``: for both cases, at state b, the loss dict and the autograd gradient with each of the
+nine weights on alone at its stage-2 value (``terms_<clip>`` [9 one-hot runs, 9 terms], ``grad_<clip>`` [9, F, 6 + D]).  Sources, contacts,
+terrain, constraints and state b are read back from the committed per-clip fixtures, so both records speak of exactly the same state.
 """
 import os
 import sys
@@ -189,5 +194,55 @@ def main():
         print("wrote", path, os.path.getsize(path), "bytes; terms b:", out["terms_b"])
 
 
+def main_terms():
+    char = kcm.KinCharModel("cpu")
+    char.load_char_file(os.path.join(REPO, "data/assets/humanoid.xml"))
+    pts2, flat2, _ = ref_points(char, STAGE2)
+    out = {}
+    for clip, stride, _ in CASES:
+        z = np.load(os.path.join(HERE, f"motion_opt_{clip}_s{stride}.npz"))
+        assert np.array_equal(flat2, z["pts_stage2"])
+        assert np.array_equal(z["weights"], np.array([WEIGHTS[k] for k in mo.WEIGHT_KEYS], np.float32))
+        hf = torch.tensor(z["hf"])
+        terrain = terrain_util.SubTerrain(x_dim=hf.shape[0], y_dim=hf.shape[1], dx=float(z["dx"]), dy=float(z["dx"]),
+                                          min_x=float(z["min_point"][0]), min_y=float(z["min_point"][1]), device="cpu")
+        terrain.hf = hf
+        rp, rq, jr, ct = [torch.tensor(z[k]) for k in ("root_pos", "root_rot", "joint_rot", "contacts")]
+        src_body_pos, src_body_rot = char.forward_kinematics(rp, rq, jr)
+        src = dict(src_root_pos=rp, src_root_rot_quat=rq, src_joint_rot=jr, contacts=ct,
+                   src_body_vels=src_body_pos[1:] - src_body_pos[:-1],
+                   src_body_rot_vels=tu.quat_diff_angle(src_body_rot[1:], src_body_rot[:-1]))
+        cons = [[] for _ in range(char.get_num_joints())]
+        for b, s, e, p in zip(z["cons_body"], z["cons_start"], z["cons_end"], z["cons_point"]):
+            c = moopt.BodyConstraint()
+            c.start_frame_idx, c.end_frame_idx, c.constraint_point = int(s), int(e), torch.tensor(p)
+            cons[int(b)].append(c)
+        state_b = tuple(torch.tensor(z[f"state_b_{k}"]) for k in ("root_pos", "root_rot", "dof"))
+        # the rebuilt inputs reproduce the committed record of the weighted total before anything new is written
+        terms, _, grads = loss_and_grad(state_b, src, terrain, pts2, char, cons, **WEIGHTS)
+        # (to float32 summation order, which differs between hosts and thread counts)
+        g_all, g_ref = np.concatenate(grads, 1), np.concatenate([z[f"grad_b_{k}"] for k in ("root_pos", "root_rot", "dof")], 1)
+        print(clip, "rebuilt vs committed, all weights on: terms rel", np.abs(terms / z["terms_b"] - 1).max(),
+              "grad", np.abs(g_all - g_ref).max() / np.abs(g_ref).max(), "of max")
+        assert np.allclose(terms, z["terms_b"], rtol=1e-6, atol=0) and np.abs(g_all - g_ref).max() <= 1e-6 * np.abs(g_ref).max()
+        all_terms, all_grads = [], []
+        for key in mo.WEIGHT_KEYS:
+            w = {k: (WEIGHTS[k] if k == key else 0.0) for k in mo.WEIGHT_KEYS}
+            terms, _, grads = loss_and_grad(state_b, src, terrain, pts2, char, cons, **w)
+            all_terms.append(terms)
+            all_grads.append(np.concatenate(grads, axis=1).astype(np.float32))
+        out[f"terms_{clip}"] = np.array(all_terms, np.float64)
+        out[f"grad_{clip}"] = np.array(all_grads, np.float32)
+        print(clip, "largest gradient entry per term:", [float(np.abs(g).max()) for g in all_grads])
+    path = os.path.join(HERE, "motion_opt_terms.npz")
+    np.savez_compressed(path, **out)
+    print("wrote", path, os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["terms"]:
+        main_terms()
+    elif sys.argv[1:]:
+        sys.exit("usage: make_golden_motion_opt.py [terms]")
+    else:
+        main()

@@ -4,6 +4,9 @@
 Written from the semantics table of DESIGN.md section 8d, not from the reference's code: textbook quaternion algebra, autograd for the
 gradient.  ``tests/test_motion_opt_cpu.py`` checks it against the reference fixtures; it is the CPU-side statement of what the HIP kernels
 (``parc_motion_opt.hpp``) compute, and a second derivation of the gradients they produce analytically.
+
+Everything is computed in the dtype of ``params`` (``Character`` and ``as_tensors`` take it as an argument; the other inputs are given in
+it): float32 as the reference computes, float64 as the yardstick of ``tests/test_motion_opt_terms_*.py``.
 """
 import numpy as np
 import torch
@@ -54,28 +57,29 @@ def exp_map_to_quat(e):
 
 
 def hinge_quat(axis, d):
+    axis = axis.to(d.dtype)
     half = 0.5 * d.unsqueeze(-1)
     return torch.cat([axis / axis.norm() * torch.sin(half), torch.cos(half)], -1)
 
 
 class Character:
-    def __init__(self, cm):
+    def __init__(self, cm, dtype=torch.float32):
         self.cm = cm
         self.B = cm.get_num_bodies()
         self.parent = [int(p) for p in cm._parent_indices]
-        self.lt = torch.tensor(cm._local_translation, dtype=torch.float32)
-        self.lr = torch.tensor(cm._local_rotation, dtype=torch.float32)
+        self.lt = torch.tensor(cm._local_translation, dtype=dtype)
+        self.lr = torch.tensor(cm._local_rotation, dtype=dtype)
 
     def dof_to_rot(self, dof):
         out = []
         for j in range(1, self.B):
             jt = self.cm._joints[j]
             if jt.joint_type == JointType.HINGE:
-                out.append(hinge_quat(torch.tensor(jt.axis, dtype=torch.float32), dof[..., jt.dof_idx]))
+                out.append(hinge_quat(torch.tensor(jt.axis, dtype=dof.dtype), dof[..., jt.dof_idx]))
             elif jt.joint_type == JointType.SPHERICAL:
                 out.append(exp_map_to_quat(dof[..., jt.dof_idx:jt.dof_idx + 3]))
             else:
-                out.append(torch.tensor([0.0, 0.0, 0.0, 1.0]).expand(dof.shape[:-1] + (4,)))
+                out.append(torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=dof.dtype).expand(dof.shape[:-1] + (4,)))
         return torch.stack(out, -2)
 
     def fk(self, root_pos, root_rot, joint_rot):
@@ -95,8 +99,8 @@ def box_sdf(p, h):
 def column_sdf(x, hf, x0, y0, min_point, dx, bottom, top):
     """Min over the cells [x0, x0+sx) x [y0, y0+sy) of the box SDF of the columns [bottom, hf] (top is None) or [hf, top]."""
     sx, sy = hf.shape
-    i = torch.arange(sx, dtype=torch.float32)
-    j = torch.arange(sy, dtype=torch.float32)
+    i = torch.arange(sx, dtype=x.dtype)
+    j = torch.arange(sy, dtype=x.dtype)
     cx = (min_point[0] + x0 * dx) + i * dx
     cy = (min_point[1] + y0 * dx) + j * dx
     lo, hi = (torch.full_like(hf, bottom), hf) if top is None else (hf, torch.full_like(hf, top))
@@ -139,7 +143,7 @@ def loss_terms(ch, params, src, pts, pt_body, contacts, contact_id, hf, min_poin
         ground.append(column_sdf(x[f], sub, start[f, 0], start[f, 1], min_point, dx, -10.0, None))
     air, ground = torch.stack(air), torch.stack(ground)
     t[4] = air.clamp(min=0.0).sum()
-    zero = torch.zeros((), dtype=torch.float32)
+    zero = torch.zeros((), dtype=params.dtype)
     t[5] = zero
     if w[5] != 0.0:
         g = ground.clamp(min=0.0)
@@ -148,15 +152,15 @@ def loss_terms(ch, params, src, pts, pt_body, contacts, contact_id, hf, min_poin
                 t[5] = t[5] + (g[:, pt_body == b].min(dim=1).values * contacts[:, contact_id[b]]).sum()
     # body constraints: hands (sphere geom) |dist to centre - r|, feet (box) the first 18 points, clamp(dist - 1.25 |half|, 0)
     t[7] = zero
-    keep = torch.ones(F - 1, B)
+    keep = torch.ones(F - 1, B, dtype=params.dtype)
     for b, s, e, cp in cons:
         g = ch.cm._geoms[b][0]
         fr = slice(s, e + 1)
         if g.shape == GeomType.SPHERE:
-            ctr = qrot(rot[fr, b], torch.tensor(g.pos, dtype=torch.float32)) + pos[fr, b]
+            ctr = qrot(rot[fr, b], torch.tensor(g.pos, dtype=params.dtype)) + pos[fr, b]
             t[7] = t[7] + (torch.linalg.vector_norm(cp - ctr, dim=-1) - float(g.size[0])).abs().sum()
         elif g.shape == GeomType.BOX:
-            r = torch.linalg.vector_norm(torch.tensor(g.size, dtype=torch.float32)) * 1.25
+            r = torch.linalg.vector_norm(torch.tensor(g.size, dtype=params.dtype)) * 1.25
             sole = x[fr][:, pt_body == b][:, :18].reshape(-1, 3)
             t[7] = t[7] + (torch.linalg.vector_norm(cp - sole, dim=-1) - r).clamp(min=0.0).sum()
         else:
@@ -186,5 +190,5 @@ def refine_constraint_point(p, hf, min_point, dx, steps=1000, lr=0.01):
     return p.detach()
 
 
-def as_tensors(z):
-    return {k: torch.tensor(np.asarray(z[k])) for k in ("root_pos", "root_rot", "joint_rot")}
+def as_tensors(z, dtype=None):
+    return {k: torch.tensor(np.asarray(z[k]), dtype=dtype) for k in ("root_pos", "root_rot", "joint_rot")}
