@@ -937,6 +937,87 @@ int parc_mdm_kernel_times(ParcMdm *h, float *ms3);
 /* VGPRs are the compiler's; this is what the handle chose: dynamic LDS bytes of k_mdm_forward, its grid (resident slots), scratch floats per slot. */
 int parc_mdm_describe(ParcMdm *h, int64_t *out3);
 
+/* ---- path-following motion generation: the generator's world-frame wrapper and the rollout along a path (parc_mpath_*) --
+ * gen_util.gen_mdm_motion (RELATIVE_TO_ROOT) and mdm_path.generate_frames_until_end_of_path for N rows at once, each row on the terrain
+ * and the path that row_path names.  A window is k_mpath_cond, parc_mdm_sample as it is, k_mpath_append; the host reads one int per
+ * window (the rows not done).  A frame of the world-frame buffers is FD = 7 + 4 (B - 1) + B floats: root position 3, root rotation 4
+ * (x, y, z, w), joint rotations (B - 1) x 4, contacts B.  x_T of window w of a row is the generator's draw of
+ * (seed, sample index row_id * 4096 + w, step 0): it depends on the row's id, never on its place in the batch. */
+#define PARC_MPATH_HEADING_AUTO 0                /* the first heading: atan2 of node 1 - node 0 */
+#define PARC_MPATH_HEADING_RANDOM 1              /* uniform in [0, 2 pi), one per path */
+typedef struct ParcMdmPath ParcMdmPath;
+typedef struct {
+    uint32_t struct_size;                    /* sizeof(ParcMdmPathParams) */
+    ParcMdm *mdm;                            /* the generator the rollout drives; it must outlive this handle */
+    float grid_dx, grid_dy;                  /* heightmap.horizontal_scale */
+    int32_t num_x_neg, num_x_pos, num_y_neg, num_y_pos;   /* heightmap.local_grid: 31 x 31 points */
+    float max_h;                             /* heightmap.max_h */
+    float sequence_fps;
+    int32_t left_foot, right_foot;           /* body ids of the done test */
+    /* MDMPathSettings */
+    int32_t next_node_lookahead, rewind_num_frames;
+    float max_motion_length;
+    /* MDMGenSettings */
+    int32_t use_prev_state, use_cfg;
+    float cfg_scale;
+    int32_t prev_state_ind_key, target_condition_key, use_ddim, ddim_stride;
+} ParcMdmPathParams;
+typedef struct {                             /* device arrays that parc_mpath_conds fills, n = the scene's rows */
+    float *hf;                               /* [n][31][31], minus the canonical z, clamped to +-max_h and divided by it */
+    float *target;                           /* [n][2] */
+    float *prev_state;                       /* [n][num_prev_states][frame_dim], standardised */
+    int32_t *obs_flag, *target_flag, *prev_state_flag, *noise_ind, *done, *closest_node, *target_node;   /* [n] */
+    float *canon;                            /* [n][8]: canonical xy, z, heading, heading quaternion */
+} ParcMdmPathCondOut;
+typedef struct {
+    int32_t n;
+    const float *x;                          /* [n][seq_len][frame_dim]: the sampler's result, standardised */
+    const float *prev_state;                 /* [n][num_prev_states][frame_dim]: the clean previous state, standardised */
+    const int32_t *noise_ind;                /* [n] */
+    const float *canon;                      /* [n][8] */
+    int32_t guided;                          /* the window ran under guidance: the indicator counts as false (gen_sequence) */
+    int32_t lo, hi, offset;                  /* frames [lo, hi) of the window go to frames[row][offset ..] */
+    float *frames;                           /* [n][max_frames][FD] */
+    int32_t max_frames;
+    float *prev_next;                        /* [n][num_prev_states][FD] or NULL: frames [start_frame - num_prev_states, start_frame) */
+    const int32_t *done;                     /* with final_frame, or both NULL: final_frame[row] = total where done and still -1 */
+    int32_t *final_frame;
+    int32_t total;
+} ParcMdmPathAppendArgs;
+typedef struct {
+    const float *prev_frames;                /* device [n][num_prev_states][FD], or NULL: blank frames, the last at node 0 */
+    const float *rel_height_host;            /* [P] relative root height of the start, or NULL: drawn in [0.7, 0.9) from seed */
+    const float *heading_host;               /* [P] first heading, or NULL: heading_mode */
+    int32_t heading_mode;                    /* PARC_MPATH_HEADING_* */
+    const float *noise;                      /* device [noise_windows][n][seq_len][frame_dim]: x_T of every window, or NULL: drawn */
+    int32_t noise_windows;
+    uint64_t seed;
+    const int64_t *row_ids_host;             /* [n] global row ids, 0 .. 2^28 - 1, or NULL: 0 .. n - 1 */
+    const int64_t *path_ids_host;            /* [P] global path ids, 0 .. 2^40 - 1, or NULL: 0 .. P - 1: the key of the drawn start */
+    float *frames;                           /* out, device [n][max_frames][FD] (max_frames: parc_mpath_describe) */
+    int32_t *final_frame;                    /* out, device [n]: frames at the first window that saw the row done, -1 if none */
+    int32_t *done;                           /* out, device [n]: the done flags of the last window */
+} ParcMdmPathRolloutArgs;
+int parc_mpath_create(const ParcMdmPathParams *p, ParcMdmPath **out);
+void parc_mpath_destroy(ParcMdmPath *h);
+/* Host arrays, copied: terrains hf [P][X][Y] with min_points [P][2] and common dx / dy, paths [P][max_nodes][3] with counts [P] (a path
+ * has 2 .. max_nodes finite nodes; path p lies on terrain p), row_path [num_rows] (num_rows <= the generator's max_batch). */
+int parc_mpath_set_scene(ParcMdmPath *h, const float *hf_host, int32_t num_terrains, int32_t dim_x, int32_t dim_y, const float *min_points_host, float dx,
+                         float dy, const float *paths_host, const int32_t *path_counts_host, int32_t max_nodes, const int32_t *row_path_host,
+                         int32_t num_rows);
+/* k_mpath_cond on its own: prev_frames device [n][num_prev_states][FD].  first != 0: the target is node 1 (the path's start);
+ * blank != 0: the indicator is off (a start from blank frames); else it is on for first != 0 (given frames at the path's start, as the
+ * rollout's first window) and use_prev_state otherwise.  No host sync. */
+int parc_mpath_conds(ParcMdmPath *h, const float *prev_frames, int32_t first, int32_t blank, const ParcMdmPathCondOut *o, void *stream);
+/* k_mpath_append on its own.  No host sync. */
+int parc_mpath_append(ParcMdmPath *h, const ParcMdmPathAppendArgs *a, void *stream);
+/* The whole rollout: windows x (3 + 2 steps) launches, one more for blank previous frames; one 4-byte read-back per window after the first. */
+int parc_mpath_rollout(ParcMdmPath *h, const ParcMdmPathRolloutArgs *a, void *stream);
+/* Device ms of the last rollout's k_mpath_cond and k_mpath_append launches (summed; waits for the last event). */
+int parc_mpath_kernel_times(ParcMdmPath *h, float *ms2);
+/* max_frames, max_windows, FD; then of the last rollout: windows, kernel launches, frames per row. */
+int parc_mpath_describe(ParcMdmPath *h, int64_t *out6);
+
 #ifdef __cplusplus
 }
 #endif

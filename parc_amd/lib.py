@@ -264,6 +264,35 @@ class ParcMdmSampleArgs(C.Structure):
                 ("first_index", C.c_uint64), ("keep", C.c_void_p)]
 
 
+MPATH_HEADING_AUTO, MPATH_HEADING_RANDOM = 0, 1   # PARC_MPATH_HEADING_*
+
+
+class ParcMdmPathParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mdm", C.c_void_p), ("grid_dx", C.c_float), ("grid_dy", C.c_float),
+                ("num_x_neg", C.c_int32), ("num_x_pos", C.c_int32), ("num_y_neg", C.c_int32), ("num_y_pos", C.c_int32),
+                ("max_h", C.c_float), ("sequence_fps", C.c_float), ("left_foot", C.c_int32), ("right_foot", C.c_int32),
+                ("next_node_lookahead", C.c_int32), ("rewind_num_frames", C.c_int32), ("max_motion_length", C.c_float),
+                ("use_prev_state", C.c_int32), ("use_cfg", C.c_int32), ("cfg_scale", C.c_float), ("prev_state_ind_key", C.c_int32),
+                ("target_condition_key", C.c_int32), ("use_ddim", C.c_int32), ("ddim_stride", C.c_int32)]
+
+
+class ParcMdmPathCondOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("hf", "target", "prev_state", "obs_flag", "target_flag", "prev_state_flag", "noise_ind", "done",
+                                          "closest_node", "target_node", "canon")]
+
+
+class ParcMdmPathAppendArgs(C.Structure):
+    _fields_ = [("n", C.c_int32), ("x", C.c_void_p), ("prev_state", C.c_void_p), ("noise_ind", C.c_void_p), ("canon", C.c_void_p),
+                ("guided", C.c_int32), ("lo", C.c_int32), ("hi", C.c_int32), ("offset", C.c_int32), ("frames", C.c_void_p),
+                ("max_frames", C.c_int32), ("prev_next", C.c_void_p), ("done", C.c_void_p), ("final_frame", C.c_void_p), ("total", C.c_int32)]
+
+
+class ParcMdmPathRolloutArgs(C.Structure):
+    _fields_ = [("prev_frames", C.c_void_p), ("rel_height_host", f32p), ("heading_host", f32p), ("heading_mode", C.c_int32),
+                ("noise", C.c_void_p), ("noise_windows", C.c_int32), ("seed", C.c_uint64), ("row_ids_host", i64p), ("path_ids_host", i64p), ("frames", C.c_void_p),
+                ("final_frame", C.c_void_p), ("done", C.c_void_p)]
+
+
 class ParcEnvBuffers(C.Structure):
     _fields_ = [(n, {"f": f32p, "i": i32p, "l": i64p}[t]) for n, t in BUFFER_FIELDS]
 
@@ -401,6 +430,15 @@ def _signatures():
         "parc_mdm_draw_noise": (rc, [vp, i32, u64, u64, u32, vp, vp]),
         "parc_mdm_kernel_times": (rc, [vp, f32p]),
         "parc_mdm_describe": (rc, [vp, i64p]),
+        # path-following motion generation
+        "parc_mpath_create": (rc, [P(ParcMdmPathParams), P(vp)]),
+        "parc_mpath_destroy": (None, [vp]),
+        "parc_mpath_set_scene": (rc, [vp, f32p, i32, i32, i32, f32p, f32, f32, f32p, i32p, i32, i32p, i32]),
+        "parc_mpath_conds": (rc, [vp, vp, i32, i32, P(ParcMdmPathCondOut), vp]),
+        "parc_mpath_append": (rc, [vp, P(ParcMdmPathAppendArgs), vp]),
+        "parc_mpath_rollout": (rc, [vp, P(ParcMdmPathRolloutArgs), vp]),
+        "parc_mpath_kernel_times": (rc, [vp, f32p]),
+        "parc_mpath_describe": (rc, [vp, i64p]),
     }
 
 
