@@ -3,7 +3,8 @@
 
 Run where the reference checkout is available (the tests only read the fixtures it writes):
 
-    python tests/golden/make_golden_motion_sampler.py
+    python tests/golden/make_golden_motion_sampler.py           # motion_sampler_{root_boxes,floor_boxes,noise,none,stats}.npz
+    python tests/golden/make_golden_motion_sampler.py shapes    # motion_sampler_{rect_root,rect_floor,rect_noise,wrap_root,wrap_floor}.npz
 
 The reference's ``MDMHeightfieldContactMotionSampler`` is driven as ``make_golden_motion_terrain.py`` drives ``terrain_util`` (a ``parc``
 package alias, empty module stubs, our data-only ms-file decoder) on a two-clip library, ``civilization`` and
@@ -18,6 +19,12 @@ cells fp32 rounding may move -- (a) the patch point's terrain cell coordinate li
 cell's rotated index coordinate lies within 1e-4 cells of an edge of one of the sample's boxes.  At most 1 % of a case's cells may be
 skipped (asserted).  ``motion_sampler_stats.npz`` holds ``get_motion_sequences_for_id`` of the shorter clip (every ninth window) and the feature statistics
 of the library in ``MDM._compute_stats``' arithmetic (mdm.py:467-495).
+
+Mode ``shapes`` leaves those files alone and records, with the same recorder, skip cells and keys (plus ``loop_modes``), the cases off
+the 31 x 31, 15-frame CLAMP configuration (``SHAPE_CASES``): a 7 x 32 patch with T = 20 at 20 fps (the clips have 30), ref frame 4
+and 7 boxes; a 32 x 5 patch in ``RELATIVE_TO_ROOT_FLOOR`` with ``FLOOR_HEIGHTS``; a 9 x 11 NOISE patch (99 cells, no multiple of 4);
+and the first two on ``WRAP`` copies of the clips (written to a temporary directory, ``loop_mode`` alone changed) with windows that
+start a few frames and one frame before the clip's end and targets past it (asserted from the recorded plan).
 """
 import json
 import os
@@ -212,7 +219,8 @@ def skip_cells(s, ids, canon_pos, canon_rot, plan, terrains):
     return skip
 
 
-def main():
+def setup():
+    """(recorder, directory for temporary files, library YAML of the two clips, their (hf_mask_inds, hf_maxmin))."""
     rec = Recorder()
     import parc.anim.kin_char_model as kcm
     char = kcm.KinCharModel("cpu")
@@ -238,88 +246,106 @@ def main():
         z = np.load(os.path.join(HERE, f"motion_terrain_{c}.npz"))
         assert np.array_equal(torch.cat(inds).numpy().astype(np.int32), z["mask_inds"]) and np.array_equal(ret.hf_maxmin.numpy(), z["hf_maxmin"])
         extra.append((inds, ret.hf_maxmin))
+    return rec, tmp, lib_yaml, extra
 
+
+def clamp_starts(rng, ids, lengths, duration):
+    """Start times of a CLAMP library: uniform over [0, length - sequence_duration], the first and the last possible one of each clip."""
+    t0 = (rng.rand(NUM_SAMPLES).astype(np.float32) * (lengths[ids] - np.float32(duration))).astype(np.float32)
+    t0[0] = t0[2] = 0.0                                                                  # the first possible start time of each clip
+    t0[1], t0[3] = lengths[0] - np.float32(duration), lengths[1] - np.float32(duration)  # and the last (length - sequence_duration)
+    return t0
+
+
+def record_case(rec, case, cfg, lib_yaml, extra, starts=clamp_starts, extra_out=None, check=None):
+    """One fixture file: the reference's sample_motion_data on 12 (clip, start time) pairs, every draw recorded."""
+    rec.events = None
+    s = build_sampler(cfg, lib_yaml, extra)
+    mlib = s._mlib
+    gx, gy, T = s._grid_dim_x, s._grid_dim_y, s._seq_len
+    rng = np.random.RandomState(1234)
+    ids = np.array([0, 0, 1, 1] + list(rng.randint(0, 2, NUM_SAMPLES - 4)), np.int64)
+    lengths = mlib._motion_lengths.numpy()
+    t0 = starts(rng, ids, lengths, cfg["sequence_duration"])
+    ids_t, t0_t = torch.tensor(ids), torch.tensor(t0)
+    per_sample, captured = [], {}
+    orig_box, orig_noise = s._box_hf_augmentation, s._noise_hf_augmentation
+    orig_future, orig_helper = s._sample_motion_future_times, s.get_hfs_from_data_helper
+
+    def box(hf, mm):
+        rec.events = []
+        orig_box(hf, mm)
+        per_sample.append(rec.events)
+        rec.events = None
+
+    def noise(hf, mm):
+        rec.events = []
+        orig_noise(hf, mm)
+        per_sample.append(rec.events)
+        rec.events = None
+
+    def future(*a, **k):
+        captured["t_future"] = orig_future(*a, **k).clone()
+        return captured["t_future"]
+
+    def helper(*a, **k):
+        hfs, mms = orig_helper(*a, **k)
+        captured["bounds_raw"] = torch.stack(mms).clone()
+        captured["hf_raw"] = torch.stack(hfs).clone()
+        return hfs, mms
+
+    s._box_hf_augmentation, s._noise_hf_augmentation = box, noise
+    s._sample_motion_future_times, s.get_hfs_from_data_helper = future, helper
+    random.seed(7)
+    torch.manual_seed(7)
+    rec.randn = []
+    motion, hfs, target = s.sample_motion_data(motion_ids=ids_t, motion_start_times=t0_t)
+    assert len(rec.randn) == 1
+    plan = dict(motion_id=ids.astype(np.int32), t0=t0, t_future=captured["t_future"].numpy(),
+                future_pos_noise=(s._future_pos_noise_scale * rec.randn[0]).numpy(),
+                change_height=np.zeros(NUM_SAMPLES, np.int32), height_value=np.zeros(NUM_SAMPLES, np.float32),
+                pool_kind=np.zeros((NUM_SAMPLES, 3), np.int32), pool_size=np.zeros((NUM_SAMPLES, 3), np.int32),
+                num_boxes=np.zeros(NUM_SAMPLES, np.int32), boxes=np.zeros((NUM_SAMPLES, s._max_num_boxes, 6), np.float32))
+    mode = cfg["hf_augmentation_mode"]
+    if mode == "MAXPOOL_AND_BOXES":
+        for i, ev in enumerate(per_sample):
+            for k, v in plan_from_events(s, ev, NUM_SAMPLES, gx, gy).items():
+                plan[k][i] = v
+    elif mode == "NOISE":
+        plan["noise"] = np.stack([(ev[0][1] * (s._max_h - s._min_h) + s._min_h).numpy() for ev in per_sample])
+    # the canonicalisation inputs, for the skip cells
+    times = (t0_t.unsqueeze(-1) + s._motion_times)[:, s._ref_frame_idx]
+    cp, cr = s._extract_root_pos_and_rot(ids_t, times)
+    skip = skip_cells(s, ids, cp, cr, plan, mlib._terrains)
+    share = skip.mean()
+    assert share <= MAX_SKIP_SHARE, (case, share)
+    out = dict(config=np.array(json.dumps({k: v for k, v in cfg.items() if k not in ("device", "char_file")})), clips=np.array(CLIPS),
+               skip=skip, bounds_raw=captured["bounds_raw"].numpy(), hf_raw=captured["hf_raw"].numpy(),
+               root_pos=motion[MDMFrameType.ROOT_POS].numpy(), root_rot=motion[MDMFrameType.ROOT_ROT].numpy(),
+               joint_pos=motion[MDMFrameType.JOINT_POS].numpy(), joint_rot=motion[MDMFrameType.JOINT_ROT].numpy(),
+               contacts=motion[MDMFrameType.CONTACTS].numpy(), hfs=hfs.numpy(), target_pos=target.future_pos.numpy(),
+               target_rot=target.future_rot.numpy())
+    if MDMFrameType.FLOOR_HEIGHTS in motion:   # the reference stacks hf i under EVERY sample's roots: [n, n, T, 1]; the diagonal is sample i's own
+        fh = motion[MDMFrameType.FLOOR_HEIGHTS].numpy()
+        out["floor_heights"] = np.stack([fh[i, i, :, 0] for i in range(NUM_SAMPLES)])
+    out.update({"plan_" + k: v for k, v in plan.items()})
+    if extra_out:
+        out.update(extra_out)
+    if check:
+        check(s, plan, out)
+    path = os.path.join(HERE, f"motion_sampler_{case}.npz")
+    np.savez_compressed(path, **{k: (v.astype(np.float32) if isinstance(v, np.ndarray) and v.dtype == np.float64 else v) for k, v in out.items()})
+    print("wrote", path, os.path.getsize(path), "bytes; skipped share %.5f" % share, "pools", plan["pool_kind"].tolist(), "boxes",
+          plan["num_boxes"].tolist(), "height", plan["change_height"].tolist())
+    assert os.path.getsize(path) <= 235 * 1024
+
+
+def main():
+    rec, tmp, lib_yaml, extra = setup()
     for case, over in CASES:
         cfg = dict(BASE_CFG)
         cfg.update(over)
-        rec.events = None
-        s = build_sampler(cfg, lib_yaml, extra)
-        mlib = s._mlib
-        gx, gy, T = s._grid_dim_x, s._grid_dim_y, s._seq_len
-        rng = np.random.RandomState(1234)
-        ids = np.array([0, 0, 1, 1] + list(rng.randint(0, 2, NUM_SAMPLES - 4)), np.int64)
-        lengths = mlib._motion_lengths.numpy()
-        t0 = (rng.rand(NUM_SAMPLES).astype(np.float32) * (lengths[ids] - np.float32(cfg["sequence_duration"]))).astype(np.float32)
-        t0[0] = t0[2] = 0.0                                                        # the first possible start time of each clip
-        t0[1], t0[3] = lengths[0] - np.float32(0.5), lengths[1] - np.float32(0.5)  # and the last (length - sequence_duration)
-        ids_t, t0_t = torch.tensor(ids), torch.tensor(t0)
-
-        per_sample, captured = [], {}
-        orig_box, orig_noise = s._box_hf_augmentation, s._noise_hf_augmentation
-        orig_future, orig_helper = s._sample_motion_future_times, s.get_hfs_from_data_helper
-
-        def box(hf, mm):
-            rec.events = []
-            orig_box(hf, mm)
-            per_sample.append(rec.events)
-            rec.events = None
-
-        def noise(hf, mm):
-            rec.events = []
-            orig_noise(hf, mm)
-            per_sample.append(rec.events)
-            rec.events = None
-
-        def future(*a, **k):
-            captured["t_future"] = orig_future(*a, **k).clone()
-            return captured["t_future"]
-
-        def helper(*a, **k):
-            hfs, mms = orig_helper(*a, **k)
-            captured["bounds_raw"] = torch.stack(mms).clone()
-            captured["hf_raw"] = torch.stack(hfs).clone()
-            return hfs, mms
-
-        s._box_hf_augmentation, s._noise_hf_augmentation = box, noise
-        s._sample_motion_future_times, s.get_hfs_from_data_helper = future, helper
-        random.seed(7)
-        torch.manual_seed(7)
-        rec.randn = []
-        motion, hfs, target = s.sample_motion_data(motion_ids=ids_t, motion_start_times=t0_t)
-        assert len(rec.randn) == 1
-        plan = dict(motion_id=ids.astype(np.int32), t0=t0, t_future=captured["t_future"].numpy(),
-                    future_pos_noise=(s._future_pos_noise_scale * rec.randn[0]).numpy(),
-                    change_height=np.zeros(NUM_SAMPLES, np.int32), height_value=np.zeros(NUM_SAMPLES, np.float32),
-                    pool_kind=np.zeros((NUM_SAMPLES, 3), np.int32), pool_size=np.zeros((NUM_SAMPLES, 3), np.int32),
-                    num_boxes=np.zeros(NUM_SAMPLES, np.int32), boxes=np.zeros((NUM_SAMPLES, s._max_num_boxes, 6), np.float32))
-        mode = cfg["hf_augmentation_mode"]
-        if mode == "MAXPOOL_AND_BOXES":
-            for i, ev in enumerate(per_sample):
-                for k, v in plan_from_events(s, ev, NUM_SAMPLES, gx, gy).items():
-                    plan[k][i] = v
-        elif mode == "NOISE":
-            plan["noise"] = np.stack([(ev[0][1] * (s._max_h - s._min_h) + s._min_h).numpy() for ev in per_sample])
-        # the canonicalisation inputs, for the skip cells
-        times = (t0_t.unsqueeze(-1) + s._motion_times)[:, s._ref_frame_idx]
-        cp, cr = s._extract_root_pos_and_rot(ids_t, times)
-        skip = skip_cells(s, ids, cp, cr, plan, mlib._terrains)
-        share = skip.mean()
-        assert share <= MAX_SKIP_SHARE, (case, share)
-        out = dict(config=np.array(json.dumps({k: v for k, v in cfg.items() if k not in ("device", "char_file")})), clips=np.array(CLIPS),
-                   skip=skip, bounds_raw=captured["bounds_raw"].numpy(), hf_raw=captured["hf_raw"].numpy(),
-                   root_pos=motion[MDMFrameType.ROOT_POS].numpy(), root_rot=motion[MDMFrameType.ROOT_ROT].numpy(),
-                   joint_pos=motion[MDMFrameType.JOINT_POS].numpy(), joint_rot=motion[MDMFrameType.JOINT_ROT].numpy(),
-                   contacts=motion[MDMFrameType.CONTACTS].numpy(), hfs=hfs.numpy(), target_pos=target.future_pos.numpy(),
-                   target_rot=target.future_rot.numpy())
-        if MDMFrameType.FLOOR_HEIGHTS in motion:   # the reference stacks hf i under EVERY sample's roots: [n, n, T, 1]; the diagonal is sample i's own
-            fh = motion[MDMFrameType.FLOOR_HEIGHTS].numpy()
-            out["floor_heights"] = np.stack([fh[i, i, :, 0] for i in range(NUM_SAMPLES)])
-        out.update({"plan_" + k: v for k, v in plan.items()})
-        path = os.path.join(HERE, f"motion_sampler_{case}.npz")
-        np.savez_compressed(path, **{k: (v.astype(np.float32) if isinstance(v, np.ndarray) and v.dtype == np.float64 else v) for k, v in out.items()})
-        print("wrote", path, os.path.getsize(path), "bytes; skipped share %.5f" % share, "pools", plan["pool_kind"].tolist(), "boxes",
-              plan["num_boxes"].tolist(), "height", plan["change_height"].tolist())
-        assert os.path.getsize(path) <= 235 * 1024
+        record_case(rec, case, cfg, lib_yaml, extra)
 
     # get_motion_sequences_for_id of the shorter clip and the feature statistics (mdm.py:467-495, rot_type DEFAULT = quaternions)
     rec.events = None
@@ -371,5 +397,71 @@ def main():
     assert os.path.getsize(path) <= 235 * 1024
 
 
+# ---- mode "shapes": off the 31 x 31, 15-frame CLAMP configuration ---------------------------------------------------------------------
+RECT_ROOT = dict(sequence_fps=20, sequence_duration=1.0, num_prev_states=5, max_num_boxes=7,
+                 heightmap=dict(horizontal_scale=0.2, local_grid=dict(num_x_neg=2, num_x_pos=4, num_y_neg=20, num_y_pos=11), max_h=3.0))
+RECT_FLOOR = dict(relative_z_style="RELATIVE_TO_ROOT_FLOOR",
+                  features=dict(frame_components=DEFAULT_COMPONENTS + ["FLOOR_HEIGHTS"], rot_type="DEFAULT", canonicalize_samples=True),
+                  heightmap=dict(horizontal_scale=0.2, local_grid=dict(num_x_neg=20, num_x_pos=11, num_y_neg=1, num_y_pos=3), max_h=3.0))
+RECT_NOISE = dict(hf_augmentation_mode="NOISE",   # 9 x 11 = 99 cells: the NOISE field's last Philox block is cut
+                  heightmap=dict(horizontal_scale=0.2, local_grid=dict(num_x_neg=3, num_x_pos=5, num_y_neg=6, num_y_pos=4), max_h=3.0))
+# (name, overrides, loop mode of both clips)
+SHAPE_CASES = [("rect_root", RECT_ROOT, "CLAMP"), ("rect_floor", RECT_FLOOR, "CLAMP"), ("rect_noise", RECT_NOISE, "CLAMP"),
+               ("wrap_root", RECT_ROOT, "WRAP"), ("wrap_floor", RECT_FLOOR, "WRAP")]
+CLIP_FPS = 30
+
+
+def wrap_starts(rng, ids, lengths, duration):
+    """Start times of a WRAP library: uniform over [0, length) (_sample_motion_start_times), then 0.2 s, and windows that begin one
+    frame (both clips) and four frames before the clip's end."""
+    t0 = (rng.rand(NUM_SAMPLES).astype(np.float32) * lengths[ids]).astype(np.float32)
+    frame = np.float32(1.0 / CLIP_FPS)
+    t0[0], t0[1] = 0.2, lengths[0] - frame
+    t0[2], t0[3] = lengths[1] - 4 * frame, lengths[1] - frame
+    return t0
+
+
+def check_wrap(s, plan, out):
+    """What the WRAP cases are there for, read from the recorded plan and bounds."""
+    ids, t0 = plan["motion_id"], plan["t0"]
+    length, nf = s._mlib._motion_lengths.numpy()[ids], s._mlib._motion_num_frames.numpy()[ids]
+    before_end = nf - 1 - np.round(t0.astype(np.float64) * CLIP_FPS).astype(np.int64)       # clip frames from the start to the last frame
+    assert (before_end == 1).any() and ((before_end >= 2) & (before_end <= 6)).any(), before_end
+    assert (t0 + np.float32(s._motion_times[-1]) > length).any() and (plan["t_future"] > length).any()
+    f0 = np.round(t0 / np.float32(s._timestep)).astype(np.int64)                              # the mask frames' first index (:214)
+    cut = f0 + s._seq_len > nf
+    # at sequence_fps < the clips' fps the indices round(t0 sequence_fps) + k stay below num_frames for every t0 < length: no cut there
+    can_cut = (np.round(length / np.float32(s._timestep)).astype(np.int64) + s._seq_len > nf).any()
+    assert cut.any() == can_cut, (f0, nf)
+    touched = (out["bounds_raw"][..., 0] != np.float32(2.0 * s._max_h)).any(axis=(1, 2))
+    assert touched.any()
+    print("  windows past the end:", int((t0 + np.float32(s._motion_times[-1]) > length).sum()), "targets past the end:",
+          int((plan["t_future"] > length).sum()), "mask slices cut:", int(cut.sum()), "samples with touched cells:", int(touched.sum()))
+
+
+def main_shapes():
+    rec, tmp, lib_yaml, extra = setup()
+    wrap_yaml = os.path.join(tmp, "motions_wrap.yaml")
+    files = []
+    for c in CLIPS:                                  # WRAP copies: loop_mode alone changes
+        d = ms_file.load_ms_file(os.path.join(REPO, "data/motion_terrains", c + ".pkl"), load_misc=False)
+        d.motion_data.loop_mode = "WRAP"
+        files.append(os.path.join(tmp, c + "_wrap.pkl"))
+        ms_file.save_ms_file(d, files[-1])
+    with open(wrap_yaml, "w") as f:
+        yaml.safe_dump({"motions": [{"file": p, "weight": 1.0} for p in files]}, f)
+    for case, over, loop in SHAPE_CASES:
+        cfg = dict(BASE_CFG)
+        cfg.update(over)
+        wrap = loop == "WRAP"
+        record_case(rec, case, cfg, wrap_yaml if wrap else lib_yaml, extra, starts=wrap_starts if wrap else clamp_starts,
+                    extra_out=dict(loop_modes=np.full(len(CLIPS), int(wrap), np.int32)), check=check_wrap if wrap else None)
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["shapes"]:
+        main_shapes()
+    elif sys.argv[1:]:
+        sys.exit("usage: make_golden_motion_sampler.py [shapes]")
+    else:
+        main()

@@ -18,15 +18,16 @@ def clip_path(name):
     return os.path.join(DATA, "motion_terrains", name + ".pkl")
 
 
-def load_clips(names):
+def load_clips(names, loop_modes=None):
+    """``loop_modes`` (one of 0 = CLAMP / 1 = WRAP per clip) overrides what the files hold."""
     out = []
-    for nm in names:
+    for i, nm in enumerate(names):
         d = ms_file.load_ms_file(clip_path(nm), load_misc=False)
         m, t = d.motion_data, d.terrain_data
         out.append(dict(name=nm, root_pos=m.root_pos.astype(np.float32), root_rot=m.root_rot.astype(np.float32),
                         joint_rot=m.joint_rot.astype(np.float32),
                         contacts=None if m.body_contacts is None else m.body_contacts.astype(np.float32),
-                        fps=int(m.fps), loop_mode=0 if m.loop_mode == "CLAMP" else 1,
+                        fps=int(m.fps), loop_mode=(0 if m.loop_mode == "CLAMP" else 1) if loop_modes is None else int(loop_modes[i]),
                         hf=t.hf.astype(np.float32), min_point=t.min_point.astype(np.float32), dx=float(t.dx)))
     return out
 

@@ -21,6 +21,9 @@ import motion_sampler_ref as ref  # noqa: E402
 
 CHAR = os.path.join(REPO, "data/assets/humanoid.xml")
 CASES = ["root_boxes", "floor_boxes", "noise", "none"]
+# off the 31 x 31, 15-frame CLAMP configuration (make_golden_motion_sampler.py shapes): 7 x 32 at 20 fps with T = 20, ref frame 4, 7 boxes;
+# 32 x 5 in floor mode; 9 x 11 NOISE; the first two on WRAP copies of the clips with windows and targets across the clip's end
+SHAPE_CASES = ["rect_root", "rect_floor", "rect_noise", "wrap_root", "wrap_floor"]
 TOL = 1e-5   # the bar of tests/test_device_ops_gpu.py for calc_motion_frame / FK against the reference goldens
 
 
@@ -41,8 +44,8 @@ def extra_vals(clip_names):
     return out
 
 
-def library(clip_names):
-    return ref.Library(helpers.load_clips(clip_names), extra_vals(clip_names))
+def library(clip_names, loop_modes=None):
+    return ref.Library(helpers.load_clips(clip_names, loop_modes), extra_vals(clip_names))
 
 
 def plan_of(z):
@@ -61,11 +64,11 @@ def cm():
     return CharModel(CHAR)
 
 
-@pytest.mark.parametrize("case", CASES)
+@pytest.mark.parametrize("case", CASES + SHAPE_CASES)
 def test_restatement_matches_reference(cm, case):
     z = fixture(case)
     cfg = ms.parse_config(z["cfg"])
-    o = ref.sample_with(library([str(c) for c in z["clips"]]), cm, cfg, plan_of(z))
+    o = ref.sample_with(library([str(c) for c in z["clips"]], z.get("loop_modes")), cm, cfg, plan_of(z))
     for k in ("root_pos", "root_rot", "joint_pos", "joint_rot", "contacts", "target_pos", "target_rot"):
         print(case, k, close(o[k], z[k], TOL, k))
     keep = ~z["skip"]
@@ -78,6 +81,15 @@ def test_restatement_matches_reference(cm, case):
     sub = z["hf_raw"][:, cfg.num_x_neg, cfg.num_y_neg] if cfg.relative_z_style == 1 else None
     if sub is not None:
         assert np.array_equal(o["hf_bounds"][keep], (z["bounds_raw"] - sub[:, None, None, None])[keep])
+
+
+def test_restatement_plan_builder_draws_boxes_over_the_patch(cm):
+    """The builder scales box centres by (Gx, Gy), not by a square, so that the GPU edge plans put boxes over the whole long side."""
+    cfg = ms.parse_config(fixture("rect_root")["cfg"])
+    bx = ref.RefSampler(library([str(c) for c in fixture("rect_root")["clips"]]), cm, cfg).draw_plan(512, 3)["boxes"]
+    assert (cfg.Gx, cfg.Gy) == (7, 32) and bx.shape == (512, 7, 6)
+    assert bx[..., 0].min() >= 0 and bx[..., 0].max() <= 7 and bx[..., 0].max() > 6.5
+    assert bx[..., 1].min() >= 0 and bx[..., 1].max() <= 32 and bx[..., 1].max() > 31 and (bx[..., 1] > 7).mean() > 0.7
 
 
 def test_restatement_sequences_and_stats(cm):
