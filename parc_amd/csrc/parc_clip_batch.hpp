@@ -1,61 +1,35 @@
-// parc_clip_batch.hpp — host code shared by the handles of the motion tools (parc_mopt_*, parc_mterr_*, parc_msamp_*; DESIGN.md
-// section 8d): the fill and upload of mopt::Model from ParcCharModel, and the validation and upload of the part of a packed
-// ParcMotionOptClips batch that the optimiser, the analyser and the sampler all read.  No kernel lives here.
+// parc_clip_batch.hpp — the clip batch of the motion tools (parc_mopt_*, parc_mterr_*, parc_msamp_*, parc_maug_*):
+// the device views of a packed ParcMotionOptClips batch that the kernels take by value, and the host code that validates and uploads
+// one.  No kernel lives here.
 //
-// `pre` is the caller's message prefix ("mopt", "mterr", "msamp"); the functions know nothing else about their caller.  What only one
-// module checks or uploads stays in that module.  mopt::Model and mopt::Clips are defined with the kernels that read them
-// (parc_motion_opt.hpp, which includes this file), so the functions that fill them take them as a template parameter.
+// ClipArrays is what every tool reads; FrameClips adds the two per-frame / per-clip arrays of the optimiser and the analyser.  A tool
+// with arrays of its own derives from these (the optimiser's Clips).  `pre` is the caller's message prefix ("mopt", "mterr", "msamp", "maug");
+// the functions know nothing else about their caller.  What only one module checks or uploads stays in that module.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/parc_env.h"
 #include "parc_common.hpp"
 
-// ---- the character model ---------------------------------------------------------------------------------------------------------
-// M = zeros, then B, D and the tree of cm.  The caller has checked num_bodies (and dof_size) against the limits.
-template <typename Model> static int model_tree(const char *pre, const ParcCharModel &cm, Model &M) {
-    memset(&M, 0, sizeof(M));
-    M.B = cm.num_bodies; M.D = cm.dof_size;
-    for (int b = 0; b < M.B; ++b) {
-        M.parent[b] = cm.parent[b]; M.jtype[b] = cm.joint_type[b]; M.dof_idx[b] = cm.dof_idx[b];
-        if (b > 0 && (cm.parent[b] < 0 || cm.parent[b] >= b)) return fail(PARC_ERR_INVALID, std::string(pre) + ": parents must precede their children");
-        for (int k = 0; k < 3; ++k) { M.lt[b][k] = cm.local_translation[b][k]; M.axis[b][k] = cm.joint_axis[b][k]; }
-        for (int k = 0; k < 4; ++k) M.lr[b][k] = cm.local_rotation[b][k];
-    }
-    return PARC_OK;
-}
+struct ClipArrays {                     // device pointers of one batch
+    int C;
+    long long F;
+    const long long *frame_off, *hf_off;
+    const float *hf_geom, *hf;
+    const float *src_root_pos, *src_root_rot, *src_jrot, *contacts;   // [F][3], [F][4], [F][B-1][4], [F][B]
+    const int *hf_dims;                 // last, beside FrameClips::frame_clip: the kernels that read dims[frame_clip[f]] then fetch
+};                                      // both pointers with one scalar load (k_mterr_gather: DESIGN.md section 1 has the measurement)
 
-// the sample points, grouped by body (pt_start / pt_count), and the contact column of every body; after model_tree
-template <typename Model>
-static int model_points(const char *pre, Model &M, int num_points, const float *points_host, const int32_t *point_body_host,
-                        const int32_t *contact_body_id) {
-    M.P = num_points;
-    for (int b = 0; b < M.B; ++b) {
-        M.contact_id[b] = contact_body_id[b];
-        if (M.contact_id[b] >= M.B) return fail(PARC_ERR_INVALID, std::string(pre) + ": contact_body_id out of range");
-    }
-    int prev = -1;
-    for (int k = 0; k < M.P; ++k) {
-        const int b = point_body_host[k];
-        if (b < 0 || b >= M.B || b < prev) return fail(PARC_ERR_INVALID, std::string(pre) + ": point bodies must be in [0, B) and non-decreasing");
-        if (b != prev) M.pt_start[b] = k;
-        M.pt_count[b]++;
-        prev = b;
-        M.pt_body[k] = b;
-        for (int d = 0; d < 3; ++d) M.pts[k][d] = points_host[3 * k + d];
-    }
-    return PARC_OK;
-}
+struct FrameClips : ClipArrays {
+    const int *frame_clip;              // [F] the clip of every frame
+    const float *hf_min;                // [C] torch.min(hf).item()
+};
 
-// the handle's copy of the model on the current device, allocated from `mem`
-template <typename Model> static int model_upload(DeviceArena &mem, const Model &M, Model *&d_model) { return mem.alloc(d_model, 1, &M); }
-
-// ---- the clip batch --------------------------------------------------------------------------------------------------------------
+// ---- validation and upload -------------------------------------------------------------------------------------------------------
 struct ClipBatch {                        // what clip_batch_clips derives from a valid batch
     int C = 0;
     long long F = 0, ncell = 0;           // frames and heightfield cells of all clips
@@ -95,8 +69,8 @@ static int clip_batch_clips(const char *pre, const ParcMotionOptClips *c, ClipBa
     return PARC_OK;
 }
 
-// K.C, K.F and the nine shared arrays of K, allocated from `mem`; B = bodies of the character
-template <typename Clips> static int clip_batch_upload(DeviceArena &mem, Clips &K, const ParcMotionOptClips *c, const ClipBatch &b, int B) {
+// K.C, K.F and the nine arrays of K, allocated from `mem`; B = bodies of the character
+static int clip_batch_upload(DeviceArena &mem, ClipArrays &K, const ParcMotionOptClips *c, const ClipBatch &b, int B) {
     const long long C = b.C, F = b.F;
     K.C = b.C; K.F = F;
     PARC_TRY(mem.alloc(K.frame_off, C + 1, c->frame_off_host));
@@ -109,4 +83,10 @@ template <typename Clips> static int clip_batch_upload(DeviceArena &mem, Clips &
     PARC_TRY(mem.alloc(K.src_jrot, 4 * F * (B - 1), c->joint_rot_host));
     PARC_TRY(mem.alloc(K.contacts, F * B, c->contacts_host));
     return PARC_OK;
+}
+
+// K.frame_clip and K.hf_min from what clip_batch_clips derived
+static int clip_batch_upload_frames(DeviceArena &mem, FrameClips &K, const ClipBatch &b) {
+    PARC_TRY(mem.alloc(K.frame_clip, b.F, b.frame_clip.data()));
+    return mem.alloc(K.hf_min, b.C, b.hf_min.data());
 }

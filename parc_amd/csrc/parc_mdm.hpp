@@ -24,15 +24,10 @@
 #include "../../include/parc_env.h"
 #include "parc_common.hpp"
 #include "parc_math.hpp"
-#include "parc_clip_batch.hpp"
-#include "parc_motion_opt.hpp"       // mopt::Model, fk_frame, dof_rot, ld3 .. st4
+#include "parc_char.hpp"
 
 namespace mdm {
 using namespace parc;
-using mopt::ld3;
-using mopt::ld4;
-using mopt::st3;
-using mopt::st4;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int WG = 256, NW = 4;            // k_mdm_forward / k_mdm_cond: 4 waves, one per SIMD
@@ -377,7 +372,7 @@ __global__ void __launch_bounds__(WG) k_mdm_forward(const Net *Np, Batch Bt, flo
 
 // ---- k_mdm_update -------------------------------------------------------------------------------------------------------------------
 // Joint.rot_to_dof (kin_char_model.py:83-105)
-__device__ __forceinline__ void rot_to_dof(const mopt::Model &M, int j, Q4 q, float *dof) {
+__device__ __forceinline__ void rot_to_dof(const CharTree &M, int j, Q4 q, float *dof) {
     const int t = M.jtype[j];
     if (t == PARC_JOINT_HINGE) {
         V3 ax; float ang;
@@ -393,12 +388,12 @@ __device__ __forceinline__ void rot_to_dof(const mopt::Model &M, int j, Q4 q, fl
 
 // lane per frame (mdm.py:848, :990-1008, :982-987 / :916-920).  Per lane in LDS: the frame [D], body positions [B][3], body and joint
 // rotations [B][4] each.
-__global__ void __launch_bounds__(UPD_T) k_mdm_update(const Net *Np, const mopt::Model *Mp, long long frames, const float *x0, const float *x0_nc, float gs,
+__global__ void __launch_bounds__(UPD_T) k_mdm_update(const Net *Np, const CharTree *Mp, long long frames, const float *x0, const float *x0_nc, float gs,
                                                       float *x, int last, float c0, float ct, float cn, const float *noise, int draw,
                                                       unsigned long long seed, unsigned long long first, unsigned step, float *x0p_out) {
     extern __shared__ float4 smem4[];
     const Net &N = *Np;
-    const mopt::Model &M = *Mp;
+    const CharTree &M = *Mp;
     const int D = N.D, T = N.T, B = M.B, J = B - 1, per = (D + 11 * B) | 1;   // an odd stride: the lanes' areas start on different LDS banks
     const long long i = (long long)blockIdx.x * UPD_T + threadIdx.x;
     if (i >= frames) return;
@@ -413,8 +408,8 @@ __global__ void __launch_bounds__(UPD_T) k_mdm_update(const Net *Np, const mopt:
     }
     const int o_jp = 6, o_jr = 6 + 3 * J, o_c = o_jr + M.D;
     const Q4 rq = exp_map_to_quat(ld3(fr + 3));
-    for (int j = 1; j < B; ++j) st4(jr + 4 * j, mopt::dof_rot(M, j, fr + o_jr));
-    mopt::fk_frame(M, ld3(fr), rq, jr, pos, rot);
+    for (int j = 1; j < B; ++j) st4(jr + 4 * j, dof_rot(M, j, fr + o_jr));
+    fk_frame(M, ld3(fr), rq, jr, pos, rot);
     st3(fr + 3, quat_to_exp_map(rq));
     for (int k = 0; k < 3 * J; ++k) fr[o_jp + k] = pos[3 + k];
     for (int j = 1; j < B; ++j) rot_to_dof(M, j, ld4(jr + 4 * j), fr + o_jr);
@@ -452,10 +447,10 @@ struct EventList {                        // events with one lifetime, created a
 struct ParcMdm {
     int device = 0;
     ParcMdmParams params{};
-    mopt::Model host_model;
+    parc::CharTree host_model;
     mdm::Net net{};                       // the host's copy: dimensions, device pointers
     DeviceArena mem;                      // create .. destroy
-    mopt::Model *d_model = nullptr;
+    parc::CharTree *d_model = nullptr;
     mdm::Net *d_net = nullptr;
     mdm::Batch batch{};
     float *d_x0 = nullptr;                // [2 max_batch][T][D]
@@ -534,7 +529,8 @@ extern "C" int parc_mdm_create(const ParcMdmParams *p, ParcMdm **out) {
         return fail(PARC_ERR_INVALID, "mdm: null array");
     for (long long i = 0; i < (long long)T * D; ++i)
         if (!std::isfinite(p->mean_host[i]) || !std::isfinite(p->std_host[i]) || p->std_host[i] == 0.f) return fail(PARC_ERR_INVALID, "mdm: the feature mean / std must be finite, the std non-zero");
-    mopt::Model M;
+    parc::CharTree M;
+    model_zero(M);
     PARC_TRY(model_tree("mdm", cm, M));
 
     Net N{};

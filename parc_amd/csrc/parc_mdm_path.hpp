@@ -13,10 +13,6 @@
 
 namespace mpath {
 using namespace parc;
-using mopt::ld3;
-using mopt::ld4;
-using mopt::st3;
-using mopt::st4;
 
 constexpr int CW = 64;                     // k_mpath_cond: one wave; k_mpath_append / k_mpath_begin: lanes per block
 constexpr int G = PARC_MDM_GRID;
@@ -44,7 +40,7 @@ struct CondOut {
 // a frame of the rollout buffer: root position 3, root rotation 4, joint rotations (B - 1) x 4, contacts B
 __host__ __device__ __forceinline__ int frame_floats(int B) { return 7 + 4 * (B - 1) + B; }
 
-__global__ void __launch_bounds__(CW) k_mpath_begin(const mopt::Model *Mp, Scene S, int nprev, float *prev, const float *rel_h, const float *heading, int random_heading,
+__global__ void __launch_bounds__(CW) k_mpath_begin(const CharTree *Mp, Scene S, int nprev, float *prev, const float *rel_h, const float *heading, int random_heading,
                                                     unsigned long long seed, const long long *path_ids) {
     const int B = Mp->B, FD = frame_floats(B);
     const long long i = (long long)blockIdx.x * CW + threadIdx.x;
@@ -67,12 +63,12 @@ __global__ void __launch_bounds__(CW) k_mpath_begin(const mopt::Model *Mp, Scene
     st4(o + 3, axis_angle_to_quat(mk3(0.f, 0.f, 1.f), h));
 }
 
-__global__ void __launch_bounds__(CW) k_mpath_cond(const mdm::Net *Np, const mopt::Model *Mp, Scene S, Cfg C, const float *prev, CondOut O, int first, int ind_val,
+__global__ void __launch_bounds__(CW) k_mpath_cond(const mdm::Net *Np, const CharTree *Mp, Scene S, Cfg C, const float *prev, CondOut O, int first, int ind_val,
                                                    int *not_done, float *x, const float *noise, int draw, unsigned long long seed, const long long *row_ids,
                                                    unsigned window) {
     extern __shared__ float4 smem4[];
     const mdm::Net &N = *Np;
-    const mopt::Model &M = *Mp;
+    const CharTree &M = *Mp;
     const int row = blockIdx.x, lane = threadIdx.x;
     const int B = M.B, J = B - 1, D = N.D, nprev = N.nprev, FD = frame_floats(B), per = (D + 11 * B) | 1;
     const int p = S.row_path[row], cnt = S.counts[p];
@@ -109,7 +105,7 @@ __global__ void __launch_bounds__(CW) k_mpath_cond(const mdm::Net *Np, const mop
             rp.z = rp.z - cz;
             rr = quat_mul(hqi, rr);
         }
-        mopt::fk_frame(M, rp, rr, jr, pos, rot);
+        fk_frame(M, rp, rr, jr, pos, rot);
         if (lane < nprev) {
             const int o_jp = 6, o_jr = 6 + 3 * J, o_c = o_jr + M.D;
             st3(fr, rp);
@@ -164,12 +160,12 @@ __global__ void __launch_bounds__(CW) k_mpath_cond(const mdm::Net *Np, const mop
 
 // gen_sequence's torch.where and extract_motion_features (mdm.py:1153-1158), then gen_util.py:137-144.  Frames [lo, hi) of the window go
 // to frames[row][off ..], frames [pn_lo, pn_hi) to prev_next; final_frame (total >= 0) takes `total` where the row is done for the first time.
-__global__ void __launch_bounds__(CW) k_mpath_append(const mdm::Net *Np, const mopt::Model *Mp, int n, const float *x, const float *prevstd, const int *ind,
+__global__ void __launch_bounds__(CW) k_mpath_append(const mdm::Net *Np, const CharTree *Mp, int n, const float *x, const float *prevstd, const int *ind,
                                                      const float *canon, int guided, int lo, int hi, int off, float *frames, int max_frames, float *prev_next,
                                                      int pn_lo, int pn_hi, const int *done, int *final_frame, int total) {
     extern __shared__ float4 smem4[];
     const mdm::Net &N = *Np;
-    const mopt::Model &M = *Mp;
+    const CharTree &M = *Mp;
     const int B = M.B, J = B - 1, D = N.D, T = N.T, nprev = N.nprev, FD = frame_floats(B), per = D | 1;
     const long long i = (long long)blockIdx.x * CW + threadIdx.x;
     if (i >= (long long)n * T) return;
@@ -193,7 +189,7 @@ __global__ void __launch_bounds__(CW) k_mpath_append(const mdm::Net *Np, const m
     for (int t = 0; t < 2; ++t)
         if (dst[t]) { st3(dst[t], wp); st4(dst[t] + 3, wq); }
     for (int j = 1; j < B; ++j) {
-        const Q4 q = mopt::dof_rot(M, j, fr + o_jr);
+        const Q4 q = dof_rot(M, j, fr + o_jr);
         if (d0) st4(d0 + 7 + 4 * (j - 1), q);
         if (d1) st4(d1 + 7 + 4 * (j - 1), q);
     }

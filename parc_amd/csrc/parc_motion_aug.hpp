@@ -26,16 +26,12 @@
 #include "../../include/parc_env.h"
 #include "parc_common.hpp"
 #include "parc_math.hpp"
+#include "parc_char.hpp"
+#include "parc_grid.hpp"
 #include "parc_clip_batch.hpp"
-#include "parc_motion_opt.hpp"       // mopt::Model / Clips, qmul, ld3 .. st4
-#include "parc_motion_terrain.hpp"   // mterr::grid_index
 
 namespace maug {
 using namespace parc;
-using mopt::ld3;
-using mopt::ld4;
-using mopt::st3;
-using mopt::st4;
 
 constexpr int MAXB = PARC_MAUG_MAX_BOXES, BF = PARC_MAUG_BOX_FLOATS, MAXD = PARC_MAUG_MAX_DIM;
 constexpr int WAVE_CELLS = 1024, WG_THREADS = 256;
@@ -48,7 +44,7 @@ struct Cfg {                               // by value
     float len0, len1, ang0, ang1, bh0, bh1;            // boxes: side length (cells), angle, height ranges
     int jswap[PARC_MAX_BODIES], cswap[PARC_MAX_BODIES];   // left / right partner of every joint and contact column (itself when none)
 };
-struct Lib {                               // per clip, beside mopt::Clips
+struct Lib {                               // per clip, beside ClipArrays
     const float *maxmin;                   // [cells][2] or NULL
     const float *ring;                     // [C][2] what the pad ring reads for hf_maxmin: max of max, min of min
     const float *pgeom;                    // [C][4] the padded terrain's min point, dx, dy
@@ -70,7 +66,7 @@ __device__ __forceinline__ unsigned long long ctr_hi(unsigned long long v) { ret
 __device__ __forceinline__ float scale_u(float u, float lo, float hi) { return u * (hi - lo) + lo; }
 __device__ __forceinline__ int randint_incl(float u, int m) { const int v = (int)(u * (float)(m + 1)); return v < m ? v : m; }
 
-__device__ __forceinline__ Var draw_var(const Cfg &G, const mopt::Clips &K, const Lib &L, unsigned long long seed, unsigned long long idx, int mirror) {
+__device__ __forceinline__ Var draw_var(const Cfg &G, const ClipArrays &K, const Lib &L, unsigned long long seed, unsigned long long idx, int mirror) {
     float u[4], w[4];
     philox4(seed, ctr_hi(idx), 0u, u);
     philox4(seed, ctr_hi(idx), 1u, w);
@@ -106,7 +102,7 @@ __device__ __forceinline__ void draw_box(const Cfg &G, unsigned long long seed, 
 // variation v of the launch: drawn, or read from the plan with every index clamped into its range (memory safety; the status word
 // records that a clamp happened)
 template <bool DRAW>
-__device__ __forceinline__ Var get_var(const Cfg &G, const mopt::Clips &K, const Lib &L, const PlanD &P, long long v, unsigned long long seed,
+__device__ __forceinline__ Var get_var(const Cfg &G, const ClipArrays &K, const Lib &L, const PlanD &P, long long v, unsigned long long seed,
                                        unsigned long long first, int mirror, int *status) {
     if (DRAW) return draw_var(G, K, L, seed, first + (unsigned long long)v, mirror);
     Var V;
@@ -129,7 +125,7 @@ __device__ __forceinline__ Var get_var(const Cfg &G, const mopt::Clips &K, const
 }
 
 // lane per variation (the boxes of a variation in its lane's loop: at most PARC_MAUG_MAX_BOXES)
-__global__ void k_maug_draw(mopt::Clips K, Lib L, Cfg G, PlanD P, long long n, unsigned long long seed, unsigned long long first, int mirror) {
+__global__ void k_maug_draw(ClipArrays K, Lib L, Cfg G, PlanD P, long long n, unsigned long long seed, unsigned long long first, int mirror) {
     const long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= n) return;
     const Var V = draw_var(G, K, L, seed, first + (unsigned long long)v, mirror);
@@ -145,7 +141,7 @@ __global__ void k_maug_draw(mopt::Clips K, Lib L, Cfg G, PlanD P, long long n, u
 }
 
 template <bool DRAW>
-__global__ void k_maug_layout(mopt::Clips K, Lib L, Cfg G, PlanD P, int *cnt_f, long long n, unsigned long long seed, unsigned long long first, int *status) {
+__global__ void k_maug_layout(ClipArrays K, Lib L, Cfg G, PlanD P, int *cnt_f, long long n, unsigned long long seed, unsigned long long first, int *status) {
     const long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= n) return;
     cnt_f[v] = get_var<DRAW>(G, K, L, P, v, seed, first, 0, status).nf;
@@ -187,12 +183,12 @@ __device__ __forceinline__ float arange_point(float start, int i, float step) { 
 
 // the source cell under point (px, py) of the padded terrain of a clip (get_grid_index on the padded dims), -1 in the pad ring
 __device__ __forceinline__ long long padded_cell(const float *pg, int pad, long long X0, long long Y0, float px, float py) {
-    const long long i = mterr::grid_index(px, pg[0], pg[2], X0 + 2 * pad) - pad, j = mterr::grid_index(py, pg[1], pg[3], Y0 + 2 * pad) - pad;
+    const long long i = grid_index(px, pg[0], pg[2], X0 + 2 * pad) - pad, j = grid_index(py, pg[1], pg[3], Y0 + 2 * pad) - pad;
     return (i >= 0 && i < X0 && j >= 0 && j < Y0) ? i * Y0 + j : -1;
 }
 
 // Joint.rot_to_dof then Joint.dof_to_rot (kin_char_model.py:61-105) of the flipped quaternion of joint p, rebuilt as joint j = its mirror
-__device__ __forceinline__ Q4 mirror_joint(const mopt::Model &M, int p, int j, Q4 q) {
+__device__ __forceinline__ Q4 mirror_joint(const CharTree &M, int p, int j, Q4 q) {
     q = mk4(q.x, -q.y, q.z, -q.w);                             // flip_quat_about_XZ_plane
     const int t = M.jtype[p];
     if (t == PARC_JOINT_HINGE) {
@@ -206,9 +202,9 @@ __device__ __forceinline__ Q4 mirror_joint(const mopt::Model &M, int p, int j, Q
 }
 
 template <bool DRAW>
-__global__ void __launch_bounds__(64) k_maug_frames(const mopt::Model *Mp, mopt::Clips K, Lib L, Cfg G, PlanD P, Run R, unsigned long long seed,
+__global__ void __launch_bounds__(64) k_maug_frames(const CharTree *Mp, ClipArrays K, Lib L, Cfg G, PlanD P, Run R, unsigned long long seed,
                                                     unsigned long long first, int mirror, int *status) {
-    const mopt::Model &M = *Mp;
+    const CharTree &M = *Mp;
     const long long v = blockIdx.x;
     const int lane = threadIdx.x, B = G.B, J = B - 1;
     const Var V = get_var<DRAW>(G, K, L, P, v, seed, first, mirror, status);
@@ -226,7 +222,7 @@ __global__ void __launch_bounds__(64) k_maug_frames(const mopt::Model *Mp, mopt:
         nan |= (x != x) || (y != y);
         mnx = fminf(mnx, x); mny = fminf(mny, y); mxx = fmaxf(mxx, x); mxy = fmaxf(mxy, y);
         st3(R.root_pos + 3 * (fo + f), mk3(x, y, p.z));
-        st4(R.root_rot + 4 * (fo + f), exp_map_to_quat(quat_to_exp_map(mopt::qmul(hq, ld4(K.src_root_rot + 4 * (f0 + f))))));
+        st4(R.root_rot + 4 * (fo + f), exp_map_to_quat(quat_to_exp_map(qmul(hq, ld4(K.src_root_rot + 4 * (f0 + f))))));
     }
     mnx = wave_min(mnx); mny = wave_min(mny); mxx = wave_max(mxx); mxy = wave_max(mxy);
     // torch.min / max propagate NaN; an infinite bound (an infinite scale) is no slice either: both end as the 1 x 1 slice below
@@ -247,7 +243,7 @@ __global__ void __launch_bounds__(64) k_maug_frames(const mopt::Model *Mp, mopt:
     }
     const float lminx = mgx - cx, lminy = mgy - cy;            // min_x = min_grid_point - canon_xy
     if (G.slice) {                                             // get_hf_val_from_points(localised frame 0 = (0, 0)) on the sliced terrain (:1638)
-        const int i0 = (int)mterr::grid_index(0.f, lminx, dx, X), j0 = (int)mterr::grid_index(0.f, lminy, dy, Y);
+        const int i0 = (int)grid_index(0.f, lminx, dx, X), j0 = (int)grid_index(0.f, lminy, dy, Y);
         const long long cell = padded_cell(pg, G.pad, X0, Y0, arange_point(mgx, i0, dx), arange_point(mgy, j0, dy));
         cz = cell >= 0 ? K.hf[K.hf_off[c] + cell] : 0.f;
     }
@@ -298,7 +294,7 @@ __device__ __forceinline__ bool box_hit(const float *d, float x, float y) {
 }
 
 template <bool DRAW>
-__global__ void __launch_bounds__(WG_THREADS) k_maug_terrain(mopt::Clips K, Lib L, Cfg G, PlanD P, Run R, unsigned long long seed, unsigned long long first,
+__global__ void __launch_bounds__(WG_THREADS) k_maug_terrain(ClipArrays K, Lib L, Cfg G, PlanD P, Run R, unsigned long long seed, unsigned long long first,
                                                              int mirror, int *status) {
     __shared__ float s_b[MAXB * BS];
     const long long v = blockIdx.x;
@@ -349,7 +345,7 @@ __global__ void __launch_bounds__(WG_THREADS) k_maug_terrain(mopt::Clips K, Lib 
 
 // ---- validate -----------------------------------------------------------------------------------------------------------------------
 enum { VB_SRC = 0, VB_START, VB_NFRAMES, VB_HEADING, VB_SCALE, VB_MIRROR, VB_HSCALE, VB_NBOXES, VB_BOX_FRAME, VB_BOXES, VB_COUNT };
-__global__ void k_maug_validate(mopt::Clips K, Cfg G, PlanD P, long long n, int *bits) {
+__global__ void k_maug_validate(ClipArrays K, Cfg G, PlanD P, long long n, int *bits) {
     const long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= n) return;
     int bad = 0;
@@ -382,7 +378,7 @@ __global__ void k_maug_validate(mopt::Clips K, Cfg G, PlanD P, long long n, int 
 struct ParcMotionAug {
     struct Library {                      // what one parc_maug_set_clips loads
         DeviceArena mem;
-        mopt::Clips K{};
+        ClipArrays K{};
         maug::Lib L{};
     };
     struct Result {                       // what one run leaves: released by the next run, a new library, or with the handle
@@ -392,10 +388,10 @@ struct ParcMotionAug {
         long long F = 0, cells = 0;
     };
     int device = 0;
-    mopt::Model host_model;
+    parc::CharTree host_model;
     ParcMotionAugParams params{};
     DeviceArena mem;                      // create .. destroy: d_model, d_status
-    mopt::Model *d_model = nullptr;
+    parc::CharTree *d_model = nullptr;
     maug::Cfg cfg{};
     std::unique_ptr<Library> lib;
     std::unique_ptr<Result> res;
@@ -418,7 +414,8 @@ extern "C" int parc_maug_create(const ParcMotionAugParams *p, ParcMotionAug **ou
         return fail(PARC_ERR_INVALID, "maug: terrain_padding_size must be 0 .. PARC_MAUG_MAX_DIM = " + std::to_string(PARC_MAUG_MAX_DIM));
     const float ranges[][2] = {{p->min_heading_angle, p->max_heading_angle}, {p->x_scale[0], p->x_scale[1]}, {p->y_scale[0], p->y_scale[1]}};
     for (const auto &r : ranges) if (!std::isfinite(r[0]) || !std::isfinite(r[1])) return fail(PARC_ERR_INVALID, "maug: a heading or scale range is not finite");
-    mopt::Model M;
+    parc::CharTree M;
+    model_zero(M);
     PARC_TRY(model_tree("maug", cm, M));
     maug::Cfg G{};
     G.mode = p->mode; G.pad = p->terrain_padding_size; G.slice = p->slice_terrain != 0; G.B = M.B;
@@ -565,7 +562,7 @@ template <bool DRAW>
 static int maug_run(ParcMotionAug *h, int n, const ParcMotionAugPlan *plan, unsigned long long seed, unsigned long long first, int mirror, hipStream_t st,
                     ParcMotionAugSizes *sizes) {
     const maug::Cfg &G = h->cfg;
-    const mopt::Clips &K = h->lib->K;
+    const ClipArrays &K = h->lib->K;
     const maug::Lib &L = h->lib->L;
     const maug::PlanD P = maug_plan(plan);
     const int B = G.B, J = B - 1;

@@ -25,6 +25,8 @@
 #include "../../include/parc_env.h"
 #include "parc_common.hpp"
 #include "parc_math.hpp"
+#include "parc_char.hpp"
+#include "parc_grid.hpp"
 #include "parc_clip_batch.hpp"
 
 namespace mopt {
@@ -36,27 +38,17 @@ constexpr int MAXB = PARC_MAX_BODIES;
 constexpr int PT_THREADS = 256;
 enum { T_ROOT_POS = 0, T_ROOT_ROT, T_JOINT_ROT, T_SMOOTH, T_PEN, T_CONTACT, T_SLIDING, T_BODYCONS, T_JERK };
 
-struct Model {                          // global memory, read with uniform indices
-    int B, D, NP, P;
-    int parent[MAXB], jtype[MAXB], dof_idx[MAXB];
-    float lt[MAXB][3], lr[MAXB][4], axis[MAXB][3];
-    int pt_start[MAXB], pt_count[MAXB];
-    int g0type[MAXB], contact_id[MAXB];
+struct Model : CharPoints {             // the character (parc_char.hpp) + what the loss terms read; global memory, uniform indices
+    int NP;
+    int g0type[MAXB];
     float g0off[MAXB][3], g0rad[MAXB];
     float w[NT];
     float max_jerk;                     // already scaled by (1/30)^3
-    float pts[MAXP][3];
-    int pt_body[MAXP];
 };
 
-struct Clips {                          // device pointers of one batch
-    int C;
-    long long F;
-    const long long *frame_off, *hf_off, *cons_off;
-    const int *frame_clip;              // [F]
-    const int *hf_dims; const float *hf_geom, *hf, *hf_min;
-    const float *src_root_pos, *src_root_rot, *src_jrot, *contacts;   // [F][3], [F][4], [F][B-1][4], [F][B]
-    float *src_pos, *src_rot;                                         // source FK [F][B][3], [F][B][4]
+struct Clips : FrameClips {             // the batch (parc_clip_batch.hpp) + the source FK and the constraints
+    const long long *cons_off;
+    float *src_pos, *src_rot;           // source FK [F][B][3], [F][B][4]
     const int *cons_body, *cons_range; float *cons_point;
 };
 
@@ -69,22 +61,6 @@ struct Work {                           // per-frame workspace, each frame owned
     float *fterms;                      // [F][NT]
     float *terms;                       // [C][NT]
 };
-
-__device__ __forceinline__ V3 add3(V3 a, V3 b) { return mk3(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ V3 sub3(V3 a, V3 b) { return mk3(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ V3 scl3(V3 a, float s) { return mk3(a.x * s, a.y * s, a.z * s); }
-__device__ __forceinline__ float dot3(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 ld3(const float *p) { return mk3(p[0], p[1], p[2]); }
-__device__ __forceinline__ Q4 ld4(const float *p) { return mk4(p[0], p[1], p[2], p[3]); }
-__device__ __forceinline__ void st3(float *p, V3 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
-__device__ __forceinline__ void st4(float *p, Q4 q) { p[0] = q.x; p[1] = q.y; p[2] = q.z; p[3] = q.w; }
-__device__ __forceinline__ void acc3(float *p, V3 v) { p[0] += v.x; p[1] += v.y; p[2] += v.z; }
-__device__ __forceinline__ void acc4(float *p, Q4 q) { p[0] += q.x; p[1] += q.y; p[2] += q.z; p[3] += q.w; }
-// Hamilton product written out (the adjoint products; the forward keeps parc::quat_mul's factored form)
-__device__ __forceinline__ Q4 qmul(Q4 a, Q4 b) {
-    return mk4(a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y, a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x,
-               a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w, a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z);
-}
 
 // d/dq of quat_rotate(q, v) = v + w t + u x t, t = 2 u x v, applied to g: gu = 2w (v x g) + t x g + 2 v x (g x u), gw = g . t
 __device__ __forceinline__ Q4 rotate_vjp_q(Q4 q, V3 v, V3 g) {
@@ -129,36 +105,8 @@ __device__ __forceinline__ float hinge_vjp(const float *axis, float d, Q4 g) {
     return 0.5f * cosf(0.5f * d) * (na.x * g.x + na.y * g.y + na.z * g.z) - 0.5f * sinf(0.5f * d) * g.w;
 }
 
-__device__ __forceinline__ Q4 dof_rot(const Model &M, int j, const float *dof) {
-    const int t = M.jtype[j];
-    if (t == PARC_JOINT_HINGE) return axis_angle_to_quat(mk3(M.axis[j][0], M.axis[j][1], M.axis[j][2]), dof[M.dof_idx[j]]);
-    if (t == PARC_JOINT_SPHERICAL) {
-        const float *d = dof + M.dof_idx[j];
-        return exp_map_to_quat(mk3(d[0], d[1], d[2]));
-    }
-    return mk4(0.f, 0.f, 0.f, 1.f);
-}
-
-// FK of one frame (kin_char_model.py:617-649) into pos / rot ([B][3], [B][4]); jrot [B][4], body 0 unused
-__device__ __forceinline__ void fk_frame(const Model &M, V3 rp, Q4 rq, const float *jrot, float *pos, float *rot) {
-    st3(pos, rp); st4(rot, rq);
-    for (int j = 1; j < M.B; ++j) {
-        const int p = M.parent[j];
-        const Q4 pr = ld4(rot + 4 * p);
-        const V3 wt = quat_rotate(pr, mk3(M.lt[j][0], M.lt[j][1], M.lt[j][2]));
-        const V3 pp = ld3(pos + 3 * p);
-        st3(pos + 3 * j, add3(pp, wt));
-        st4(rot + 4 * j, quat_mul(pr, quat_mul(mk4(M.lr[j][0], M.lr[j][1], M.lr[j][2], M.lr[j][3]), ld4(jrot + 4 * j))));
-    }
-}
-
-// sdBox (geom_util.py:124-145) of a point relative to the box centre, and its gradient as autograd computes it (sign(p) through abs,
-// the clamp masks q >= 0 / max(q) <= 0, the first maximal component for max(dim=-1), 0 for a zero norm)
-__device__ __forceinline__ float sd_box(V3 p, V3 h) {
-    const float qx = fabsf(p.x) - h.x, qy = fabsf(p.y) - h.y, qz = fabsf(p.z) - h.z;
-    const float px = fmaxf(qx, 0.f), py = fmaxf(qy, 0.f), pz = fmaxf(qz, 0.f);
-    return sqrtf(px * px + py * py + pz * pz) + fminf(fmaxf(qx, fmaxf(qy, qz)), 0.f);
-}
+// the gradient of sdBox (parc_grid.hpp's sd_box; geom_util.py:124-145) as autograd computes it (sign(p) through abs, the clamp masks
+// q >= 0 / max(q) <= 0, the first maximal component for max(dim=-1), 0 for a zero norm)
 __device__ __forceinline__ V3 sd_box_grad(V3 p, V3 h) {
     const float qx = fabsf(p.x) - h.x, qy = fabsf(p.y) - h.y, qz = fabsf(p.z) - h.z;
     const float px = fmaxf(qx, 0.f), py = fmaxf(qy, 0.f), pz = fmaxf(qz, 0.f);
@@ -214,11 +162,6 @@ __device__ __forceinline__ SdfOut patch_sdf(V3 x, const float *hf, int Y, int x0
                               mk3(hx, hy, (10.f - h) / 2.f));
     }
     return o;
-}
-
-// torch's .to(int64) of a floor / ceil on x86: NaN and out-of-range give INT64_MIN (then clamped like every other index)
-__device__ __forceinline__ long long to_i64(float v) {
-    return (v >= -9.0e18f && v <= 9.0e18f) ? (long long)v : (long long)(-9223372036854775807LL - 1);
 }
 
 // ---- setup: FK of the source frames and the initial iterate (motion_optimization.py:744-758) -----------------------------------------
@@ -589,6 +532,7 @@ extern "C" int parc_mopt_create(const ParcMotionOptParams *p, ParcMotionOpt **ou
     if (p->num_points < 1 || p->num_points > PARC_MOPT_MAX_POINTS || !p->points_host || !p->point_body_host)
         return fail(PARC_ERR_INVALID, "mopt: num_points must be in [1, 512] with points and point bodies given");
     mopt::Model M;
+    model_zero(M);
     PARC_TRY(model_tree("mopt", cm, M));
     M.NP = PARC_MOPT_NP(cm.dof_size);
     for (int b = 0; b < M.B; ++b) {
@@ -635,8 +579,7 @@ extern "C" int parc_mopt_set_clips(ParcMotionOpt *h, const ParcMotionOptClips *c
     DeviceArena &mem = nb->mem;
     PARC_TRY(clip_batch_upload(mem, K, c, cb, B));
     PARC_TRY(mem.alloc(K.cons_off, C + 1, c->cons_off_host));
-    PARC_TRY(mem.alloc(K.frame_clip, F, cb.frame_clip.data()));
-    PARC_TRY(mem.alloc(K.hf_min, C, cb.hf_min.data()));
+    PARC_TRY(clip_batch_upload_frames(mem, K, cb));
     PARC_TRY(mem.alloc(K.src_pos, 3 * F * B));
     PARC_TRY(mem.alloc(K.src_rot, 4 * F * B));
     PARC_TRY(mem.alloc(K.cons_body, ncons, c->cons_body_host));

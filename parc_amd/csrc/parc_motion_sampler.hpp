@@ -6,7 +6,7 @@
 //   k_msamp_draw    lane per sample: fills a plan from (seed, sample index) with Philox4x32-10 (sample_motions, _sample_motion_start_times,
 //                   _sample_motion_future_times, _box_hf_augmentation's and add_boxes_to_hf2's draws); lane per cell for the NOISE field
 //   k_msamp_window  one wave per sample, lanes over frames x bodies: calc_motion_frame (motion_lib.py:94-126) at t0 + times[k],
-//                   canonicalisation to the heading frame of the reference frame (sample_motion_data :227-249), FK with the optimiser's
+//                   canonicalisation to the heading frame of the reference frame (sample_motion_data :227-249), FK with parc_char.hpp's
 //                   fk_frame, lane per frame, in LDS; the target (_sample_target_info :147-161); coalesced stores from LDS
 //   k_msamp_hf      one workgroup per sample: the window's cell mask as a bitset over the clip's terrain in LDS, the patch and its two
 //                   bound planes in LDS (get_hfs_from_data :373-398), the augmentation (_box_hf_augmentation :293-335, maxpool_hf*
@@ -26,16 +26,12 @@
 #include "../../include/parc_env.h"
 #include "parc_common.hpp"
 #include "parc_math.hpp"
+#include "parc_char.hpp"
+#include "parc_grid.hpp"
 #include "parc_clip_batch.hpp"
-#include "parc_motion_opt.hpp"       // mopt::Model / Clips, fk_frame, qmul, to_i64
-#include "parc_motion_terrain.hpp"   // mterr::grid_index
 
 namespace msamp {
 using namespace parc;
-using mopt::ld3;
-using mopt::ld4;
-using mopt::st3;
-using mopt::st4;
 
 constexpr int HF_THREADS = 256;
 constexpr int GM = PARC_MSAMP_MAX_GRID;
@@ -49,7 +45,7 @@ struct Cfg {                               // by value
     const float *times, *gridx, *gridy;    // [T], [Gx], [Gy]
 };
 
-struct Lib {                               // the resident library (mopt::Clips K holds the frames and terrains)
+struct Lib {                               // the resident library (ClipArrays K holds the frames and terrains)
     const MotionMeta *meta;                // [C] start = first frame, nframes, length, loop, wrap delta, fps
     const float *maxmin;                   // [cells][2]
     const long long *mask_off;             // [F + 1]
@@ -60,7 +56,7 @@ struct Lib {                               // the resident library (mopt::Clips 
 __device__ __forceinline__ float nanf_() { return __int_as_float(0x7fc00000); }
 
 // root position and rotation of calc_motion_frame (motion_lib.py:94-118): lerp, slerp, the WRAP offset (:440)
-__device__ __forceinline__ void root_at(const mopt::Clips &K, const MotionMeta &m, float t, V3 &pos, Q4 &rot) {
+__device__ __forceinline__ void root_at(const ClipArrays &K, const MotionMeta &m, float t, V3 &pos, Q4 &rot) {
     const Blend bl = frame_blend(m, t);
     const float b = bl.b, a = 1.0f - b;
     const V3 A = ld3(K.src_root_pos + 3 * (long long)bl.i0), Bv = ld3(K.src_root_pos + 3 * (long long)bl.i1);
@@ -77,7 +73,7 @@ __device__ __forceinline__ void root_at(const mopt::Clips &K, const MotionMeta &
 // :375-380, rotate_2d_vec torch_util.py:651-662, SubTerrain.get_grid_index terrain_util.py:146-152)
 __device__ __forceinline__ int patch_cell(float gx, float gy, float ch, float sh, float rx, float ry, const float *g, long long X, long long Y) {
     const float px = (gx * ch - gy * sh) + rx, py = (gx * sh + gy * ch) + ry;
-    return (int)(mterr::grid_index(px, g[0], g[2], X) * Y + mterr::grid_index(py, g[1], g[3], Y));
+    return (int)(grid_index(px, g[0], g[2], X) * Y + grid_index(py, g[1], g[3], Y));
 }
 
 // torch.clamp(x, min, max) = min(max(x, min), max); NaN in any operand gives NaN
@@ -108,10 +104,10 @@ __host__ __device__ __forceinline__ int win_sr(int B) { return 4 * B + 1; }
 __host__ __device__ __forceinline__ int win_sp(int B) { return (3 * B) | 1; }
 __host__ __device__ __forceinline__ size_t win_lds_bytes(int T, int B) { return (size_t)T * (2 * win_sr(B) + win_sp(B) + B) * sizeof(float); }
 
-__global__ void __launch_bounds__(64) k_msamp_window(const mopt::Model *Mp, mopt::Clips K, Lib L, Cfg G, PlanD P, OutD O, int enum_clip,
+__global__ void __launch_bounds__(64) k_msamp_window(const CharTree *Mp, ClipArrays K, Lib L, Cfg G, PlanD P, OutD O, int enum_clip,
                                                      int *status) {
     extern __shared__ float s_win[];
-    const mopt::Model &M = *Mp;
+    const CharTree &M = *Mp;
     const long long s = blockIdx.x;
     const int lane = threadIdx.x, T = G.T, B = G.B, J = B - 1;
     const int SR = win_sr(B), SP = win_sp(B);
@@ -140,7 +136,7 @@ __global__ void __launch_bounds__(64) k_msamp_window(const mopt::Model *Mp, mopt
             if (floor_mode) p.z = p.z - center_h;
             p = quat_rotate(hinv, mk3(p.x - cpos.x, p.y - cpos.y, p.z - cpos.z));
             st3(s_pos + k * SP, p);
-            st4(s_rot + k * SR, mopt::qmul(hinv, r));       // torch_util.quat_multiply: the written-out product
+            st4(s_rot + k * SR, qmul(hinv, r));       // torch_util.quat_multiply: the written-out product
         } else {
             const Blend bl = frame_blend(meta, t);
             const float *q0 = K.src_jrot + ((long long)bl.i0 * J + (j - 1)) * 4, *q1 = K.src_jrot + ((long long)bl.i1 * J + (j - 1)) * 4;
@@ -152,7 +148,7 @@ __global__ void __launch_bounds__(64) k_msamp_window(const mopt::Model *Mp, mopt
     }
     __syncthreads();
     for (int k = lane; k < T; k += 64)
-        mopt::fk_frame(M, ld3(s_pos + k * SP), ld4(s_rot + k * SR), s_jrot + k * SR, s_pos + k * SP, s_rot + k * SR);
+        fk_frame(M, ld3(s_pos + k * SP), ld4(s_rot + k * SR), s_jrot + k * SR, s_pos + k * SP, s_rot + k * SR);
     if (lane == 63 && O.target_pos) {                        // _sample_target_info :147-161
         V3 fp; Q4 fr;
         root_at(K, meta, P.t_future[s], fp, fr);
@@ -160,7 +156,7 @@ __global__ void __launch_bounds__(64) k_msamp_window(const mopt::Model *Mp, mopt
         fp = mk3(fp.x + nz[0], fp.y + nz[1], fp.z + nz[2]);
         fp = quat_rotate(hinv, mk3(fp.x - cpos.x, fp.y - cpos.y, fp.z - cpos.z));
         st3(O.target_pos + 3 * s, fp);
-        *(float4 *)(O.target_rot + 4 * s) = mopt::qmul(hinv, fr);
+        *(float4 *)(O.target_rot + 4 * s) = qmul(hinv, fr);
     }
     __syncthreads();
     // stores: consecutive lanes write consecutive addresses; the quaternion outputs as one float4 per lane
@@ -172,7 +168,7 @@ __global__ void __launch_bounds__(64) k_msamp_window(const mopt::Model *Mp, mopt
 }
 
 // ---- heightfield kernel ---------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(HF_THREADS) k_msamp_hf(mopt::Clips K, Lib L, Cfg G, PlanD P, OutD O, int *status) {
+__global__ void __launch_bounds__(HF_THREADS) k_msamp_hf(ClipArrays K, Lib L, Cfg G, PlanD P, OutD O, int *status) {
     __shared__ float s_hf[GM * GP], s_mx[GM * GP], s_mn[GM * GP], s_tmp[GM * GP];
     extern __shared__ unsigned s_bits[];                    // [bit_words of the launch] >= the words of every clip's terrain
     const long long s = blockIdx.x;
@@ -190,7 +186,7 @@ __global__ void __launch_bounds__(HF_THREADS) k_msamp_hf(mopt::Clips K, Lib L, C
     for (int w = tid; w < words; w += HF_THREADS) s_bits[w] = 0u;
     __syncthreads();
     {
-        const long long n = meta.nframes, f0 = mopt::to_i64(rintf(t0 / G.timestep));
+        const long long n = meta.nframes, f0 = to_i64(rintf(t0 / G.timestep));
         const long long lo = f0 < 0 ? 0 : (f0 < n ? f0 : n), hi = f0 + G.T < lo ? lo : (f0 + G.T < n ? f0 + G.T : n);
         const long long e0 = L.mask_off[meta.start + lo], e1 = L.mask_off[meta.start + hi];
         for (long long e = e0 + tid; e < e1; e += HF_THREADS) {
@@ -275,7 +271,7 @@ __global__ void __launch_bounds__(HF_THREADS) k_msamp_hf(mopt::Clips K, Lib L, C
         __syncthreads();
         for (int k = tid; k < G.T; k += HF_THREADS) {
             const float *rp = O.root_pos + (s * G.T + k) * 3;
-            const long long i = mterr::grid_index(rp[0], G.gminx, G.dx, Gx), j = mterr::grid_index(rp[1], G.gminy, G.dx, Gy);
+            const long long i = grid_index(rp[0], G.gminx, G.dx, Gx), j = grid_index(rp[1], G.gminy, G.dx, Gy);
             O.floor_heights[s * G.T + k] = s_hf[i * GP + j];
         }
     }
@@ -285,7 +281,7 @@ __global__ void __launch_bounds__(HF_THREADS) k_msamp_hf(mopt::Clips K, Lib L, C
 // Philox4x32-10 keyed by the seed; counter = (sample index, block): blocks 0-4 the scalar draws, 8 + 2 b and 9 + 2 b box b.
 __device__ __forceinline__ int randint_incl(float u, int m) { const int v = (int)(u * (float)(m + 1)); return v < m ? v : m; }
 
-__global__ void k_msamp_draw(mopt::Clips K, Lib L, Cfg G, PlanD P, long long n, unsigned long long seed) {
+__global__ void k_msamp_draw(ClipArrays K, Lib L, Cfg G, PlanD P, long long n, unsigned long long seed) {
     const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
     float u[4], v[4];
@@ -354,15 +350,15 @@ __global__ void k_msamp_draw_noise(Cfg G, float *noise, long long n, unsigned lo
 struct ParcMotionSampler {
     struct Library {                      // what one parc_msamp_set_clips loads; a library is loaded when the handle holds one
         DeviceArena mem;
-        mopt::Clips K{};                  // the frames and terrains
+        ClipArrays K{};                  // the frames and terrains
         msamp::Lib L{};
         std::vector<int> clip_windows;    // num_frames - T per clip
         int bit_words = 0;                // words of the largest terrain's cell bitset
     };
     int device = 0;
-    mopt::Model host_model;
+    parc::CharTree host_model;
     DeviceArena mem;                      // create .. destroy: d_model, d_status, the times / grid tables of cfg
-    mopt::Model *d_model = nullptr;
+    parc::CharTree *d_model = nullptr;
     msamp::Cfg cfg{};
     std::unique_ptr<Library> lib;
     int *d_status = nullptr;
@@ -390,7 +386,8 @@ extern "C" int parc_msamp_create(const ParcMotionSamplerParams *p, ParcMotionSam
     if (p->max_num_boxes < 0 || p->max_num_boxes > PARC_MSAMP_MAX_BOXES || p->hf_max_maxpool_size < 0)
         return fail(PARC_ERR_INVALID, "msamp: max_num_boxes must be in [0, " + std::to_string(PARC_MSAMP_MAX_BOXES) + "], hf_max_maxpool_size >= 0");
     if (!(p->timestep > 0.f) || !(p->dx > 0.f)) return fail(PARC_ERR_INVALID, "msamp: sequence_fps and horizontal_scale must be > 0");
-    mopt::Model M;
+    parc::CharTree M;
+    model_zero(M);
     PARC_TRY(model_tree("msamp", cm, M));
     std::unique_ptr<ParcMotionSampler> h(new (std::nothrow) ParcMotionSampler());   // every failure below is a plain return
     if (!h) return fail(PARC_ERR_INVALID, "msamp: out of host memory");
@@ -470,7 +467,7 @@ extern "C" int parc_msamp_set_clips(ParcMotionSampler *h, const ParcMotionOptCli
     h->lib.reset();
     std::unique_ptr<ParcMotionSampler::Library> nl(new (std::nothrow) ParcMotionSampler::Library());
     if (!nl) return fail(PARC_ERR_INVALID, "msamp: out of host memory");
-    mopt::Clips &K = nl->K;
+    ClipArrays &K = nl->K;
     msamp::Lib &L = nl->L;
     DeviceArena &mem = nl->mem;
     PARC_TRY(clip_batch_upload(mem, K, c, cb, B));

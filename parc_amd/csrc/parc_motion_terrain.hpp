@@ -4,7 +4,7 @@
 // (terrain_util.py:1851-1947: per-frame cell masks, the lowest body point per cell, the augmentation bounds hf_maxmin), the clip
 // scores of mdm_path.compute_motion_loss (mdm_path.py:31-127: penetration and contact against the exact column-box SDF of the whole
 // terrain) and the jerk statistics of scripts/motion_tests/compute_losses.py:163-174.  All clips of a batch go through:
-//   k_mterr_fk      lane per frame: validity of the frame's inputs, FK (the optimiser's fk_frame) into a per-frame workspace
+//   k_mterr_fk      lane per frame: validity of the frame's inputs, FK (parc_char.hpp's fk_frame) into a per-frame workspace
 //   k_mterr_init    lane per cell:  lowest point = 99999.9999f (encoded), touched = 0
 //   k_mterr_points  block per frame, lane per sample point: world point, cell index (round half to even of a true division, clamped),
 //                   integer atomicMin of the encoded height + touched flag, exact ground / air SDF (ring-pruned or brute force);
@@ -28,14 +28,12 @@
 #include "../../include/parc_env.h"
 #include "parc_common.hpp"
 #include "parc_math.hpp"
+#include "parc_char.hpp"
+#include "parc_grid.hpp"
 #include "parc_clip_batch.hpp"
-#include "parc_motion_opt.hpp"       // mopt::Model / Clips, fk_frame, sd_box, to_i64
 
 namespace mterr {
 using namespace parc;
-using mopt::add3;
-using mopt::ld3;
-using mopt::ld4;
 
 constexpr int PT_THREADS = 256;
 constexpr int MAXP = PARC_MOPT_MAX_POINTS;
@@ -75,19 +73,12 @@ __host__ __device__ __forceinline__ float dec_f(int e) {
 
 __device__ __forceinline__ bool fin3(V3 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z); }
 
-// get_grid_index (terrain_util.py:146-152): torch.round (half to even) of a true fp32 division, .to(int64), clamp to [0, dims - 1]
-__device__ __forceinline__ long long grid_index(float p, float mn, float d, long long dim) {
-    long long i = mopt::to_i64(rintf((p - mn) / d));
-    i = i < dim - 1 ? i : dim - 1;
-    return i > 0 ? i : 0;
-}
-
 // the ground box [base_z, h] and the air box [h, top_z] of one cell (points_hf_sdf, terrain_util.py:1736-1794; sdBox geom_util.py:124)
 __device__ __forceinline__ float ground_sd(V3 x, float cx, float cy, float hx, float hy, float h, float base_z) {
-    return mopt::sd_box(mk3(x.x - cx, x.y - cy, x.z - (h + base_z) / 2.f), mk3(hx, hy, (h - base_z) / 2.f));
+    return sd_box(mk3(x.x - cx, x.y - cy, x.z - (h + base_z) / 2.f), mk3(hx, hy, (h - base_z) / 2.f));
 }
 __device__ __forceinline__ float air_sd(V3 x, float cx, float cy, float hx, float hy, float h, float top_z) {
-    return mopt::sd_box(mk3(x.x - cx, x.y - cy, x.z - (h + top_z) / 2.f), mk3(hx, hy, (top_z - h) / 2.f));
+    return sd_box(mk3(x.x - cx, x.y - cy, x.z - (h + top_z) / 2.f), mk3(hx, hy, (top_z - h) / 2.f));
 }
 
 // points_hf_sdf's cell centres: torch.linspace(0, (n - 1) dx, n) + min.  The CPU kernel computes step * i below the middle and
@@ -167,13 +158,13 @@ __device__ __forceinline__ void terrain_sdf(V3 x, const float *hf, long long X, 
 }
 
 // compute_motion_loss: base_z = torch.min(hf).item() - 10.0 (a Python float), used by fp32 tensor ops
-__device__ __forceinline__ float clip_base_z(const mopt::Clips &K, int c) { return (float)((double)K.hf_min[c] - 10.0); }
+__device__ __forceinline__ float clip_base_z(const FrameClips &K, int c) { return (float)((double)K.hf_min[c] - 10.0); }
 
 // ---- kernels ----------------------------------------------------------------------------------------------------------------
-__global__ void k_mterr_fk(const mopt::Model *Mp, mopt::Clips K, Work W) {
+__global__ void k_mterr_fk(const CharPoints *Mp, FrameClips K, Work W) {
     const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= K.F) return;
-    const mopt::Model &M = *Mp;
+    const CharPoints &M = *Mp;
     const int B = M.B;
     const V3 rp = ld3(K.src_root_pos + 3 * f);
     const Q4 rq = ld4(K.src_root_rot + 4 * f);
@@ -182,7 +173,7 @@ __global__ void k_mterr_fk(const mopt::Model *Mp, mopt::Clips K, Work W) {
     for (int k = 0; k < (B - 1) * 4; ++k) ok = ok && isfinite(jr[k]);
     for (int b = 0; b < B; ++b) ok = ok && isfinite(K.contacts[f * B + b]);
     // fk_frame reads joint j's rotation at base + 4 j for j >= 1 only
-    mopt::fk_frame(M, rp, rq, jr - 4, W.pos + f * B * 3, W.rot + f * B * 4);
+    fk_frame(M, rp, rq, jr - 4, W.pos + f * B * 3, W.rot + f * B * 4);
     W.valid[f] = ok ? 1 : 0;
 }
 
@@ -193,13 +184,13 @@ __global__ void k_mterr_init(long long ncell, Work W) {
     W.touched[i] = 0;
 }
 
-__global__ void __launch_bounds__(PT_THREADS) k_mterr_points(const mopt::Model *Mp, mopt::Clips K, Work W, Cfg G) {
+__global__ void __launch_bounds__(PT_THREADS) k_mterr_points(const CharPoints *Mp, FrameClips K, Work W, Cfg G) {
     __shared__ float s_x[MAXP][3], s_c[MAXP], s_pen[MAXP];
     __shared__ int s_key[MAXP];
     __shared__ float s_body[MAXB][4];
     __shared__ int s_bad, s_wave[PT_THREADS / 64];
     const long long f = blockIdx.x;
-    const mopt::Model &M = *Mp;
+    const CharPoints &M = *Mp;
     const int B = M.B, P = M.P, tid = threadIdx.x;
     const int c = K.frame_clip[f];
     const long long X = K.hf_dims[2 * c], Y = K.hf_dims[2 * c + 1], cell0 = K.hf_off[c];
@@ -297,7 +288,7 @@ __global__ void __launch_bounds__(PT_THREADS) k_mterr_points(const mopt::Model *
     }
 }
 
-__global__ void k_mterr_reduce(mopt::Clips K, Work W, int B) {
+__global__ void k_mterr_reduce(FrameClips K, Work W, int B) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= K.C) return;
     double pen = 0.0, con = 0.0, js = 0.0, jc = 0.0;
@@ -323,7 +314,7 @@ __global__ void k_mterr_reduce(mopt::Clips K, Work W, int B) {
 }
 
 // compute_hf_extra_vals (terrain_util.py:1920-1945): Python-float sums in double rounded to fp32, the jump test and bound in fp32
-__global__ void k_mterr_cells(mopt::Clips K, Work W, Cfg G, long long ncell) {
+__global__ void k_mterr_cells(FrameClips K, Work W, Cfg G, long long ncell) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= ncell) return;
     int lo = 0, hi = K.C - 1;                                 // the clip whose cells hold i (hf_off strictly increasing)
@@ -343,7 +334,7 @@ __global__ void k_mterr_cells(mopt::Clips K, Work W, Cfg G, long long ncell) {
     W.maxmin[2 * i + 1] = mn;
 }
 
-__global__ void k_mterr_gather(mopt::Clips K, Work W, int P, int *out) {
+__global__ void k_mterr_gather(FrameClips K, Work W, int P, int *out) {
     const long long f = blockIdx.x;
     const int c = K.frame_clip[f];
     const int Y = K.hf_dims[2 * c + 1], n = W.cnt[f];
@@ -356,10 +347,10 @@ __global__ void k_mterr_gather(mopt::Clips K, Work W, int P, int *out) {
 }
 
 // test entry: the raw ground / air SDF minima of every sample point of frames [f0, f0 + gridDim.x)
-__global__ void __launch_bounds__(PT_THREADS) k_mterr_point_sdf(const mopt::Model *Mp, mopt::Clips K, Work W, Cfg G, long long f0,
+__global__ void __launch_bounds__(PT_THREADS) k_mterr_point_sdf(const CharPoints *Mp, FrameClips K, Work W, Cfg G, long long f0,
                                                                  float *ground, float *air) {
     const long long fi = blockIdx.x, f = f0 + fi;
-    const mopt::Model &M = *Mp;
+    const CharPoints &M = *Mp;
     const int B = M.B, P = M.P;
     const int c = K.frame_clip[f];
     const long long X = K.hf_dims[2 * c], Y = K.hf_dims[2 * c + 1];
@@ -381,7 +372,7 @@ __global__ void __launch_bounds__(PT_THREADS) k_mterr_point_sdf(const mopt::Mode
 struct ParcMotionTerrain {
     struct Batch {                        // what one parc_mterr_set_clips loads; a batch is loaded when the handle holds one
         DeviceArena mem;
-        mopt::Clips K{};
+        FrameClips K{};
         mterr::Work W{};
         std::vector<int> counts;          // per-frame mask counts of the last run
         std::vector<long long> offsets;
@@ -389,9 +380,9 @@ struct ParcMotionTerrain {
         bool ran = false;
     };
     int device = 0;
-    mopt::Model host_model;
+    parc::CharPoints host_model;
     DeviceArena mem;                      // create .. destroy: d_model
-    mopt::Model *d_model = nullptr;
+    parc::CharPoints *d_model = nullptr;
     mterr::Cfg cfg{};
     std::unique_ptr<Batch> batch;
     DeviceArena inds;                     // d_inds alone: released and allocated anew when it must grow
@@ -413,9 +404,9 @@ extern "C" int parc_mterr_create(const ParcMotionTerrainParams *p, ParcMotionTer
     if (p->num_points < 1 || p->num_points > PARC_MOPT_MAX_POINTS || !p->points_host || !p->point_body_host)
         return fail(PARC_ERR_INVALID, "mterr: num_points must be in [1, 512] with points and point bodies given");
     if (p->sdf_mode != PARC_MTERR_SDF_PRUNED && p->sdf_mode != PARC_MTERR_SDF_BRUTE) return fail(PARC_ERR_INVALID, "mterr: unknown sdf_mode");
-    mopt::Model M;
+    parc::CharPoints M;
+    model_zero(M);
     PARC_TRY(model_tree("mterr", cm, M));
-    M.NP = PARC_MOPT_NP(cm.dof_size);
     PARC_TRY(model_points("mterr", M, p->num_points, p->points_host, p->point_body_host, p->contact_body_id));
     int sort_n = 1;
     while (sort_n < M.P) sort_n <<= 1;
@@ -448,12 +439,11 @@ extern "C" int parc_mterr_set_clips(ParcMotionTerrain *h, const ParcMotionOptCli
     h->batch.reset();
     std::unique_ptr<ParcMotionTerrain::Batch> nb(new (std::nothrow) ParcMotionTerrain::Batch());
     if (!nb) return fail(PARC_ERR_INVALID, "mterr: out of host memory");
-    mopt::Clips &K = nb->K;
+    FrameClips &K = nb->K;
     mterr::Work &W = nb->W;
     DeviceArena &mem = nb->mem;
     PARC_TRY(clip_batch_upload(mem, K, c, cb, B));
-    PARC_TRY(mem.alloc(K.frame_clip, F, cb.frame_clip.data()));
-    PARC_TRY(mem.alloc(K.hf_min, C, cb.hf_min.data()));
+    PARC_TRY(clip_batch_upload_frames(mem, K, cb));
     PARC_TRY(mem.alloc(W.pos, 3 * F * B));
     PARC_TRY(mem.alloc(W.rot, 4 * F * B));
     PARC_TRY(mem.alloc(W.valid, F));

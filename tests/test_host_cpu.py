@@ -381,6 +381,26 @@ def test_env_and_dynamics_units_do_not_include_each_other():
         assert h not in dyn, h
 
 
+def test_tool_headers_include_only_the_shared_headers():
+    """No motion tool is written against another tool's types: a tool header includes the C-ABI header and the shared headers only
+    (the path rollout also the generator, which it runs), and mopt:: is spelled in the optimiser alone.  Source text only."""
+    csrc = os.path.join(REPO, "parc_amd", "csrc")
+    tools = ["parc_motion_opt", "parc_motion_terrain", "parc_motion_sampler", "parc_motion_aug", "parc_mdm", "parc_mdm_path",
+             "parc_path_planner", "parc_terrain_gen", "parc_learner"]
+    shared = {"../../include/parc_env.h", "parc_common.hpp", "parc_math.hpp", "parc_char.hpp", "parc_grid.hpp", "parc_clip_batch.hpp",
+              "parc_motion_table.hpp"}
+    for t in tools:
+        with open(os.path.join(csrc, t + ".hpp")) as f:
+            inc = re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), re.M)
+        assert inc, t
+        extra = set(inc) - shared - ({"parc_mdm.hpp"} if t == "parc_mdm_path" else set())
+        assert not extra, (t, sorted(extra))
+    for h in sorted(os.listdir(csrc)):
+        if h.endswith(".hpp") and h != "parc_motion_opt.hpp":
+            with open(os.path.join(csrc, h)) as f:
+                assert "mopt::" not in f.read(), h
+
+
 CSRC_HEADERS = sorted(f for f in os.listdir(os.path.join(REPO, "parc_amd", "csrc")) if f.endswith(".hpp"))
 
 
