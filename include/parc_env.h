@@ -67,9 +67,10 @@ typedef struct {
  * (ig_char_env.py:100-143, humanoid.xml) and the sim block of dm_env_default.yaml:175-186. */
 /* ControlMode of the reference (ig_char_env.py:21-26).  pd: the action is the PD position target (exp-map per spherical joint), clipped to the action
  * bounds (implicit drive, PhysX DOF_MODE_POS).  vel: velocity target, drive force = damping * (action - dof_vel) (DOF_MODE_VEL, stiffness 0).  torque: the
- * clipped action is the joint torque (DOF_MODE_EFFORT).  pd_exp / pd_1d: the explicit PD torque of ig_char_env.py:399-421, computed once per control
- * step from the state at its start, target = the action as given (not clipped, :500-503), limited to the motor efforts; pd_1d needs a character
- * whose joints all have one dof (the reference asserts it, :246-250). */
+ * clipped action is the joint torque (DOF_MODE_EFFORT).  pd_exp / pd_1d: the explicit PD torque of ig_char_env.py:399-421, target = the action as given
+ * (not clipped, :500-503), limited to the motor efforts; pd_1d needs a character whose joints all have one dof (the reference asserts it, :246-250).
+ * This library forms that torque once per control step, from the state at its start, and holds it; the reference forms it again at every sim step
+ * (_step_sim -> _apply_forces, :369-397).  A known deviation: ADVICE.md item 1; the one place that decides it is joint_control_* in parc_dynamics.hpp. */
 #define PARC_CTRL_PD 0
 #define PARC_CTRL_VEL 1
 #define PARC_CTRL_TORQUE 2

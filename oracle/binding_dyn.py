@@ -23,6 +23,55 @@ def _p(a):
     return a.ctypes.data_as(f32p)
 
 
+class JointModel:
+    """The joint model of parc_dynamics.hpp (control law of a joint, drive of one dof) as the three solvers call it; `ctrl` = PARC_CTRL_*.
+    Gains are given per joint as 3-vectors (a hinge: scalars, its dof 0)."""
+
+    def __init__(self):
+        self.lib = C.CDLL(build())
+
+    @staticmethod
+    def _gains(kp, kd, arm, eff, lo, hi, act_lo, act_hi):
+        g = np.zeros((8, 3), np.float32)
+        for r, v in enumerate((kp, kd, arm, eff, lo, hi, act_lo, act_hi)):
+            g[r, :np.size(v)] = v
+        return g
+
+    def dof_drive(self, ctrl, kp, kd, arm, eff, lo, hi, lim_k, lim_d, dt, e, cur, qd):
+        """-> (t, aug) of one dof in one substep; e = the pose error (pd) or the feed-forward torque."""
+        out = np.zeros(2, np.float32)
+        self.lib.orc_dof_drive(C.c_int(ctrl), _p(self._gains(kp, kd, arm, eff, lo, hi, 0, 0)), _p(np.array([lim_k, lim_d], np.float32)), C.c_int(0),
+                               C.c_float(dt), C.c_float(e), C.c_float(cur), C.c_float(qd), _p(out))
+        return out[0], out[1]
+
+    def _control(self, fn, nout, ctrl, kp, kd, eff, act_lo, act_hi, pos, vel, a):
+        out = np.zeros(nout, np.float32)
+        rows = [np.concatenate([np.full(2, 99.0, np.float32), np.atleast_1d(np.asarray(v, np.float32))]) for v in (pos, vel, a)]   # the joint's dofs at di = 2
+        fn(C.c_int(ctrl), _p(self._gains(kp, kd, 0, eff, 0, 0, act_lo, act_hi)), _p(rows[0]), _p(rows[1]), _p(rows[2]), C.c_int(2), _p(out))
+        return out
+
+    def control_hinge(self, ctrl, kp, kd, eff, act_lo, act_hi, pos, vel, a):
+        """-> (hang, qd, thang); thang = the clipped target (pd) or the feed-forward torque."""
+        out = self._control(self.lib.orc_joint_control_hinge, 3, ctrl, kp, kd, eff, act_lo, act_hi, pos, vel, a)
+        return out[0], out[1], out[2]
+
+    def control_spherical(self, ctrl, kp, kd, eff, act_lo, act_hi, pos, vel, a):
+        """3-vectors in -> (jq[4], qd[3], tq[4]); tq = the target rotation (pd) or xyz = the feed-forward torque."""
+        out = self._control(self.lib.orc_joint_control_spherical, 11, ctrl, kp, kd, eff, act_lo, act_hi, pos, vel, a)
+        return out[:4], out[4:7], out[7:]
+
+    def qexp(self, v):
+        out = np.zeros(4, np.float32)
+        self.lib.orc_qexp(_p(np.ascontiguousarray(v, np.float32)), _p(out))
+        return out
+
+    def rot_diff(self, frm, to):
+        """Rotation from the pose `frm` to the pose `to` (exp maps) as an exp map."""
+        out = np.zeros(3, np.float32)
+        self.lib.orc_rot_diff(_p(np.ascontiguousarray(frm, np.float32)), _p(np.ascontiguousarray(to, np.float32)), _p(out))
+        return out
+
+
 class DynOracle:
     def __init__(self, cfg_struct):
         """cfg_struct: parc_amd.lib.ParcEnvConfig (model + dynamics + action bounds)."""

@@ -84,6 +84,38 @@ int orc_segment_edge_point(const float *hf, int X, int Y, float min_x, float min
     return w > 0.f ? 1 : 0;
 }
 
+// the joint model (parc_dynamics.hpp, THE JOINT MODEL) as the three solvers call it, on one joint given by value: gains = 8 rows (kp, kd, arm,
+// eff, lo, hi, act_lo, act_hi) of 3 dofs each (a hinge uses dof 0); scalars = (lim_k, lim_d)
+static JointGains gains_of(const float *g) { JointGains G = {g, g + 3, g + 6, g + 9, g + 12, g + 15, g + 18, g + 21}; return G; }
+static DynModel scalars_of(int ctrl, const float *sc) { DynModel M; memset(&M, 0, sizeof(M)); M.ctrl = ctrl; M.lim_k = sc[0]; M.lim_d = sc[1]; return M; }
+// the drive of dof q in a substep -> (t, aug)
+void orc_dof_drive(int ctrl, const float *gains, const float *scalars, int q, float dt, float e, float cur, float qd, float *out2) {
+    const DynModel M = scalars_of(ctrl, scalars);
+    dof_drive(M, gains_of(gains), q, dt, e, cur, qd, out2[0], out2[1]);
+}
+// the control law of a hinge -> (hang, qd, thang) and of a spherical joint -> (jq[4], qd[3], tq[4]) from the dof rows / the action at di
+void orc_joint_control_hinge(int ctrl, const float *gains, const float *dp, const float *dv, const float *ac, int di, float *out3) {
+    const float sc[2] = {0.f, 0.f};
+    const DynModel M = scalars_of(ctrl, sc);
+    joint_control_hinge(M, gains_of(gains), dp, dv, ac, di, out3[0], out3[1], out3[2]);
+}
+void orc_joint_control_spherical(int ctrl, const float *gains, const float *dp, const float *dv, const float *ac, int di, float *out11) {
+    const float sc[2] = {0.f, 0.f};
+    const DynModel M = scalars_of(ctrl, sc);
+    q4 jq, tq; v3 qd;
+    tq.x = 0.f; tq.y = 0.f; tq.z = 0.f; tq.w = 1.f;
+    joint_control_spherical(M, gains_of(gains), dp, dv, ac, di, jq, qd, tq);
+    const float o[11] = {jq.x, jq.y, jq.z, jq.w, qd.x, qd.y, qd.z, tq.x, tq.y, tq.z, tq.w};
+    memcpy(out11, o, sizeof(o));
+}
+// the header's quaternion primitives, for the tests that state a formula around them: exp map -> quaternion, and the rotation from the
+// pose `from` to the pose `to` (both exp maps) as an exp map
+void orc_qexp(const float *v, float *q_out) { const q4 q = qexp(mk(v[0], v[1], v[2])); q_out[0] = q.x; q_out[1] = q.y; q_out[2] = q.z; q_out[3] = q.w; }
+void orc_rot_diff(const float *from, const float *to, float *out3) {
+    const v3 d = qlog(qmul(qconj(qexp(mk(from[0], from[1], from[2]))), qexp(mk(to[0], to[1], to[2]))));
+    out3[0] = d.x; out3[1] = d.y; out3[2] = d.z;
+}
+
 // state arrays are [n][...] row-major like the env tensors
 void orc_dyn_step(void *m, const float *hf, int X, int Y, float min_x, float min_y, float dx, float dy, int n, float *root_pos,
                   float *root_rot, float *root_vel, float *root_ang_vel, float *dof_pos, float *dof_vel, float *contact_force,

@@ -110,7 +110,7 @@ struct DynModel {
     float max_ang_vel, ang_damping;
     float total_mass;
     int ctrl;                    // control mode (PARC_CTRL_*, ig_char_env.py:21-26): 0 = pd, the implicit drive towards the action's pose; the others
-                                 // turn the action into a feed-forward joint torque that is constant over the control step (ctrl_ff / drive_ff below)
+                                 // turn the action into a feed-forward joint torque that is constant over the control step (ctrl_ff / dof_drive below)
     int truncated;               // collision points / segments / mass parts that did not fit the fixed tables (DYN_MAXC / DYN_MAXS / 64): the model
                                  // would depend on the geom order -- parc_env_create refuses such a model
     float ext_acc[2];            // TEST HOOK of the host build (oracle/dyn_oracle.cpp): uniform horizontal acceleration, i.e. a tilted gravity
@@ -453,15 +453,21 @@ struct DynState { // pointers to this env's rows
     float *body_pos;      // [B][3] or null
 };
 
+// ================================================================ THE JOINT MODEL
+// What a joint is -- control law, drive of one dof with its limit spring, integration, the dof rows -- stated once for the three solvers
+// (dyn_control_step below = the host build and k_dynamics, k_dynamics_coop, k_dynamics_wave / k_dynamics_wave_ff).  How they decompose
+// the character and eliminate the joints is theirs; this section is not.  dyn_control_step and k_dynamics_coop call every function
+// of it; k_dynamics_wave calls the joint integration and keeps the other statements in its own text (parc_dynamics_wave.hpp, at
+// wv_load_joint, says why) -- a change here is repeated there.
 PARC_HD float clampf(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
-// Control modes other than pd (ig_char_env.py:488-506, 374-421).  One dof's FEED-FORWARD torque, formed once per control step:
+// Control modes other than pd (ig_char_env.py:488-506, 374-421).  One dof's FEED-FORWARD torque:
 //   vel     velocity target: PhysX's drive force is damping * (target - dof_vel) with the stiffness set to 0 (:122-123): damping * target is the
 //           constant part, -damping * dof_vel stays in the (implicit) drive;
 //   torque  the action clipped to its bounds (= +- the motor efforts, :361-368) is the joint torque (:378-380, 498-499);
-//   pd_exp, pd_1d   explicit PD torque from the state at the start of the control step (_apply_forces runs once per _step_sim, :374-397); `diff` is
-//           the rotation from the joint's pose to the target's as an exponential map (pd_exp, compute_dof_vel with dt = 1, :404-409) or the plain
-//           difference (pd_1d, :419); the target is the action AS GIVEN (:500-503 store `actions`, not the clipped copy); limited to the motor efforts.
+//   pd_exp, pd_1d   explicit PD torque; `diff` is the rotation from the joint's pose to the target's as an exponential map (pd_exp,
+//           compute_dof_vel with dt = 1, :404-409) or the plain difference (pd_1d, :419); the target is the action AS GIVEN (:500-503 store
+//           `actions`, not the clipped copy); limited to the motor efforts.
 PARC_HD float ctrl_ff(int ctrl, float kp, float kd, float eff, float act_lo, float act_hi, float a, float diff, float qd0) {
     if (ctrl == PARC_CTRL_VEL) return kd * clampf(a, act_lo, act_hi);
     if (ctrl == PARC_CTRL_TORQUE) return clampf(a, act_lo, act_hi);
@@ -473,12 +479,103 @@ PARC_HD float ctrl_hinge_diff(int ctrl, float a, float hang) {
     if (ctrl == PARC_CTRL_PD_EXP) d -= 6.28318530717958648f * DYN_RINT(d * 0.159154943091895336f);
     return d;
 }
-// ... and the substep's drive torque / joint-space augmentation with it (the pd mode's are kp err - (kd + dt kp) qd and arm + dt kd + dt^2 kp)
+
+// A joint's rows of the per-dof tables, each pointer at the joint's first dof (DynModel's arrays at dof_idx; k_dynamics_coop's copy of them
+// in LDS): a view, read where a value is used, so that a solver loads what its control mode needs and nothing else.
+struct JointGains { const float *kp, *kd, *arm, *eff, *lo, *hi, *act_lo, *act_hi; };
+PARC_HD JointGains joint_gains(const DynModel &M, int di) {
+    JointGains G;
+    G.kp = M.kp + di; G.kd = M.kd + di; G.arm = M.arm + di; G.eff = M.eff + di; G.lo = M.lo + di; G.hi = M.hi + di; G.act_lo = M.act_lo + di; G.act_hi = M.act_hi + di;
+    return G;
+}
+
+// (1) CONTROL LAW of one joint, from its dof rows (dp, dv at di) and its action (ac at di): the joint's state (jq / hang, qd) and what it
+// is driven with -- pd: the target pose (tq / thang, the action clipped to its bounds, ig_char_env.py:488-490); the other modes: the
+// feed-forward torque (ctrl_ff) in the same place, tq.xyz / thang (tq.w is left as the caller set it).  M = the model's scalars.
+// THE TORQUE IS FORMED HERE, ONCE PER CONTROL STEP, from the state at its start, and held over all its substeps.  That is a known
+// deviation from the reference, recorded as ADVICE.md item 1: the reference's _step_sim calls _apply_forces at every sim step
+// (ig_char_env.py:369-397, sim_steps of them per control step), so its pd_exp / pd_1d torque follows the state.  vel and torque are not
+// affected (the action is constant).
+PARC_HD void joint_control_spherical(const DynModel &M, const JointGains &G, const float *dp, const float *dv, const float *ac, int di, q4 &jq, v3 &qd, q4 &tq) {
+    jq = qexp(mk(dp[di], dp[di + 1], dp[di + 2]));
+    qd = mk(dv[di], dv[di + 1], dv[di + 2]);
+    if (M.ctrl == PARC_CTRL_PD) {
+        tq = qexp(mk(clampf(ac[di], G.act_lo[0], G.act_hi[0]), clampf(ac[di + 1], G.act_lo[1], G.act_hi[1]), clampf(ac[di + 2], G.act_lo[2], G.act_hi[2])));
+    } else {
+        v3 diff = mk(0.f, 0.f, 0.f);
+        if (M.ctrl >= PARC_CTRL_PD_EXP) diff = qlog(qmul(qconj(jq), qexp(mk(ac[di], ac[di + 1], ac[di + 2]))));
+        tq.x = ctrl_ff(M.ctrl, G.kp[0], G.kd[0], G.eff[0], G.act_lo[0], G.act_hi[0], ac[di], diff.x, qd.x);
+        tq.y = ctrl_ff(M.ctrl, G.kp[1], G.kd[1], G.eff[1], G.act_lo[1], G.act_hi[1], ac[di + 1], diff.y, qd.y);
+        tq.z = ctrl_ff(M.ctrl, G.kp[2], G.kd[2], G.eff[2], G.act_lo[2], G.act_hi[2], ac[di + 2], diff.z, qd.z);
+    }
+}
+PARC_HD void joint_control_hinge(const DynModel &M, const JointGains &G, const float *dp, const float *dv, const float *ac, int di, float &hang, float &qd, float &thang) {
+    hang = dp[di]; qd = dv[di];
+    if (M.ctrl == PARC_CTRL_PD) thang = clampf(ac[di], G.act_lo[0], G.act_hi[0]);
+    else thang = ctrl_ff(M.ctrl, G.kp[0], G.kd[0], G.eff[0], G.act_lo[0], G.act_hi[0], ac[di], ctrl_hinge_diff(M.ctrl, ac[di], hang), qd);
+}
+
+// the substep's drive torque / joint-space augmentation of the control modes other than pd: only vel keeps a damping, implicit
 PARC_HD void drive_ff(int ctrl, float kd, float arm, float eff, float dt, float ff, float qd, float &t, float &aug) {
     const float kdv = ctrl == PARC_CTRL_VEL ? kd : 0.f;
     t = clampf(ff - kdv * qd, -eff, eff);
     aug = arm + dt * kdv;
 }
+// (2) DRIVE of dof q of a joint in one substep: torque t and joint-space augmentation aug (added to the diagonal of D).  pd: the implicit
+// drive, e = the pose error, t = kp e - (kd + dt kp) qd limited to the motor effort, aug = arm + dt kd + dt^2 kp; the other modes: e = the
+// feed-forward torque, and only vel keeps a damping, implicit.  Then the limit spring where the coordinate `cur` is outside [lo, hi]: it
+// adds lim_k (lim - cur) - lim_d qd to the torque, after the motor limit, and dt lim_d + dt^2 lim_k to the augmentation.
+PARC_HD void dof_drive(const DynModel &M, const JointGains &G, int q, float dt, float e, float cur, float qd, float &t_out, float &aug) {
+    float t = G.kp[q] * e - (G.kd[q] + dt * G.kp[q]) * qd;
+    t = clampf(t, -G.eff[q], G.eff[q]);
+    aug = G.arm[q] + dt * G.kd[q] + dt * dt * G.kp[q];
+    if (M.ctrl != PARC_CTRL_PD) drive_ff(M.ctrl, G.kd[q], G.arm[q], G.eff[q], dt, e, qd, t, aug);
+    if (cur < G.lo[q]) { t += M.lim_k * (G.lo[q] - cur) - M.lim_d * qd; aug += dt * M.lim_d + dt * dt * M.lim_k; }
+    else if (cur > G.hi[q]) { t += M.lim_k * (G.hi[q] - cur) - M.lim_d * qd; aug += dt * M.lim_d + dt * dt * M.lim_k; }
+    t_out = t;
+}
+// ... of a spherical joint's three dofs (error and coordinate in the child frame, like _calc_pd_exp_torque ig_char_env.py:536-548) and of a hinge
+PARC_HD void joint_drive_spherical(const DynModel &M, const JointGains &G, float dt, const q4 &jq, const q4 &tq, const v3 &qd, float *tau, float *aug) {
+    const v3 err = M.ctrl == PARC_CTRL_PD ? qlog(qmul(qconj(jq), tq)) : mk(tq.x, tq.y, tq.z); // (not pd: the feed-forward torque)
+    const v3 cur = qlog(jq);
+    const float e3[3] = {err.x, err.y, err.z}, c3[3] = {cur.x, cur.y, cur.z}, q3[3] = {qd.x, qd.y, qd.z};
+    PARC_UNROLL
+    for (int q = 0; q < 3; ++q) dof_drive(M, G, q, dt, e3[q], c3[q], q3[q], tau[q], aug[q]);
+}
+PARC_HD void joint_drive_hinge(const DynModel &M, const JointGains &G, float dt, float hang, float thang, float qd, float &t, float &aug) {
+    dof_drive(M, G, 0, dt, M.ctrl == PARC_CTRL_PD ? thang - hang : thang, hang, qd, t, aug);
+}
+
+// (3) INTEGRATE one substep: semi-implicit Euler, the new velocity (limited to max_ang_vel) advances the pose.  A spherical joint's
+// velocity is in the child frame.  The root: classical acceleration of its origin, angular damping, the max_ang_vel cap, world-frame
+// angular velocity.  (k_dynamics_wave keeps its own root lines: it forms the two reciprocals and the square root with the
+// hardware approximations, DYN_RCP / DYN_SQRT, where this statement divides and calls sqrtf -- not the same floats on the device.)
+PARC_HD void joint_integrate_spherical(float dt, float max_vel, v3 qdd, q4 &jq, v3 &qd) {
+    qd = mk(clampf(qd.x + dt * qdd.x, -max_vel, max_vel), clampf(qd.y + dt * qdd.y, -max_vel, max_vel), clampf(qd.z + dt * qdd.z, -max_vel, max_vel));
+    jq = qnormalize(qmul(jq, qexp(dt * qd)));
+}
+PARC_HD void joint_integrate_hinge(float dt, float max_vel, float qdd, float &hang, float &qd) {
+    qd = clampf(qd + dt * qdd, -max_vel, max_vel);
+    hang += dt * qd;
+}
+PARC_HD void root_integrate(float dt, float ang_damping, float max_ang_vel, v3 alpha, v3 aO, v3 &rp, q4 &rq, v3 &rv, v3 &rw) {
+    const v3 rv_new = rv + dt * (aO + cross(rw, rv));
+    v3 rw_new = rw + dt * alpha;
+    rw_new = (1.f / (1.f + dt * ang_damping)) * rw_new;
+    const float wm = sqrtf(dot(rw_new, rw_new));
+    if (wm > max_ang_vel) rw_new = (max_ang_vel / wm) * rw_new;
+    rv = rv_new; rw = rw_new;
+    rp = rp + dt * rv;
+    rq = qnormalize(qmul(qexp(dt * rw), rq));
+}
+
+// (4) STORE a joint's dof rows (dp, dv at di); returns the exponential map of a spherical joint for who needs it again
+PARC_HD v3 joint_store_spherical(const q4 &jq, const v3 &qd, float *dp, float *dv, int di) {
+    const v3 ex = qlog(jq);
+    dp[di] = ex.x; dp[di + 1] = ex.y; dp[di + 2] = ex.z; dv[di] = qd.x; dv[di + 1] = qd.y; dv[di + 2] = qd.z;
+    return ex;
+}
+PARC_HD void joint_store_hinge(float hang, float qd, float *dp, float *dv, int di) { dp[di] = hang; dv[di] = qd; }
 
 // Advance one env by one CONTROL step (nsub solver substeps).  `action` = PD targets before clipping
 // (ig_char_env.py:488-490); env_off = origin of the env in the global terrain frame.
@@ -493,32 +590,14 @@ PARC_HD void dyn_control_step(const DynModel &M, const DynTerrain &T, const DynS
     v3 rw = mk(S.root_ang_vel[0], S.root_ang_vel[1], S.root_ang_vel[2]);
     q4 jq[DYN_MAXB];      // joint rotation parent->child (spherical / hinge)
     float hang[DYN_MAXB]; // hinge angle
-    float qd[DYN_MAXD];
-    q4 tq[DYN_MAXB];      // PD target rotation
+    v3 qd[DYN_MAXB];      // joint velocity (spherical: child frame; hinge: .x)
+    q4 tq[DYN_MAXB];      // pd: target rotation; the other control modes: .xyz = the feed-forward torque (joint_control_*)
     float thang[DYN_MAXB];
-    for (int d = 0; d < M.D; ++d) qd[d] = S.dof_vel[d];
-    float ff[DYN_MAXD];   // feed-forward joint torques of the control modes other than pd
-    for (int d = 0; d < DYN_MAXD; ++d) ff[d] = 0.f;
     for (int i = 1; i < B; ++i) {
         const int di = M.dof_idx[i];
-        jq[i].x = 0.f; jq[i].y = 0.f; jq[i].z = 0.f; jq[i].w = 1.f; hang[i] = 0.f; tq[i] = jq[i]; thang[i] = 0.f;
-        if (M.jtype[i] == DJ_SPHERICAL) {
-            jq[i] = qexp(mk(S.dof_pos[di], S.dof_pos[di + 1], S.dof_pos[di + 2]));
-            if (M.ctrl == PARC_CTRL_PD) {
-                tq[i] = qexp(mk(clampf(action[di], M.act_lo[di], M.act_hi[di]), clampf(action[di + 1], M.act_lo[di + 1], M.act_hi[di + 1]),
-                                clampf(action[di + 2], M.act_lo[di + 2], M.act_hi[di + 2])));
-            } else {
-                v3 diff = mk(0.f, 0.f, 0.f);
-                if (M.ctrl >= PARC_CTRL_PD_EXP) diff = qlog(qmul(qconj(jq[i]), qexp(mk(action[di], action[di + 1], action[di + 2]))));
-                const float d3[3] = {diff.x, diff.y, diff.z};
-                for (int k = 0; k < 3; ++k)
-                    ff[di + k] = ctrl_ff(M.ctrl, M.kp[di + k], M.kd[di + k], M.eff[di + k], M.act_lo[di + k], M.act_hi[di + k], action[di + k], d3[k], qd[di + k]);
-            }
-        } else if (M.jtype[i] == DJ_HINGE) {
-            hang[i] = S.dof_pos[di];
-            if (M.ctrl == PARC_CTRL_PD) thang[i] = clampf(action[di], M.act_lo[di], M.act_hi[di]);
-            else ff[di] = ctrl_ff(M.ctrl, M.kp[di], M.kd[di], M.eff[di], M.act_lo[di], M.act_hi[di], action[di], ctrl_hinge_diff(M.ctrl, action[di], hang[i]), qd[di]);
-        }
+        jq[i].x = 0.f; jq[i].y = 0.f; jq[i].z = 0.f; jq[i].w = 1.f; hang[i] = 0.f; tq[i] = jq[i]; thang[i] = 0.f; qd[i] = mk(0.f, 0.f, 0.f);
+        if (M.jtype[i] == DJ_SPHERICAL) joint_control_spherical(M, joint_gains(M, di), S.dof_pos, S.dof_vel, action, di, jq[i], qd[i], tq[i]);
+        else if (M.jtype[i] == DJ_HINGE) joint_control_hinge(M, joint_gains(M, di), S.dof_pos, S.dof_vel, action, di, hang[i], qd[i].x, thang[i]);
     }
     Patch patch;
     load_patch(T, rp.x + env_off[0], rp.y + env_off[1], patch);
@@ -533,7 +612,7 @@ PARC_HD void dyn_control_step(const DynModel &M, const DynTerrain &T, const DynS
         vel[0] = s6mk(rw, rv); // reference point O is the root origin: v_O = root linear velocity
         cJ[0] = s6zero();
         for (int i = 1; i < B; ++i) {
-            const int p = M.parent[i], di = M.dof_idx[i];
+            const int p = M.parent[i];
             r[i] = r[p] + mulv(R[p], mk(M.lt[i][0], M.lt[i][1], M.lt[i][2]));
             q4 lq; lq.x = M.lr[i][0]; lq.y = M.lr[i][1]; lq.z = M.lr[i][2]; lq.w = M.lr[i][3];
             q4 jr = jq[i];
@@ -541,8 +620,8 @@ PARC_HD void dyn_control_step(const DynModel &M, const DynTerrain &T, const DynS
             bq[i] = qnormalize(qmul(bq[p], qmul(lq, jr)));
             R[i] = qmat(bq[i]);
             v3 wj = mk(0.f, 0.f, 0.f);
-            if (M.jtype[i] == DJ_SPHERICAL) wj = mulv(R[i], mk(qd[di], qd[di + 1], qd[di + 2]));
-            else if (M.jtype[i] == DJ_HINGE) wj = qd[di] * mulv(R[i], mk(M.axis[i][0], M.axis[i][1], M.axis[i][2]));
+            if (M.jtype[i] == DJ_SPHERICAL) wj = mulv(R[i], qd[i]);
+            else if (M.jtype[i] == DJ_HINGE) wj = qd[i].x * mulv(R[i], mk(M.axis[i][0], M.axis[i][1], M.axis[i][2]));
             s6 vJ = s6mk(wj, cross(r[i], wj));
             vel[i] = vel[p] + vJ;
             cJ[i] = crm(vel[i], vJ);
@@ -632,28 +711,11 @@ PARC_HD void dyn_control_step(const DynModel &M, const DynTerrain &T, const DynS
                     v3 a = mk(R[i].m[0][k], R[i].m[1][k], R[i].m[2][k]);
                     Scol[i][k] = s6mk(a, cross(r[i], a));
                 }
-                v3 err = qlog(qmul(qconj(jq[i]), tq[i])); // child frame, like _calc_pd_exp_torque ig_char_env.py:536-548
-                v3 cur = qlog(jq[i]);
-                const float e3[3] = {err.x, err.y, err.z}, c3[3] = {cur.x, cur.y, cur.z};
-                for (int k = 0; k < 3; ++k) {
-                    float t = M.kp[di + k] * e3[k] - (M.kd[di + k] + dt * M.kp[di + k]) * qd[di + k];
-                    t = clampf(t, -M.eff[di + k], M.eff[di + k]);
-                    aug[k] = M.arm[di + k] + dt * M.kd[di + k] + dt * dt * M.kp[di + k];
-                    if (M.ctrl != PARC_CTRL_PD) drive_ff(M.ctrl, M.kd[di + k], M.arm[di + k], M.eff[di + k], dt, ff[di + k], qd[di + k], t, aug[k]);
-                    if (c3[k] < M.lo[di + k]) { t += M.lim_k * (M.lo[di + k] - c3[k]) - M.lim_d * qd[di + k]; aug[k] += dt * M.lim_d + dt * dt * M.lim_k; }
-                    else if (c3[k] > M.hi[di + k]) { t += M.lim_k * (M.hi[di + k] - c3[k]) - M.lim_d * qd[di + k]; aug[k] += dt * M.lim_d + dt * dt * M.lim_k; }
-                    tau[k] = t;
-                }
+                joint_drive_spherical(M, joint_gains(M, di), dt, jq[i], tq[i], qd[i], tau, aug);
             } else {
                 v3 a = mulv(R[i], mk(M.axis[i][0], M.axis[i][1], M.axis[i][2]));
                 Scol[i][0] = s6mk(a, cross(r[i], a));
-                float t = M.kp[di] * (thang[i] - hang[i]) - (M.kd[di] + dt * M.kp[di]) * qd[di];
-                t = clampf(t, -M.eff[di], M.eff[di]);
-                aug[0] = M.arm[di] + dt * M.kd[di] + dt * dt * M.kp[di];
-                if (M.ctrl != PARC_CTRL_PD) drive_ff(M.ctrl, M.kd[di], M.arm[di], M.eff[di], dt, ff[di], qd[di], t, aug[0]);
-                if (hang[i] < M.lo[di]) { t += M.lim_k * (M.lo[di] - hang[i]) - M.lim_d * qd[di]; aug[0] += dt * M.lim_d + dt * dt * M.lim_k; }
-                else if (hang[i] > M.hi[di]) { t += M.lim_k * (M.hi[di] - hang[i]) - M.lim_d * qd[di]; aug[0] += dt * M.lim_d + dt * dt * M.lim_k; }
-                tau[0] = t;
+                joint_drive_hinge(M, joint_gains(M, di), dt, hang[i], thang[i], qd[i].x, tau[0], aug[0]);
             }
             float Dm[3][3] = {{1.f, 0.f, 0.f}, {0.f, 1.f, 0.f}, {0.f, 0.f, 1.f}};
             for (int k = 0; k < nd; ++k) {
@@ -724,9 +786,9 @@ PARC_HD void dyn_control_step(const DynModel &M, const DynTerrain &T, const DynS
             for (int a = 0; a < 6; ++a) acc[0].a[a] = xs[a];
         }
         // ---- outward pass: joint accelerations ------------------------------------------------------------------
-        float qdd[DYN_MAXD];
+        v3 qdd[DYN_MAXB];
         for (int i = 1; i < B; ++i) {
-            const int p = M.parent[i], di = M.dof_idx[i];
+            const int p = M.parent[i];
             const int nd = M.jtype[i] == DJ_SPHERICAL ? 3 : (M.jtype[i] == DJ_HINGE ? 1 : 0);
             s6 ap = acc[p] + cJ[i];
             if (nd == 0) { acc[i] = ap; continue; }
@@ -744,32 +806,17 @@ PARC_HD void dyn_control_step(const DynModel &M, const DynTerrain &T, const DynS
                 q3[2] = Dinv[i][4] * rhs[0] + Dinv[i][5] * rhs[1] + Dinv[i][2] * rhs[2];
             }
             acc[i] = ap;
-            for (int k = 0; k < nd; ++k) {
-                qdd[di + k] = q3[k];
+            qdd[i] = mk(q3[0], q3[1], q3[2]);
+            for (int k = 0; k < nd; ++k)
                 for (int a = 0; a < 6; ++a) acc[i].a[a] += Scol[i][k].a[a] * q3[k];
-            }
         }
         // ---- implicit correction of the reported contact force: f_new = f_old - dt B a_point ---------------------
         // (cheap approximation: scale by the change of the normal velocity is skipped; the explicit force is reported)
         // ---- integrate ------------------------------------------------------------------------------------------
-        v3 alpha = s6ang(acc[0]), aO = s6lin(acc[0]);
-        v3 rv_new = rv + dt * (aO + cross(rw, rv)); // classical acceleration of the root origin
-        v3 rw_new = rw + dt * alpha;
-        rw_new = (1.f / (1.f + dt * M.ang_damping)) * rw_new;
-        float wm = sqrtf(dot(rw_new, rw_new));
-        if (wm > M.max_ang_vel) rw_new = (M.max_ang_vel / wm) * rw_new;
-        rv = rv_new; rw = rw_new;
-        rp = rp + dt * rv;
-        rq = qnormalize(qmul(qexp(dt * rw), rq)); // world-frame angular velocity
+        root_integrate(dt, M.ang_damping, M.max_ang_vel, s6ang(acc[0]), s6lin(acc[0]), rp, rq, rv, rw);
         for (int i = 1; i < B; ++i) {
-            const int di = M.dof_idx[i];
-            if (M.jtype[i] == DJ_SPHERICAL) {
-                for (int k = 0; k < 3; ++k) qd[di + k] = clampf(qd[di + k] + dt * qdd[di + k], -M.max_ang_vel, M.max_ang_vel);
-                jq[i] = qnormalize(qmul(jq[i], qexp(dt * mk(qd[di], qd[di + 1], qd[di + 2])))); // child-frame velocity
-            } else if (M.jtype[i] == DJ_HINGE) {
-                qd[di] = clampf(qd[di] + dt * qdd[di], -M.max_ang_vel, M.max_ang_vel);
-                hang[i] += dt * qd[di];
-            }
+            if (M.jtype[i] == DJ_SPHERICAL) joint_integrate_spherical(dt, M.max_ang_vel, qdd[i], jq[i], qd[i]);
+            else if (M.jtype[i] == DJ_HINGE) joint_integrate_hinge(dt, M.max_ang_vel, qdd[i].x, hang[i], qd[i].x);
         }
     }
     // ---- write back ---------------------------------------------------------------------------------------------
@@ -779,14 +826,8 @@ PARC_HD void dyn_control_step(const DynModel &M, const DynTerrain &T, const DynS
     S.root_ang_vel[0] = rw.x; S.root_ang_vel[1] = rw.y; S.root_ang_vel[2] = rw.z;
     for (int i = 1; i < B; ++i) {
         const int di = M.dof_idx[i];
-        if (M.jtype[i] == DJ_SPHERICAL) {
-            v3 e = qlog(jq[i]);
-            S.dof_pos[di] = e.x; S.dof_pos[di + 1] = e.y; S.dof_pos[di + 2] = e.z;
-            S.dof_vel[di] = qd[di]; S.dof_vel[di + 1] = qd[di + 1]; S.dof_vel[di + 2] = qd[di + 2];
-        } else if (M.jtype[i] == DJ_HINGE) {
-            S.dof_pos[di] = hang[i];
-            S.dof_vel[di] = qd[di];
-        }
+        if (M.jtype[i] == DJ_SPHERICAL) joint_store_spherical(jq[i], qd[i], S.dof_pos, S.dof_vel, di);
+        else if (M.jtype[i] == DJ_HINGE) joint_store_hinge(hang[i], qd[i].x, S.dof_pos, S.dof_vel, di);
     }
     for (int i = 0; i < B; ++i) { S.contact_force[3 * i] = fcon[i].x; S.contact_force[3 * i + 1] = fcon[i].y; S.contact_force[3 * i + 2] = fcon[i].z; }
 }

@@ -177,24 +177,9 @@ __global__ __launch_bounds__(64, 1) void k_dynamics_coop(const DynModel *__restr
         jq[k].x = 0.f; jq[k].y = 0.f; jq[k].z = 0.f; jq[k].w = 1.f; tq[k] = jq[k]; hang[k] = 0.f; thang[k] = 0.f; qd[k] = mk(0.f, 0.f, 0.f);
         const float *dp = buf.char_dof_pos + (size_t)Mg.D * ec, *dv = buf.char_dof_vel + (size_t)Mg.D * ec, *ac = action + (size_t)Mg.D * ec;
         const int di = did[k];
-        if (jty[k] == DJ_SPHERICAL) {
-            jq[k] = qexp(mk(dp[di], dp[di + 1], dp[di + 2]));
-            qd[k] = mk(dv[di], dv[di + 1], dv[di + 2]);
-            if (Mg.ctrl == PARC_CTRL_PD) {
-                tq[k] = qexp(mk(clampf(ac[di], M.act_lo[di], M.act_hi[di]), clampf(ac[di + 1], M.act_lo[di + 1], M.act_hi[di + 1]),
-                                clampf(ac[di + 2], M.act_lo[di + 2], M.act_hi[di + 2])));
-            } else { // the other control modes keep the joint's feed-forward torque (ctrl_ff) where the pd mode keeps its target
-                v3 diff = mk(0.f, 0.f, 0.f);
-                if (Mg.ctrl >= PARC_CTRL_PD_EXP) diff = qlog(qmul(qconj(jq[k]), qexp(mk(ac[di], ac[di + 1], ac[di + 2]))));
-                tq[k].x = ctrl_ff(Mg.ctrl, M.kp[di], M.kd[di], M.eff[di], M.act_lo[di], M.act_hi[di], ac[di], diff.x, qd[k].x);
-                tq[k].y = ctrl_ff(Mg.ctrl, M.kp[di + 1], M.kd[di + 1], M.eff[di + 1], M.act_lo[di + 1], M.act_hi[di + 1], ac[di + 1], diff.y, qd[k].y);
-                tq[k].z = ctrl_ff(Mg.ctrl, M.kp[di + 2], M.kd[di + 2], M.eff[di + 2], M.act_lo[di + 2], M.act_hi[di + 2], ac[di + 2], diff.z, qd[k].z);
-            }
-        } else if (jty[k] == DJ_HINGE) {
-            hang[k] = dp[di]; qd[k].x = dv[di];
-            if (Mg.ctrl == PARC_CTRL_PD) thang[k] = clampf(ac[di], M.act_lo[di], M.act_hi[di]);
-            else thang[k] = ctrl_ff(Mg.ctrl, M.kp[di], M.kd[di], M.eff[di], M.act_lo[di], M.act_hi[di], ac[di], ctrl_hinge_diff(Mg.ctrl, ac[di], hang[k]), qd[k].x);
-        }
+        // (the other control modes keep the joint's feed-forward torque where the pd mode keeps its target: joint_control_*)
+        if (jty[k] == DJ_SPHERICAL) joint_control_spherical(Mg, joint_gains(M, di), dp, dv, ac, di, jq[k], qd[k], tq[k]);
+        else if (jty[k] == DJ_HINGE) joint_control_hinge(Mg, joint_gains(M, di), dp, dv, ac, di, hang[k], qd[k].x, thang[k]);
     }
     // root state lives in the lane of chain 0
     v3 rp = mk(buf.char_root_pos[3 * ec], buf.char_root_pos[3 * ec + 1], buf.char_root_pos[3 * ec + 2]);
@@ -431,30 +416,11 @@ __global__ __launch_bounds__(64, 1) void k_dynamics_coop(const DynModel *__restr
                                 if (nd == 3) {
                                     PARC_UNROLL
                                     for (int q = 0; q < 3; ++q) { const v3 a = mk(R.m[0][q], R.m[1][q], R.m[2][q]); Sc[q] = s6mk(a, cross(r, a)); }
-                                    const bool pd = Mg.ctrl == PARC_CTRL_PD;
-                                    const v3 err = pd ? qlog(qmul(qconj(jqk), tqk)) : mk(tqk.x, tqk.y, tqk.z); // (not pd: the feed-forward torque)
-                                    const v3 cur = qlog(jqk);
-                                    const float e3[3] = {err.x, err.y, err.z}, c3[3] = {cur.x, cur.y, cur.z}, q3[3] = {qdk.x, qdk.y, qdk.z};
-                                    PARC_UNROLL
-                                    for (int q = 0; q < 3; ++q) {
-                                        float t = M.kp[di + q] * e3[q] - (M.kd[di + q] + dt * M.kp[di + q]) * q3[q];
-                                        t = clampf(t, -M.eff[di + q], M.eff[di + q]);
-                                        aug[q] = M.arm[di + q] + dt * M.kd[di + q] + dt * dt * M.kp[di + q];
-                                        if (!pd) drive_ff(Mg.ctrl, M.kd[di + q], M.arm[di + q], M.eff[di + q], dt, e3[q], q3[q], t, aug[q]);
-                                        if (c3[q] < M.lo[di + q]) { t += Mg.lim_k * (M.lo[di + q] - c3[q]) - Mg.lim_d * q3[q]; aug[q] += dt * Mg.lim_d + dt * dt * Mg.lim_k; }
-                                        else if (c3[q] > M.hi[di + q]) { t += Mg.lim_k * (M.hi[di + q] - c3[q]) - Mg.lim_d * q3[q]; aug[q] += dt * Mg.lim_d + dt * dt * Mg.lim_k; }
-                                        tau[q] = t;
-                                    }
+                                    joint_drive_spherical(Mg, joint_gains(M, di), dt, jqk, tqk, qdk, tau, aug);
                                 } else {
                                     const v3 a = mulv(R, mk(M.axis[b][0], M.axis[b][1], M.axis[b][2]));
                                     Sc[0] = s6mk(a, cross(r, a)); Sc[1] = s6zero(); Sc[2] = s6zero();
-                                    float t = M.kp[di] * (thk - hk) - (M.kd[di] + dt * M.kp[di]) * qdk.x;
-                                    t = clampf(t, -M.eff[di], M.eff[di]);
-                                    aug[0] = M.arm[di] + dt * M.kd[di] + dt * dt * M.kp[di];
-                                    if (Mg.ctrl != PARC_CTRL_PD) drive_ff(Mg.ctrl, M.kd[di], M.arm[di], M.eff[di], dt, thk, qdk.x, t, aug[0]);
-                                    if (hk < M.lo[di]) { t += Mg.lim_k * (M.lo[di] - hk) - Mg.lim_d * qdk.x; aug[0] += dt * Mg.lim_d + dt * dt * Mg.lim_k; }
-                                    else if (hk > M.hi[di]) { t += Mg.lim_k * (M.hi[di] - hk) - Mg.lim_d * qdk.x; aug[0] += dt * Mg.lim_d + dt * dt * Mg.lim_k; }
-                                    tau[0] = t;
+                                    joint_drive_hinge(Mg, joint_gains(M, di), dt, hk, thk, qdk.x, tau[0], aug[0]);
                                 }
                                 float Dm[3][3] = {{1.f, 0.f, 0.f}, {0.f, 1.f, 0.f}, {0.f, 0.f, 1.f}};
                                 PARC_UNROLL
@@ -593,27 +559,13 @@ __global__ __launch_bounds__(64, 1) void k_dynamics_coop(const DynModel *__restr
         DSTAMP(9);
         // ================= integrate =================
         if (c == 0) {
-            const v3 alpha = s6ang(acc_root), aO = s6lin(acc_root);
-            const v3 rv_new = rv + dt * (aO + cross(rw, rv));
-            v3 rw_new = rw + dt * alpha;
-            rw_new = (1.f / (1.f + dt * Mg.ang_damping)) * rw_new;
-            const float wm = sqrtf(dot(rw_new, rw_new));
-            if (wm > Mg.max_ang_vel) rw_new = (Mg.max_ang_vel / wm) * rw_new;
-            rv = rv_new; rw = rw_new;
-            rp = rp + dt * rv;
-            rq = qnormalize(qmul(qexp(dt * rw), rq));
+            root_integrate(dt, Mg.ang_damping, Mg.max_ang_vel, s6ang(acc_root), s6lin(acc_root), rp, rq, rv, rw);
         }
 #pragma unroll
         for (int k = 0; k < CO_MAXLEN; ++k) {
             if (k < my_len) {
-                if (jty[k] == DJ_SPHERICAL) {
-                    qd[k] = mk(clampf(qd[k].x + dt * qdd[k].x, -Mg.max_ang_vel, Mg.max_ang_vel), clampf(qd[k].y + dt * qdd[k].y, -Mg.max_ang_vel, Mg.max_ang_vel),
-                               clampf(qd[k].z + dt * qdd[k].z, -Mg.max_ang_vel, Mg.max_ang_vel));
-                    jq[k] = qnormalize(qmul(jq[k], qexp(dt * qd[k])));
-                } else if (jty[k] == DJ_HINGE) {
-                    qd[k].x = clampf(qd[k].x + dt * qdd[k].x, -Mg.max_ang_vel, Mg.max_ang_vel);
-                    hang[k] += dt * qd[k].x;
-                }
+                if (jty[k] == DJ_SPHERICAL) joint_integrate_spherical(dt, Mg.max_ang_vel, qdd[k], jq[k], qd[k]);
+                else if (jty[k] == DJ_HINGE) joint_integrate_hinge(dt, Mg.max_ang_vel, qdd[k].x, hang[k], qd[k].x);
             }
         }
         __syncthreads();
@@ -635,10 +587,8 @@ __global__ __launch_bounds__(64, 1) void k_dynamics_coop(const DynModel *__restr
         if (k < my_len) {
             const int b = bid[k], di = did[k];
             float *dp = buf.char_dof_pos + (size_t)Mg.D * e, *dv = buf.char_dof_vel + (size_t)Mg.D * e;
-            if (jty[k] == DJ_SPHERICAL) {
-                const v3 ex = qlog(jq[k]);
-                dp[di] = ex.x; dp[di + 1] = ex.y; dp[di + 2] = ex.z; dv[di] = qd[k].x; dv[di + 1] = qd[k].y; dv[di + 2] = qd[k].z;
-            } else if (jty[k] == DJ_HINGE) { dp[di] = hang[k]; dv[di] = qd[k].x; }
+            if (jty[k] == DJ_SPHERICAL) joint_store_spherical(jq[k], qd[k], dp, dv, di);
+            else if (jty[k] == DJ_HINGE) joint_store_hinge(hang[k], qd[k].x, dp, dv, di);
             float *cf = buf.contact_forces + 3 * ((size_t)e * B + b);
             cf[0] = fcon[k].x; cf[1] = fcon[k].y; cf[2] = fcon[k].z;
         }

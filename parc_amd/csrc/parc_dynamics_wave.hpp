@@ -318,6 +318,11 @@ struct WvBody { // per-body registers of the owning lane
     v3 fcon_c;                           // contact force on the fixed leaf merged into this body (WvBodyC::child)
 };
 
+// THE JOINT MODEL (parc_dynamics.hpp) IN THIS KERNEL.  wv_integrate_joint calls the shared statement.  wv_load_joint, the drive lines of
+// wv_joint_inward, wv_store_joint and the root's integration in the kernel body carry the SAME statements in their own text: through the
+// shared functions the values are the same, bit for bit, but the instruction order and the register allocation of this kernel move
+// (it sits at 256 VGPR + 255 AGPR), and the rule here is that its machine code does not change without a measured reason (DESIGN.md
+// section 4b).  A change to the joint model is made in parc_dynamics.hpp and in these four places.
 template <bool FF> // FF: a control mode other than pd -- B.tq.xyz / B.thang then hold the joint's feed-forward torque (ctrl_ff) instead of the target
 __device__ __forceinline__ void wv_load_joint(const DynModel &M, const WaveTables &W, int b, WvBody &B, const float *dp, const float *dv, const float *ac) {
     B.jq.x = 0.f; B.jq.y = 0.f; B.jq.z = 0.f; B.jq.w = 1.f; B.tq = B.jq; B.hang = 0.f; B.thang = 0.f; B.qd = mk(0.f, 0.f, 0.f);
@@ -700,7 +705,7 @@ __device__ __forceinline__ void wv_joint_inward(const DynModel &M, const WaveTab
         // (round 4: -117 of ~560 vector instructions per elimination; parc_dynamics.hpp keeps the joint-frame statement, S = P R:
         // U = U' R, D = R^T D' R, K = K' R, K u = K' u', I - K U^T = I - K' U'^T -- the same projection up to rounding).  The factors kept
         // for the outward pass are K' and D'^-1 u' (world axes); the joint-frame acceleration the integrator needs is R^T q'.
-        float tau[3], aug[3];
+        float tau[3], aug[3]; // (joint_drive_spherical's statement: see wv_load_joint)
         const v3 err = FF ? mk(B.tq.x, B.tq.y, B.tq.z) : qlog(qmul(qconj(B.jq), B.tq)); // (FF: the feed-forward torque)
         const v3 cur = qlog(B.jq);
         const float e3[3] = {err.x, err.y, err.z}, c3[3] = {cur.x, cur.y, cur.z}, q3[3] = {B.qd.x, B.qd.y, B.qd.z};
@@ -847,14 +852,8 @@ __device__ __forceinline__ void wv_joint_outward(const DynModel &M, const WaveTa
 
 __device__ __forceinline__ void wv_integrate_joint(const DynModel &M, const WaveTables &W, int b, WvBody &B, float dt) {
     const int jt = W.c[b].jtype;
-    const float mw = M.max_ang_vel;
-    if (jt == DJ_SPHERICAL) {
-        B.qd = mk(clampf(B.qd.x + dt * B.qdd.x, -mw, mw), clampf(B.qd.y + dt * B.qdd.y, -mw, mw), clampf(B.qd.z + dt * B.qdd.z, -mw, mw));
-        B.jq = qnormalize(qmul(B.jq, qexp(dt * B.qd)));
-    } else if (jt == DJ_HINGE) {
-        B.qd.x = clampf(B.qd.x + dt * B.qdd.x, -mw, mw);
-        B.hang += dt * B.qd.x;
-    }
+    if (jt == DJ_SPHERICAL) joint_integrate_spherical(dt, M.max_ang_vel, B.qdd, B.jq, B.qd);
+    else if (jt == DJ_HINGE) joint_integrate_hinge(dt, M.max_ang_vel, B.qdd.x, B.hang, B.qd.x);
 }
 
 // pr (optional): the env's prep record for the observation kernel (k_env_prep's output, parc_env.hip): slot b = dof -> quat of joint b
@@ -1219,6 +1218,7 @@ __device__ __forceinline__ void dynamics_wave_body(const DynModel *__restrict__ 
                     }
                     if (k == 0) { // integrate the root at once: the limbs that hang off it (the long chains) then have the next
                                   // substep's kinematics of their parent before the trunk's outward pass and integration are through
+                        // (root_integrate's statement, parc_dynamics.hpp, with the hardware reciprocal / square root)
                         const v3 alpha = s6ang(acc_root), aO = s6lin(acc_root);
                         const v3 rv_new = rv + dt * (aO + cross(rw, rv));
                         v3 rw_new = rw + dt * alpha;

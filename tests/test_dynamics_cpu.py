@@ -719,3 +719,124 @@ def test_control_mode_pd_1d_on_a_hinge_chain(dyn):
     far = np.tile(np.asarray([0.3 + 4.0, -0.2], np.float32), (n, 1))                  # 4.0 rad ahead = 2.28 rad behind, the shorter way
     d1.step(*FLAT, s_a, far, off); de.step(*FLAT, s_b, far, off)
     assert s_a["dof_vel"][0, 0] > qd0[0] and s_b["dof_vel"][0, 0] < qd0[0], (s_a["dof_vel"][0], s_b["dof_vel"][0])
+
+
+def test_dof_drive_pd_feedforward_and_limit_spring():
+    """The joint model that the three solvers share (parc_dynamics.hpp, THE JOINT MODEL): the drive of one dof in a substep -- implicit pd or the
+    feed-forward torque of the other control modes, then the joint-limit spring -- and the control law of a hinge and of a spherical joint, against
+    the formulas written out here in fp32, bit for bit (the host build rounds every operation separately, like numpy's float32 scalars).  The
+    formulas are the statements the solvers carried before they shared them: t = kp e - (kd + dt kp) qd limited to +-eff, aug = arm + dt kd +
+    dt^2 kp; not pd: t = ff - [vel: kd] qd limited to +-eff, aug = arm + dt [vel: kd]; outside [lo, hi] the spring adds lim_k (lim - cur) - lim_d qd
+    to the torque -- after the motor limit -- and dt lim_d + dt^2 lim_k to the augmentation."""
+    from oracle.binding_dyn import JointModel
+    from parc_amd.envs import scene
+    jm = JointModel()
+    f = np.float32
+    PD, VEL, TORQUE, PD_EXP, PD_1D = (scene.CONTROL_MODES[k] for k in ("pd", "vel", "torque", "pd_exp", "pd_1d"))
+
+    def clampf(x, lo, hi):
+        return lo if x < lo else (hi if x > hi else x)
+
+    def ctrl_ff(ctrl, kp, kd, eff, alo, ahi, a, diff, qd0):
+        if ctrl == VEL:
+            return kd * clampf(a, alo, ahi)
+        if ctrl == TORQUE:
+            return clampf(a, alo, ahi)
+        return clampf(kp * diff - kd * qd0, -eff, eff)
+
+    def hinge_diff(ctrl, a, hang):
+        d = a - hang
+        if ctrl == PD_EXP:
+            d = d - f(6.28318530717958648) * np.rint(d * f(0.159154943091895336))
+        return d
+
+    def drive(ctrl, kp, kd, arm, eff, lo, hi, lim_k, lim_d, dt, e, cur, qd):
+        t = kp * e - (kd + dt * kp) * qd
+        t = clampf(t, -eff, eff)
+        aug = arm + dt * kd + dt * dt * kp
+        if ctrl != PD:
+            kdv = kd if ctrl == VEL else f(0.0)
+            t = clampf(e - kdv * qd, -eff, eff)
+            aug = arm + dt * kdv
+        if cur < lo:
+            t = t + (lim_k * (lo - cur) - lim_d * qd); aug = aug + (dt * lim_d + dt * dt * lim_k)
+        elif cur > hi:
+            t = t + (lim_k * (hi - cur) - lim_d * qd); aug = aug + (dt * lim_d + dt * dt * lim_k)
+        return t, aug
+
+    def same(got, want, what):
+        got, want = np.asarray(got), np.asarray(want)
+        assert got.dtype == np.float32 and want.dtype == np.float32, what
+        assert np.array_equal(got, want), (what, got, want)
+
+    kp, kd, arm, eff, lo, hi = f(300.7), f(30.3), f(0.0123), f(150.5), f(-1.1), f(2.3)
+    lim_k, lim_d, dt = f(1234.5), f(12.7), f(1.0 / 120.0)
+    G = (kp, kd, arm, eff, lo, hi, lim_k, lim_d, dt)
+    # ---- pd: in range, beyond either limit, at the motor limit (with and without the spring on top)
+    for name, e, cur, qd in [("in range", 0.1, 0.3, 0.7), ("below lo", 0.1, -1.4, 0.7), ("above hi", -0.2, 2.6, -0.4), ("at lo", 0.1, -1.1, 0.7),
+                             ("+eff", 1.0, 0.3, 0.7), ("-eff", -1.0, 0.3, 0.7), ("+eff and spring", 1.0, 2.9, 0.7), ("-eff and spring", -1.0, -1.6, -2.0)]:
+        e, cur, qd = f(e), f(cur), f(qd)
+        got, want = jm.dof_drive(PD, *G, e, cur, qd), drive(PD, *G, e, cur, qd)
+        same(got, want, ("pd", name))
+        t0 = clampf(kp * e - (kd + dt * kp) * qd, -eff, eff); a0 = arm + dt * kd + dt * dt * kp
+        if name in ("in range", "at lo"):
+            assert got[0] == t0 and abs(got[0]) < eff and got[1] == a0, name
+        elif "eff" in name and "spring" not in name:
+            assert got[0] == (eff if name[0] == "+" else -eff) and got[1] == a0, name
+        else:
+            lim = lo if cur < lo else hi
+            assert got[0] == t0 + (lim_k * (lim - cur) - lim_d * qd) and got[0] != t0, name
+            assert got[1] == a0 + (dt * lim_d + dt * dt * lim_k) and got[1] > a0, name
+            if "spring" in name:
+                assert abs(got[0]) > eff, name          # the spring is not a motor: it acts on top of the limited torque
+    # ---- the other modes on a hinge: control law (action inside / outside its bounds), then the drive with that torque
+    alo, ahi = f(-2.0), f(2.5)
+    for ctrl in (VEL, TORQUE, PD_EXP, PD_1D, PD):
+        for a in (0.4, -7.0, 9.0):
+            for pos, vel in [(0.3, 0.7), (-1.4, -0.5), (2.6, 3.0)]:
+                a_, pos_, vel_ = f(a), f(pos), f(vel)
+                hang, qd, th = jm.control_hinge(ctrl, kp, kd, eff, alo, ahi, pos_, vel_, a_)
+                want = clampf(a_, alo, ahi) if ctrl == PD else ctrl_ff(ctrl, kp, kd, eff, alo, ahi, a_, hinge_diff(ctrl, a_, pos_), vel_)
+                same([hang, qd, th], [pos_, vel_, want], ("hinge control", ctrl, a, pos))
+                e = th - hang if ctrl == PD else th
+                same(jm.dof_drive(ctrl, *G, e, hang, qd), drive(ctrl, *G, e, hang, qd), ("hinge drive", ctrl, a, pos))
+    assert jm.control_hinge(VEL, kp, kd, eff, alo, ahi, f(0), f(0), f(9.0))[2] == kd * ahi            # clipped to the bounds, times the damping
+    assert jm.control_hinge(TORQUE, kp, kd, eff, alo, ahi, f(0), f(0), f(-7.0))[2] == alo
+    t_v, aug_v = jm.dof_drive(VEL, *G, f(20.0), f(0.3), f(0.7))
+    t_t, aug_t = jm.dof_drive(TORQUE, *G, f(20.0), f(0.3), f(0.7))
+    assert t_v == f(20.0) - kd * f(0.7) and aug_v == arm + dt * kd and t_t == f(20.0) and aug_t == arm   # only vel keeps a damping, implicit
+    # ---- pd_exp takes a hinge's difference the shorter way round, pd_1d subtracts: across +-pi they part (soft gains: neither at the motor limit)
+    skp, skd = f(20.3), f(1.7)
+    for pos, a in [(3.0, -3.0), (-3.1, 3.1), (0.5, 0.5 + 3.2), (0.5, 0.5 - 3.2), (0.5, 0.5 + 3.1)]:
+        pos_, a_ = f(pos), f(a)
+        t_e = jm.control_hinge(PD_EXP, skp, skd, eff, alo, ahi, pos_, f(0.3), a_)[2]
+        t_1 = jm.control_hinge(PD_1D, skp, skd, eff, alo, ahi, pos_, f(0.3), a_)[2]
+        same(t_e, ctrl_ff(PD_EXP, skp, skd, eff, alo, ahi, a_, hinge_diff(PD_EXP, a_, pos_), f(0.3)), ("pd_exp", pos, a))
+        same(t_1, ctrl_ff(PD_1D, skp, skd, eff, alo, ahi, a_, a_ - pos_, f(0.3)), ("pd_1d", pos, a))
+        assert abs(t_e) < eff and abs(t_1) < eff
+        if abs(a - pos) > np.pi:
+            assert np.sign(t_e) == -np.sign(t_1) and abs(skp * hinge_diff(PD_EXP, a_, pos_)) < skp * f(np.pi), (pos, a, t_e, t_1)
+        else:
+            assert t_e == t_1, (pos, a)
+    # ---- a spherical joint: three dofs with gains of their own
+    kp3, kd3, eff3 = np.array([300.7, 20.3, 500.1], np.float32), np.array([30.3, 1.7, 50.9], np.float32), np.array([150.5, 40.0, 2.5], np.float32)
+    lo3, hi3 = np.array([-1.2, -0.5, -2.0], np.float32), np.array([1.0, 0.7, 2.5], np.float32)
+    pos, vel = np.array([0.3, -0.4, 0.2], np.float32), np.array([0.7, -1.5, 0.1], np.float32)
+    for a in (np.array([0.2, 0.1, -0.3], np.float32), np.array([3.0, -0.9, 0.4], np.float32)):    # inside the bounds; two components outside
+        clipped = np.minimum(np.maximum(a, lo3), hi3)
+        for ctrl in (PD, VEL, TORQUE, PD_EXP):
+            jq, qd, tq = jm.control_spherical(ctrl, kp3, kd3, eff3, lo3, hi3, pos, vel, a)
+            same(jq, jm.qexp(pos), ("jq", ctrl)); same(qd, vel, ("qd", ctrl))
+            if ctrl == PD:
+                want = jm.qexp(clipped)
+                assert not np.array_equal(want, jm.qexp(a)) or np.array_equal(a, clipped)
+            else:
+                diff = jm.rot_diff(pos, a) if ctrl == PD_EXP else np.zeros(3, np.float32)          # the action as given, not the clipped one
+                want = np.array([ctrl_ff(ctrl, kp3[k], kd3[k], eff3[k], lo3[k], hi3[k], a[k], diff[k], vel[k]) for k in range(3)] + [f(1.0)], np.float32)
+                if ctrl == PD_EXP:
+                    assert abs(want[2]) == eff3[2] and abs(want[1]) < eff3[1]                       # one dof at its motor limit, one not
+            same(tq, want, ("tq", ctrl, a))
+    # (the primitives behind it mean what they say: exp map -> quaternion, and the rotation between two poses about one axis is the difference)
+    ang = np.linalg.norm(pos.astype(np.float64))
+    assert np.abs(jm.qexp(pos) - np.append(np.sin(ang / 2) * pos / ang, np.cos(ang / 2))).max() < 1e-6
+    assert np.abs(jm.rot_diff(np.array([0, 0.3, 0], np.float32), np.array([0, 1.1, 0], np.float32)) - [0, 0.8, 0]).max() < 1e-6

@@ -638,3 +638,75 @@ def test_control_modes_three_kernels_and_the_host_build_agree(mode):
         assert all(torch.equal(out[1][k], out[2][k]) for k in state)
     assert ref._lib.parc_env_dynamics_timeouts(ref._handle) == 0 and ref.dynamics_manifold_drops() == 0
     assert torch.isfinite(ref._obs_buf).all() and torch.isfinite(ref._reward_buf).all()
+
+
+def test_joint_limit_springs_three_kernels_and_the_host_build_agree():
+    """The joint-limit spring of the shared joint model (parc_dynamics.hpp, dof_drive): dofs pushed 0.2 rad beyond their limits, hinges and
+    spherical joints alike, in every second env; the three kernels and the host build of the reference statement integrate the same control
+    step from that state.  pd mode, 96 envs (three 32-env blocks of the wave kernel), the roots lifted 5 m: without contact the step is not
+    chaotic, so every env is held to the tolerances of test_control_modes_three_kernels_and_the_host_build_agree -- no quantiles."""
+    import torch
+    from gpu_helpers import default_config, to_np
+    from oracle.binding_dyn import DynOracle
+    from parc_amd.envs.hip_parkour_env import HipParkourEnv
+    n = 96
+    envs = {k: HipParkourEnv(default_config(), n, "cuda:0", False, seed=33, enable_dynamics=True, mirror_ref_state=False, dev_options={"kernel": k})
+            for k in ("wave", "coop", "thread")}
+    assert [envs[k].describe()["dynamics_kernel"] for k in ("wave", "coop", "thread")] == ["k_dynamics_wave", "k_dynamics_coop", "k_dynamics"]
+    ref = envs["wave"]
+    for e in envs.values():
+        e.reset()
+    sc = ref._scene
+    D = sc.cfg.model.dof_size
+    lower = np.array(list(sc.cfg.dynamics.dof_lower)[:D], np.float32); upper = np.array(list(sc.cfg.dynamics.dof_upper)[:D], np.float32)
+    jt = np.array(list(sc.cfg.model.joint_type)[:sc.cfg.model.num_bodies]); di = np.array(list(sc.cfg.model.dof_idx)[:sc.cfg.model.num_bodies])
+    hinge_dofs = [int(di[b]) for b in range(len(jt)) if jt[b] == 1]
+    sph_dofs = [int(di[b]) + k for b in range(len(jt)) if jt[b] == 2 for k in range(3)]
+    assert hinge_dofs and sph_dofs and len(hinge_dofs) + len(sph_dofs) == D
+    state = ["_char_root_pos", "_char_root_rot", "_char_root_vel", "_char_root_ang_vel", "_char_dof_pos", "_char_dof_vel"]
+    tol = {"_char_root_pos": 1e-4, "_char_root_rot": 1e-4, "_char_root_vel": 2e-3, "_char_root_ang_vel": 1e-2, "_char_dof_pos": 2e-4, "_char_dof_vel": 5e-2}
+    act = ref._char_dof_pos.clone().contiguous()             # the pd target: the pose of the reset
+    pushed = np.where(np.arange(D) % 2 == 0, lower - np.float32(0.2), upper + np.float32(0.2)).astype(np.float32)
+    pos = to_np(ref._char_dof_pos).copy()
+    pos[::2] = pushed
+    # the coordinates the limits apply to: a hinge's angle; a spherical joint's exponential map with its angle in [0, pi] (beyond half a turn
+    # the pushed dofs are the same rotation the other way round)
+    cur = pos.astype(np.float64)
+    for d in sph_dofs[::3]:
+        ang = np.linalg.norm(cur[:, d:d + 3], axis=1, keepdims=True)
+        cur[:, d:d + 3] *= np.where(ang > np.pi, (ang - 2 * np.pi) / ang, 1.0)
+    out = (cur < lower - 1e-3) | (cur > upper + 1e-3)
+    assert out[::2][:, hinge_dofs].any(1).all() and out[::2][:, sph_dofs].any(1).all()
+    assert out[::2].sum(1).min() >= 10, out[::2].sum(1).min()
+    ref._char_dof_pos.copy_(torch.from_numpy(pos).to(ref._char_dof_pos.device))
+    ref._char_root_pos[:, 2] += 5.0
+    for kern in ("coop", "thread"):
+        for nm in state + ["_char_contact_forces"]:
+            getattr(envs[kern], nm).copy_(getattr(ref, nm))
+    st = dict(root_pos=to_np(ref._char_root_pos).copy(), root_rot=to_np(ref._char_root_rot).copy(), root_vel=to_np(ref._char_root_vel).copy(),
+              root_ang_vel=to_np(ref._char_root_ang_vel).copy(), dof_pos=to_np(ref._char_dof_pos).copy(), dof_vel=to_np(ref._char_dof_vel).copy(),
+              contact_force=np.zeros((n, 15, 3), np.float32))
+    vel0 = st["dof_vel"].copy()
+    for e in envs.values():
+        e.step(act)
+    torch.cuda.synchronize()
+    DynOracle(sc.cfg).step(sc.grid.terrain.hf, sc.grid.terrain.min_point, sc.grid.terrain.dxdy, st, to_np(act), sc.env_offsets)
+    assert np.abs(st["contact_force"]).max() == 0 and float(ref._char_contact_forces.abs().max()) == 0       # in the air
+    # the springs acted: a pushed env has 26 dofs 0.2 rad outside (200 N m of spring each, on top of the drive towards the reset pose), the others
+    # only follow their targets -- the typical pushed env's joints were driven harder than the typical other one's
+    dv = np.abs(st["dof_vel"] - vel0).max(1)
+    assert np.median(dv[::2]) > np.median(dv[1::2]), (np.median(dv[::2]), np.median(dv[1::2]))
+    host = {"_char_root_pos": "root_pos", "_char_root_rot": "root_rot", "_char_root_vel": "root_vel", "_char_root_ang_vel": "root_ang_vel",
+            "_char_dof_pos": "dof_pos", "_char_dof_vel": "dof_vel"}
+    errs = {}
+    for nm in state:
+        a = to_np(getattr(ref, nm))
+        assert np.isfinite(a).all(), nm
+        for kern in ("coop", "thread", "host"):
+            b = st[host[nm]] if kern == "host" else to_np(getattr(envs[kern], nm))
+            errs[kern, nm] = float(np.abs(a - b).max())
+            print("limit springs: wave vs %-6s %-20s max err %.3e (tol %.0e)" % (kern, nm, errs[kern, nm], tol[nm]))
+    for (kern, nm), err in errs.items():
+        assert err <= tol[nm], (kern, nm, err)
+    for e in envs.values():
+        assert e.dynamics_timeouts() == 0
