@@ -489,6 +489,45 @@ int parc_mopt_build_constraints(ParcMotionOpt *h, int32_t n, const int32_t *clip
 /* Per-kernel device time (hipEvents) of the last parc_mopt_step call, ms per iteration: fk, patch, points, grad, reduce, adam. */
 int parc_mopt_kernel_times(ParcMotionOpt *h, float *ms6);
 
+/* The motion generator's training loss: the reference's MDM.motion_difference (motion_generator/mdm.py:573-692) for
+ * N windows of T frames in one launch, with the analytic derivative of each window's sum of terms with respect to the standardised
+ * prediction (through unstandardise, exp_map_to_quat, joint_dof_to_rot and forward kinematics).  Its own handle; every array of a call
+ * is a device pointer and the launch goes to the caller's stream.  A prediction row is root_pos[3] | root exp map[3] | joint
+ * positions[3 (B - 1)] | joint dofs[dof_size] | contacts[B].  Terms, in this order: VEL_ROOT_POS, VEL_ROOT_ROT, VEL_JOINT_ROT,
+ * SIMPLE_ROOT_POS, SIMPLE_ROOT_ROT, SIMPLE_JOINT_ROT, SIMPLE_CONTACT, SIMPLE_BODY_POS, FK_BODY_POS, FK_BODY_ROT, BODY_POS_CONSISTENCY,
+ * VEL_FK_BODY_POS, TARGET.  A window's result does not depend on which other windows are in the batch. */
+#define PARC_MLOSS_NUM_TERMS 13
+#define PARC_MLOSS_SQUARED_L2 0
+#define PARC_MLOSS_PSEUDO_HUBER 1
+typedef struct ParcMotionLoss ParcMotionLoss;
+typedef struct {
+    uint32_t struct_size;                    /* sizeof(ParcMotionLossParams) */
+    int32_t device;
+    ParcCharModel model;                     /* the tables parc_env_create takes (fk_paths unused) */
+    float sequence_fps;                      /* velocities are differences of neighbouring frames times this */
+    int32_t num_prev_states;                 /* >= 1: the target term measures from frame num_prev_states - 1 to the last frame */
+    float weights[PARC_MLOSS_NUM_TERMS];     /* in the order of the terms */
+    int32_t use_pos_loss;                    /* 0: the four FK terms (FK_BODY_POS, FK_BODY_ROT, BODY_POS_CONSISTENCY, VEL_FK_BODY_POS) are 0 */
+    int32_t use_target_loss;                 /* 0: TARGET is 0 and target_dir is not read */
+    float target_dir_len_eps;                /* TARGET = w clamp(-dir . (root_xy[T - 1] - root_xy[num_prev_states - 1]), min = -eps) */
+    int32_t loss_fn;                         /* PARC_MLOSS_SQUARED_L2: sum of squares; PARC_MLOSS_PSEUDO_HUBER: sqrt(sum(sq + 0.0009)) - 0.03 */
+} ParcMotionLossParams;
+typedef struct {
+    int32_t n, num_frames;                   /* N >= 1 windows of T >= 2 frames, T >= num_prev_states */
+    const float *pred;                       /* [N][T][D] standardised */
+    const float *mean, *std;                 /* [T][D] */
+    const float *root_pos, *root_rot, *joint_rot, *contacts;   /* the true windows: [N][T][3], [N][T][4] xyzw, [N][T][B-1][4], [N][T][B] */
+    const float *target_dir;                 /* [N][2]; may be NULL without use_target_loss */
+    float *terms;                            /* out [N][PARC_MLOSS_NUM_TERMS]: the weighted value of every term per window */
+    float *grad;                             /* out [N][T][D]: d (the window's sum of terms) / d pred */
+} ParcMotionLossArgs;
+int parc_mloss_create(const ParcMotionLossParams *p, ParcMotionLoss **out);
+void parc_mloss_destroy(ParcMotionLoss *h);
+/* One launch on `stream`, no host synchronisation (but when the workspace has to grow to a larger N x T than any call before). */
+int parc_mloss_eval(ParcMotionLoss *h, const ParcMotionLossArgs *a, void *stream);
+/* Device time (hipEvents) of the last parc_mloss_eval, ms; synchronises with it. */
+int parc_mloss_kernel_times(ParcMotionLoss *h, float *ms1);
+
 /* Motion-terrain analysis for B clips at once, each on its own terrain: the reference's
  * terrain_util.compute_hf_extra_vals (per-frame heightfield cell masks, lowest body point per cell, augmentation bounds hf_maxmin,
  * terrain_util.py:1851-1947), mdm_path.compute_motion_loss with unit weights (penetration and contact against the exact column-box

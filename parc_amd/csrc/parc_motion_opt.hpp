@@ -62,49 +62,6 @@ struct Work {                           // per-frame workspace, each frame owned
     float *terms;                       // [C][NT]
 };
 
-// d/dq of quat_rotate(q, v) = v + w t + u x t, t = 2 u x v, applied to g: gu = 2w (v x g) + t x g + 2 v x (g x u), gw = g . t
-__device__ __forceinline__ Q4 rotate_vjp_q(Q4 q, V3 v, V3 g) {
-    const V3 u = mk3(q.x, q.y, q.z);
-    const V3 t = scl3(cross3(u, v), 2.f);
-    const V3 a = scl3(cross3(v, g), 2.f * q.w), b = cross3(t, g), c = scl3(cross3(v, cross3(g, u)), 2.f);
-    return mk4(a.x + b.x + c.x, a.y + b.y + c.y, a.z + b.z + c.z, dot3(g, t));
-}
-
-// quat_diff_angle(q0, q1) = angle of quat_pos(q1 (x) conj(q0)) (torch_util.py:454-462, :70-91): adjoints of q0 and q1 for dL/dangle = ga.
-// Masked (|v| <= 1e-5, angle forced to 0) => zero, as autograd gives through torch.where.
-__device__ __forceinline__ void diff_angle_vjp(Q4 q0, Q4 q1, float ga, Q4 &g0, Q4 &g1) {
-    const Q4 dq = quat_mul(q1, quat_conj(q0));
-    const float s = dq.w < 0.f ? -1.f : 1.f;
-    const V3 v = mk3(s * dq.x, s * dq.y, s * dq.z);
-    const float w = s * dq.w, len = norm3(v);
-    if (!(len > 1e-5f) || ga == 0.f) { g0 = mk4(0.f, 0.f, 0.f, 0.f); g1 = g0; return; }
-    const float r2 = len * len + w * w;
-    const float kv = ga * 2.f * w / r2 / len, kw = -ga * 2.f * len / r2;
-    const Q4 gdq = mk4(s * kv * v.x, s * kv * v.y, s * kv * v.z, s * kw);
-    g1 = qmul(gdq, q0);
-    g0 = quat_conj(qmul(quat_conj(q1), gdq));
-}
-
-// exp_map_to_quat backward (torch_util.py:426-450): q = (sin(th/2) e/|e|, cos(th/2)), th = |e| wrapped to (-pi, pi].  Masked
-// |th| <= 1e-5 => 0 (the reference's backward is NaN at an exactly zero exp map: 0 here).
-__device__ __forceinline__ V3 exp_map_vjp(V3 e, Q4 g) {
-    const float t0 = norm3(e);
-    const float th = atan2f(sinf(t0), cosf(t0));
-    if (!(fabsf(th) > 1e-5f)) return mk3(0.f, 0.f, 0.f);
-    const V3 n = scl3(e, 1.f / t0);
-    const float s = sinf(0.5f * th), c = cosf(0.5f * th);
-    const V3 gv = mk3(g.x, g.y, g.z);
-    const float nd = dot3(n, gv);
-    const float a = s / t0, bn = 0.5f * c * nd - a * nd - 0.5f * s * g.w;
-    return mk3(a * gv.x + bn * n.x, a * gv.y + bn * n.y, a * gv.z + bn * n.z);
-}
-
-// hinge: axis_angle_to_quat(axis, d) backward
-__device__ __forceinline__ float hinge_vjp(const float *axis, float d, Q4 g) {
-    const V3 na = normalize3(mk3(axis[0], axis[1], axis[2]));
-    return 0.5f * cosf(0.5f * d) * (na.x * g.x + na.y * g.y + na.z * g.z) - 0.5f * sinf(0.5f * d) * g.w;
-}
-
 // the gradient of sdBox (parc_grid.hpp's sd_box; geom_util.py:124-145) as autograd computes it (sign(p) through abs, the clamp masks
 // q >= 0 / max(q) <= 0, the first maximal component for max(dim=-1), 0 for a zero norm)
 __device__ __forceinline__ V3 sd_box_grad(V3 p, V3 h) {

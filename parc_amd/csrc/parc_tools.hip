@@ -13,4 +13,5 @@
 #include "parc_motion_aug.hpp"       // parc_maug_*: stage 0's motion-terrain augmenter and the mirrored copies, batched
 #include "parc_mdm.hpp"              // parc_mdm_*: the motion generator's inference, the MDM denoiser and its DDIM / DDPM loops
 #include "parc_mdm_path.hpp"         // parc_mpath_*: path-following generation, the generator's world-frame wrapper and the rollout along a path
+#include "parc_mdm_loss.hpp"         // parc_mloss_*: the motion generator's training loss, the thirteen terms and their gradient in one launch
 #include "parc_learner.hpp"          // parc_td_lambda_return, parc_normalize_record, parc_gather_rows: the learner's kernels

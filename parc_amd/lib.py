@@ -264,6 +264,20 @@ class ParcMdmSampleArgs(C.Structure):
                 ("first_index", C.c_uint64), ("keep", C.c_void_p)]
 
 
+MLOSS_NUM_TERMS, MLOSS_SQUARED_L2, MLOSS_PSEUDO_HUBER = 13, 0, 1   # PARC_MLOSS_*
+
+
+class ParcMotionLossParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("model", ParcCharModel), ("sequence_fps", C.c_float),
+                ("num_prev_states", C.c_int32), ("weights", C.c_float * MLOSS_NUM_TERMS), ("use_pos_loss", C.c_int32),
+                ("use_target_loss", C.c_int32), ("target_dir_len_eps", C.c_float), ("loss_fn", C.c_int32)]
+
+
+class ParcMotionLossArgs(C.Structure):
+    _fields_ = [("n", C.c_int32), ("num_frames", C.c_int32)] + \
+               [(k, C.c_void_p) for k in ("pred", "mean", "std", "root_pos", "root_rot", "joint_rot", "contacts", "target_dir", "terms", "grad")]
+
+
 MPATH_HEADING_AUTO, MPATH_HEADING_RANDOM = 0, 1   # PARC_MPATH_HEADING_*
 
 
@@ -378,6 +392,11 @@ def _signatures():
         "parc_mopt_get_source_body": (rc, [vp, f32p, f32p]),
         "parc_mopt_build_constraints": (rc, [vp, i32, i32p, f32p, i32, f32]),
         "parc_mopt_kernel_times": (rc, [vp, f32p]),
+        # motion generator's training loss
+        "parc_mloss_create": (rc, [P(ParcMotionLossParams), P(vp)]),
+        "parc_mloss_destroy": (None, [vp]),
+        "parc_mloss_eval": (rc, [vp, P(ParcMotionLossArgs), vp]),
+        "parc_mloss_kernel_times": (rc, [vp, f32p]),
         # motion-terrain analysis
         "parc_mterr_create": (rc, [P(ParcMotionTerrainParams), P(vp)]),
         "parc_mterr_destroy": (None, [vp]),
