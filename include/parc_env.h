@@ -1058,6 +1058,46 @@ int parc_mpath_kernel_times(ParcMdmPath *h, float *ms2);
 /* max_frames, max_windows, FD; then of the last rollout: windows, kernel launches, frames per row. */
 int parc_mpath_describe(ParcMdmPath *h, int64_t *out6);
 
+/* Hesitation-frame removal for B clips at once: the reference's medit_lib.remove_hesitation_frames
+ * (util/motion_edit_lib.py:804-878), the step of stage 2 between the optimiser and compute_hf_extra_vals.  Its own handle.  The clips use
+ * the optimiser's layout (ParcMotionOptClips; the heightfield arrays are validated and otherwise unused, the constraint fields ignored).
+ * d(i, j) is the norm of body_pos[j] - body_pos[i] over all num_bodies x 3 numbers (FK in fp32).  Frames are visited in order: a frame i
+ * that is not flagged flags every j > i with d(i, j) < hesitation_val; a flagged frame flags nothing; frame 0 is never flagged.  Runs of
+ * consecutive flagged frames shorter than hesitation_min_seq_len are unflagged again; the other flagged frames are removed, and the kept
+ * frames are copied as they are.  A distance that is not a number flags nothing.  Results do not depend on which other clips are in the
+ * batch. */
+#define PARC_MEDIT_MAX_FRAMES 4096               /* frames per clip: the flag set of a clip is one 64-bit word per lane of a wave */
+#define PARC_MEDIT_FLAG_WORDS 64                 /* PARC_MEDIT_MAX_FRAMES / 64 */
+typedef struct ParcMotionEdit ParcMotionEdit;
+typedef struct {
+    uint32_t struct_size;                    /* sizeof(ParcMotionEditParams) */
+    int32_t device;
+    ParcCharModel model;                     /* the tables parc_env_create takes (fk_paths unused) */
+    float hesitation_val;                    /* metres, compared in fp32 (reference default 0.15) */
+    int32_t hesitation_min_seq_len;          /* >= 1 (reference default 4) */
+} ParcMotionEditParams;
+int parc_medit_create(const ParcMotionEditParams *p, ParcMotionEdit **out);
+void parc_medit_destroy(ParcMotionEdit *h);
+/* Uploads the clips (num_clips >= 1, every clip 1 .. PARC_MEDIT_MAX_FRAMES frames: PARC_ERR_INVALID names the first clip, by index, that
+ * has more; nothing is truncated).  As parc_mopt_set_clips: PARC_ERR_INVALID leaves the batch loaded before in place and usable; a failure
+ * after the validation leaves no batch (PARC_ERR_STATE until a parc_medit_set_clips succeeds).  The pair mask takes
+ * frames x ceil(frames / 64) 64-bit words of device memory per clip. */
+int parc_medit_set_clips(ParcMotionEdit *h, const ParcMotionOptClips *c);
+/* One pass over the uploaded clips.  Outputs (NULL = not copied): kept_counts [num_clips]; kept_inds [F], clip c's kept source frames
+ * (clip-local, ascending) from frame_off[c] on, -1 behind the first kept_counts[c]; total_kept = sum of kept_counts. */
+int parc_medit_run(ParcMotionEdit *h, int32_t *kept_counts_host, int32_t *kept_inds_host, int64_t *total_kept);
+/* The kept frames of the last run, clips in order: root_pos [total_kept][3], root_rot [total_kept][4], joint_rot [total_kept][B-1][4],
+ * contacts [total_kept][B]; every row is a copy of its source row. */
+int parc_medit_get_frames(ParcMotionEdit *h, float *root_pos_host, float *root_rot_host, float *joint_rot_host, float *contacts_host);
+/* TEST entry: the pair mask of clip `clip` of the last run, [frames][ceil(frames / 64)] words: bit (j & 63) of word (j >> 6) of row i is
+ * set when j > i and d(i, j) < hesitation_val. */
+int parc_medit_get_pair_rows(ParcMotionEdit *h, int32_t clip, uint64_t *rows_host);
+/* TEST entry: the flag words of the last run, [num_clips][PARC_MEDIT_FLAG_WORDS] each (bit j & 63 of word j >> 6 = frame j): after the
+ * ordered scan, and after the run filter (either may be NULL). */
+int parc_medit_get_flags(ParcMotionEdit *h, uint64_t *raw_host, uint64_t *filtered_host);
+/* Device time (hipEvents) of the last run, ms: fk, pairs, scan, and gather (the last parc_medit_get_frames). */
+int parc_medit_kernel_times(ParcMotionEdit *h, float *ms4);
+
 #ifdef __cplusplus
 }
 #endif

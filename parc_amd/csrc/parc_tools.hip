@@ -7,6 +7,7 @@
 #include "parc_clip_batch.hpp"       // the clip batch: the device views ClipArrays / FrameClips, validation and upload
 #include "parc_motion_opt.hpp"       // parc_mopt_*: the batched kinematic motion optimiser
 #include "parc_motion_terrain.hpp"   // parc_mterr_*: motion-terrain analysis
+#include "parc_motion_edit.hpp"      // parc_medit_*: stage 2's hesitation-frame removal
 #include "parc_motion_sampler.hpp"   // parc_msamp_*: the generator's motion-window sampler
 #include "parc_path_planner.hpp"     // parc_pathplan_*: stage 2's batched A* terrain path planner
 #include "parc_terrain_gen.hpp"      // parc_tgen_*: stage 2's BOXES / PATHS / STAIRS terrain generators, batched

@@ -100,6 +100,14 @@ class ParcMotionTerrainParams(C.Structure):
                 ("z_buf", C.c_double), ("jump_buf", C.c_double), ("max_jerk", C.c_double), ("sdf_mode", C.c_int32)]
 
 
+MEDIT_MAX_FRAMES, MEDIT_FLAG_WORDS = 4096, 64   # PARC_MEDIT_*
+
+
+class ParcMotionEditParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("model", ParcCharModel), ("hesitation_val", C.c_float),
+                ("hesitation_min_seq_len", C.c_int32)]
+
+
 class ParcMotionOptClips(C.Structure):
     _fields_ = [("num_clips", C.c_int32), ("frame_off_host", i64p), ("hf_off_host", i64p), ("cons_off_host", i64p),
                 ("hf_dims_host", i32p), ("hf_geom_host", f32p), ("hf_host", f32p), ("root_pos_host", f32p), ("root_rot_host", f32p),
@@ -317,7 +325,7 @@ def _signatures():
     P = C.POINTER
     vp, i32, i64, u32, u64, f32, cstr = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_char_p
     rc = C.c_int   # the return code that check() reads (the counts that three getters return are ints too)
-    u8p, u32p = P(C.c_uint8), P(u32)
+    u8p, u32p, u64p = P(C.c_uint8), P(u32), P(u64)
     plan_s, out_s = P(ParcMotionSamplerPlan), P(ParcMotionSamplerOutputs)
     return {
         # version
@@ -458,6 +466,15 @@ def _signatures():
         "parc_mpath_rollout": (rc, [vp, P(ParcMdmPathRolloutArgs), vp]),
         "parc_mpath_kernel_times": (rc, [vp, f32p]),
         "parc_mpath_describe": (rc, [vp, i64p]),
+        # hesitation-frame removal
+        "parc_medit_create": (rc, [P(ParcMotionEditParams), P(vp)]),
+        "parc_medit_destroy": (None, [vp]),
+        "parc_medit_set_clips": (rc, [vp, P(ParcMotionOptClips)]),
+        "parc_medit_run": (rc, [vp, i32p, i32p, P(i64)]),
+        "parc_medit_get_frames": (rc, [vp, f32p, f32p, f32p, f32p]),
+        "parc_medit_get_pair_rows": (rc, [vp, i32, u64p]),
+        "parc_medit_get_flags": (rc, [vp, u64p, u64p]),
+        "parc_medit_kernel_times": (rc, [vp, f32p]),
     }
 
 

@@ -12,7 +12,10 @@ clip's terrain, constraints in ``misc_data`` as plain arrays) and ``log/log_<nam
 source bounds are kept).  With ``save_flipped: true`` (or ``--save_flipped``) the mirrored copy of every optimised clip
 (``parc_2_kin_gen.py:490-495``) is written beside it as ``flipped/<name>_opt_flipped.pkl``; the copy carries the motion and the terrain only:
 ``hf_mask_inds`` and the body constraints of ``auto_compute_body_constraints`` (``opt:body_constraints``) are not mirrored into it
-(recompute the former with ``scripts/preprocess_motions.py`` on the flipped files).
+(recompute the former with ``scripts/preprocess_motions.py`` on the flipped files).  With ``remove_hesitation: true`` (or
+``--remove_hesitation``; default off) the optimised frames of the whole batch first go through ``medit_lib.remove_hesitation_frames``
+(``parc_2_kin_gen.py:467-470``; optional keys ``hesitation_val``, ``hesitation_min_seq_len``), so the file, its ``hf_mask_inds`` and the
+mirrored copy are those of the shortened clip; the body constraints stay those of the unshortened clip, as in the reference.
 """
 import argparse
 import os
@@ -44,6 +47,7 @@ def load_config(path):
     cfg.setdefault("log_every", 100)
     cfg.setdefault("hf_extras", False)
     cfg.setdefault("save_flipped", False)
+    cfg.setdefault("remove_hesitation", False)
     if int(cfg["frame_stride"]) < 1 or int(cfg["num_iters"]) < 0:
         raise ValueError("frame_stride must be >= 1 and num_iters >= 0")
     return cfg
@@ -96,6 +100,16 @@ def run(cfg):
     for f, c, h in zip(logs, clips, hist):
         f.write(f"{h[-1][0]}\t" + "\t".join(f"{h[-1][1][t.name]:.6g}" for t in mo.LossType) + "\n")
         f.close()
+    if cfg.get("remove_hesitation", False):   # parc_2_kin_gen.py:467-470: before compute_hf_extra_vals and the mirrored copy
+        from parc_amd import motion_edit as me
+        opt_clips = [mo.OptClip(fr["root_pos"], fr["root_rot"], fr["joint_rot"], fr["contacts"], c.hf, c.min_point, c.dx, c.fps, c.name)
+                     for c, fr in zip(clips, frames)]
+        remover = me.HesitationRemover(resolve(cfg["char_model"]), cfg["device"], float(cfg.get("hesitation_val", me.HESITATION_VAL)),
+                                       int(cfg.get("hesitation_min_seq_len", me.HESITATION_MIN_SEQ_LEN)))
+        short, _ = remover.remove(opt_clips)
+        for c, s in zip(opt_clips, short):
+            print(f"{c.name}: {c.num_frames - s.num_frames} hesitation frames removed ({c.num_frames} -> {s.num_frames})")
+        frames = [dict(root_pos=s.root_pos, root_rot=s.root_rot, joint_rot=s.joint_rot, contacts=s.contacts) for s in short]
     extras = [None] * len(clips)
     if cfg["hf_extras"]:
         from parc_amd.motion_terrain import MotionTerrainAnalyzer
@@ -126,12 +140,16 @@ def main(argv=None):
     ap.add_argument("--config", required=True)
     ap.add_argument("--hf_extras", action="store_true", help="write hf_mask_inds and recomputed hf_maxmin (config key hf_extras)")
     ap.add_argument("--save_flipped", action="store_true", help="also write flipped/<name>_opt_flipped.pkl, the mirrored copies (config key save_flipped)")
+    ap.add_argument("--remove_hesitation", action="store_true",
+                    help="drop the hesitation frames of the optimised clips before hf_extras and save_flipped (config key remove_hesitation)")
     args = ap.parse_args(argv)
     cfg = load_config(args.config)
     if args.hf_extras:
         cfg["hf_extras"] = True
     if args.save_flipped:
         cfg["save_flipped"] = True
+    if args.remove_hesitation:
+        cfg["remove_hesitation"] = True
     return run(cfg)
 
 
