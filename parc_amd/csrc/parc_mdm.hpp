@@ -25,6 +25,7 @@
 #include "parc_common.hpp"
 #include "parc_math.hpp"
 #include "parc_char.hpp"
+#include "parc_tool_handle.hpp"
 
 namespace mdm {
 using namespace parc;
@@ -444,13 +445,10 @@ struct EventList {                        // events with one lifetime, created a
 }  // namespace mdm
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------------------
-struct ParcMdm {
-    int device = 0;
+// ev: cond: 0, 1; step i: 2 + 3 i .. (before forward, between, after update); grown to the longest run
+struct ParcMdm : tool::CharHandle<parc::CharTree, mdm::EventList> {
     ParcMdmParams params{};
-    parc::CharTree host_model;
     mdm::Net net{};                       // the host's copy: dimensions, device pointers
-    DeviceArena mem;                      // create .. destroy
-    parc::CharTree *d_model = nullptr;
     mdm::Net *d_net = nullptr;
     mdm::Batch batch{};
     float *d_x0 = nullptr;                // [2 max_batch][T][D]
@@ -459,11 +457,9 @@ struct ParcMdm {
     size_t lds_fwd = 0, lds_upd = 0;
     bool have_conds = false, sampled = false;
     int last_steps = 0;
-    mdm::EventList ev;                    // cond: 0, 1; step i: 2 + 3 i .. (before forward, between, after update); grown to the longest run
-    ~ParcMdm() { (void)hipSetDevice(device); }
 };
 
-extern "C" void parc_mdm_destroy(ParcMdm *h) { delete h; }
+extern "C" void parc_mdm_destroy(ParcMdm *h) { tool::destroy(h); }
 
 namespace mdm {
 struct Packer {                           // the weights as the kernels read them: offsets first (as pointers), the base added after the upload
@@ -493,10 +489,8 @@ static void rebase(Lin &L, const float *base) { rebase(L.w, base); rebase(L.b, b
 
 extern "C" int parc_mdm_create(const ParcMdmParams *p, ParcMdm **out) {
     using namespace mdm;
-    if (!p || !out) return fail(PARC_ERR_INVALID, "mdm: null argument");
-    if (p->struct_size != sizeof(ParcMdmParams)) return fail(PARC_ERR_INVALID, "ParcMdmParams ABI mismatch (struct_size)");
+    PARC_TRY(tool::create_args("mdm", "ParcMdmParams", p, out, 2, false));
     const ParcCharModel &cm = p->model;
-    if (cm.num_bodies < 2 || cm.num_bodies > PARC_MAX_BODIES) return fail(PARC_ERR_INVALID, "mdm: num_bodies out of range");
     const int d = p->d_model, dh = p->d_hid, H = p->num_heads, T = p->seq_len, D = p->frame_dim;
     auto dim_ok = [](int v, int hi) { return v >= 16 && v <= hi && (v & 15) == 0; };
     if (!dim_ok(d, PARC_MDM_MAX_D_MODEL))
@@ -530,8 +524,7 @@ extern "C" int parc_mdm_create(const ParcMdmParams *p, ParcMdm **out) {
     for (long long i = 0; i < (long long)T * D; ++i)
         if (!std::isfinite(p->mean_host[i]) || !std::isfinite(p->std_host[i]) || p->std_host[i] == 0.f) return fail(PARC_ERR_INVALID, "mdm: the feature mean / std must be finite, the std non-zero");
     parc::CharTree M;
-    model_zero(M);
-    PARC_TRY(model_tree("mdm", cm, M));
+    PARC_TRY(tool::char_tree("mdm", cm, M));
 
     Net N{};
     N.d = d; N.H = H; N.hd = d / H; N.dh = dh; N.L = p->num_layers; N.T = T; N.nprev = p->num_prev_states; N.D = D;
@@ -598,52 +591,49 @@ extern "C" int parc_mdm_create(const ParcMdmParams *p, ParcMdm **out) {
         for (int i = 0; i <= counts[m]; ++i) mlps[m][i] = P.lin(mw[m].w[i], mw[m].b[i], mw[m].dims[i + 1], mw[m].dims[i]);
     N.mean = P.raw(p->mean_host, (size_t)T * D); N.std = P.raw(p->std_host, (size_t)T * D);
 
-    std::unique_ptr<ParcMdm> h(new (std::nothrow) ParcMdm());
-    if (!h) return fail(PARC_ERR_INVALID, "mdm: out of host memory");
-    h->device = p->device; h->params = *p; h->host_model = M;
-    h->params.weights_host = nullptr; h->params.weight_offsets_host = nullptr;   // the caller's buffers are not kept
-    const int TS = p->diffusion_timesteps;
-    h->sac.assign(p->sqrt_alphas_cumprod_host, p->sqrt_alphas_cumprod_host + TS);
-    h->somac.assign(p->sqrt_one_minus_alphas_cumprod_host, p->sqrt_one_minus_alphas_cumprod_host + TS);
-    h->pc1.assign(p->posterior_mean_coef1_host, p->posterior_mean_coef1_host + TS);
-    h->pc2.assign(p->posterior_mean_coef2_host, p->posterior_mean_coef2_host + TS);
-    h->pstd.assign(p->posterior_std_host, p->posterior_std_host + TS);
-    HIPCHK(hipSetDevice(p->device));
-    float *d_w = nullptr;
-    PARC_TRY(h->mem.alloc(d_w, (long long)P.v.size(), P.v.data()));
-    for (int c = 0; c < 4; ++c) { rebase(N.conv_w[c], d_w); rebase(N.conv_b[c], d_w); }
-    rebase(N.obs, d_w); rebase(N.time0, d_w); rebase(N.time1, d_w);
-    rebase(N.ind_embed, d_w); rebase(N.pe_time, d_w); rebase(N.pe_seq, d_w); rebase(N.mean, d_w); rebase(N.std, d_w);
-    for (int l = 0; l < N.L; ++l) {
-        Layer &Y = N.layer[l];
-        rebase(Y.qkv, d_w); rebase(Y.out, d_w); rebase(Y.l1, d_w); rebase(Y.l2, d_w);
-        rebase(Y.n1w, d_w); rebase(Y.n1b, d_w); rebase(Y.n2w, d_w); rebase(Y.n2b, d_w);
-    }
-    for (int m = 0; m < 3; ++m)
-        for (int i = 0; i <= counts[m]; ++i) rebase(mlps[m][i], d_w);
-    h->net = N;
-    PARC_TRY(h->mem.alloc(h->d_net, 1, &N));
-    PARC_TRY(model_upload(h->mem, M, h->d_model));
-    // the grid of k_mdm_forward: the workgroups one launch keeps resident (the scratch is indexed by the workgroup)
-    h->lds_fwd = lds_fwd;
-    h->lds_upd = (size_t)UPD_T * ((D + 11 * M.B) | 1) * sizeof(float);
-    HIPCHK(hipFuncSetAttribute((const void *)k_mdm_forward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_fwd));
-    HIPCHK(hipFuncSetAttribute((const void *)k_mdm_update, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_upd));
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, p->device));
-    int per_cu = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_mdm_forward, WG, h->lds_fwd));
-    if (per_cu < 1) return fail(PARC_ERR_INVALID, "mdm: k_mdm_forward does not fit a compute unit with " + std::to_string(h->lds_fwd) + " B of LDS");
-    h->slots = std::min(2 * p->max_batch, per_cu * prop.multiProcessorCount);
-    const long long B = p->max_batch;
-    PARC_TRY(h->mem.alloc(h->batch.tokens, B * NCOND * d));
-    PARC_TRY(h->mem.alloc(h->batch.prev, B * std::max(1, N.nprev) * D));
-    PARC_TRY(h->mem.alloc_fill(h->batch.flags, B));
-    PARC_TRY(h->mem.alloc_fill(h->batch.scratch, (long long)h->slots * (N.r1 + N.r2)));
-    PARC_TRY(h->mem.alloc_fill(h->d_x0, 2 * B * T * D));
-    PARC_TRY(h->ev.ensure(2 + 3 * 4));
-    *out = h.release();
-    return PARC_OK;
+    return tool::create("mdm", p->device, out, [&](ParcMdm &h) -> int {
+        h.params = *p; h.host_model = M;
+        h.params.weights_host = nullptr; h.params.weight_offsets_host = nullptr;   // the caller's buffers are not kept
+        const int TS = p->diffusion_timesteps;
+        h.sac.assign(p->sqrt_alphas_cumprod_host, p->sqrt_alphas_cumprod_host + TS);
+        h.somac.assign(p->sqrt_one_minus_alphas_cumprod_host, p->sqrt_one_minus_alphas_cumprod_host + TS);
+        h.pc1.assign(p->posterior_mean_coef1_host, p->posterior_mean_coef1_host + TS);
+        h.pc2.assign(p->posterior_mean_coef2_host, p->posterior_mean_coef2_host + TS);
+        h.pstd.assign(p->posterior_std_host, p->posterior_std_host + TS);
+        float *d_w = nullptr;
+        PARC_TRY(h.mem.alloc(d_w, (long long)P.v.size(), P.v.data()));
+        for (int c = 0; c < 4; ++c) { rebase(N.conv_w[c], d_w); rebase(N.conv_b[c], d_w); }
+        rebase(N.obs, d_w); rebase(N.time0, d_w); rebase(N.time1, d_w);
+        rebase(N.ind_embed, d_w); rebase(N.pe_time, d_w); rebase(N.pe_seq, d_w); rebase(N.mean, d_w); rebase(N.std, d_w);
+        for (int l = 0; l < N.L; ++l) {
+            Layer &Y = N.layer[l];
+            rebase(Y.qkv, d_w); rebase(Y.out, d_w); rebase(Y.l1, d_w); rebase(Y.l2, d_w);
+            rebase(Y.n1w, d_w); rebase(Y.n1b, d_w); rebase(Y.n2w, d_w); rebase(Y.n2b, d_w);
+        }
+        for (int m = 0; m < 3; ++m)
+            for (int i = 0; i <= counts[m]; ++i) rebase(mlps[m][i], d_w);
+        h.net = N;
+        PARC_TRY(h.mem.alloc(h.d_net, 1, &N));
+        PARC_TRY(model_upload(h.mem, M, h.d_model));
+        // the grid of k_mdm_forward: the workgroups one launch keeps resident (the scratch is indexed by the workgroup)
+        h.lds_fwd = lds_fwd;
+        h.lds_upd = (size_t)UPD_T * ((D + 11 * M.B) | 1) * sizeof(float);
+        HIPCHK(hipFuncSetAttribute((const void *)k_mdm_forward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h.lds_fwd));
+        HIPCHK(hipFuncSetAttribute((const void *)k_mdm_update, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h.lds_upd));
+        hipDeviceProp_t prop;
+        HIPCHK(hipGetDeviceProperties(&prop, p->device));
+        int per_cu = 0;
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_mdm_forward, WG, h.lds_fwd));
+        if (per_cu < 1) return fail(PARC_ERR_INVALID, "mdm: k_mdm_forward does not fit a compute unit with " + std::to_string(h.lds_fwd) + " B of LDS");
+        h.slots = std::min(2 * p->max_batch, per_cu * prop.multiProcessorCount);
+        const long long B = p->max_batch;
+        PARC_TRY(h.mem.alloc(h.batch.tokens, B * NCOND * d));
+        PARC_TRY(h.mem.alloc(h.batch.prev, B * std::max(1, N.nprev) * D));
+        PARC_TRY(h.mem.alloc_fill(h.batch.flags, B));
+        PARC_TRY(h.mem.alloc_fill(h.batch.scratch, (long long)h.slots * (N.r1 + N.r2)));
+        PARC_TRY(h.mem.alloc_fill(h.d_x0, 2 * B * T * D));
+        return h.ev.ensure(2 + 3 * 4);
+    });
 }
 
 static int mdm_check_conds(ParcMdm *h, const ParcMdmConds *c) {
@@ -658,10 +648,9 @@ static int mdm_check_conds(ParcMdm *h, const ParcMdmConds *c) {
 static int mdm_launch_cond(ParcMdm *h, const ParcMdmConds *c, float *tokens_out, uint64_t *mask_out, float *x_draw, uint64_t seed, uint64_t first, hipStream_t st) {
     h->batch.n = c->n;
     const int grid = std::min(c->n, h->slots);
-    hipLaunchKernelGGL(mdm::k_mdm_cond, dim3((unsigned)grid), dim3(mdm::WG), 16 * 20 * sizeof(float), st, h->d_net, h->batch, c->hf, c->target, c->prev_state,
+    PARC_TRY(tool::launch(mdm::k_mdm_cond, dim3((unsigned)grid), dim3(mdm::WG), 16 * 20 * sizeof(float), st, h->d_net, h->batch, c->hf, c->target, c->prev_state,
                        c->obs_flag, c->target_flag, c->prev_state_flag, c->noise_ind, tokens_out, (unsigned long long *)mask_out, x_draw,
-                       (unsigned long long)seed, (unsigned long long)first);
-    HIPCHK(hipGetLastError());
+                       (unsigned long long)seed, (unsigned long long)first));
     h->have_conds = true;
     return PARC_OK;
 }
@@ -674,8 +663,7 @@ extern "C" int parc_mdm_embed_conds(ParcMdm *h, const ParcMdmConds *c, float *to
 
 static int mdm_launch_forward(ParcMdm *h, float *x, int t, int pass, int two, float *x0_out, hipStream_t st) {
     const int rows = two ? 2 * h->batch.n : h->batch.n;
-    hipLaunchKernelGGL(mdm::k_mdm_forward, dim3((unsigned)std::min(rows, h->slots)), dim3(mdm::WG), h->lds_fwd, st, h->d_net, h->batch, x, t, pass, two, x0_out);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(mdm::k_mdm_forward, dim3((unsigned)std::min(rows, h->slots)), dim3(mdm::WG), h->lds_fwd, st, h->d_net, h->batch, x, t, pass, two, x0_out));
     return PARC_OK;
 }
 
@@ -691,9 +679,8 @@ extern "C" int parc_mdm_forward(ParcMdm *h, float *x, int32_t t, int32_t pass, f
 static int mdm_launch_update(ParcMdm *h, int n, const float *x0, const float *x0_nc, float gs, float *x, int last, float c0, float ct, float cn, const float *noise,
                              int draw, uint64_t seed, uint64_t first, unsigned step, float *x0p, hipStream_t st) {
     const long long frames = (long long)n * h->net.T;
-    hipLaunchKernelGGL(mdm::k_mdm_update, dim3(blocks(frames, mdm::UPD_T)), dim3(mdm::UPD_T), h->lds_upd, st, h->d_net, h->d_model, frames, x0, x0_nc, gs, x, last, c0,
-                       ct, cn, noise, draw, (unsigned long long)seed, (unsigned long long)first, step, x0p);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(mdm::k_mdm_update, dim3(blocks(frames, mdm::UPD_T)), dim3(mdm::UPD_T), h->lds_upd, st, h->d_net, h->d_model, frames, x0, x0_nc, gs, x, last, c0,
+                       ct, cn, noise, draw, (unsigned long long)seed, (unsigned long long)first, step, x0p));
     return PARC_OK;
 }
 
@@ -756,9 +743,8 @@ extern "C" int parc_mdm_draw_noise(ParcMdm *h, int32_t n, uint64_t seed, uint64_
     HIPCHK(hipSetDevice(h->device));
     const int per = h->net.T * h->net.D;
     const long long total = (long long)n * per;
-    hipLaunchKernelGGL(mdm::k_mdm_draw, dim3(blocks(total, 256)), dim3(256), 0, (hipStream_t)stream, out, total, per, (unsigned long long)seed,
-                       (unsigned long long)first_index, (unsigned)step);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(mdm::k_mdm_draw, dim3(blocks(total, 256)), dim3(256), 0, (hipStream_t)stream, out, total, per, (unsigned long long)seed,
+                       (unsigned long long)first_index, (unsigned)step));
     return PARC_OK;
 }
 

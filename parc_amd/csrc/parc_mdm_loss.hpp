@@ -29,6 +29,7 @@
 #include "parc_common.hpp"
 #include "parc_math.hpp"
 #include "parc_char.hpp"
+#include "parc_tool_handle.hpp"
 
 namespace mloss {
 using namespace parc;
@@ -309,52 +310,31 @@ __global__ void __launch_bounds__(THREADS) k_mloss(const Model *Mp, Args A, Work
 }  // namespace mloss
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------------------
-struct ParcMotionLoss {
-    int device = 0;
-    mloss::Model host_model;
-    DeviceArena mem;                      // create .. destroy: d_model
-    mloss::Model *d_model = nullptr;
-    DeviceArena work_mem;                 // the workspace, grown to the largest N x T seen
+struct ParcMotionLoss : tool::CharHandle<mloss::Model, DeviceEvents<2>> {   // mem: d_model
+    DeviceArena work_mem;                // the workspace, grown to the largest N x T seen
     mloss::Work W{};
     long long work_frames = 0;
-    DeviceEvents<2> ev;
     bool ran = false;
-    ~ParcMotionLoss() { (void)hipSetDevice(device); }   // the members release the rest
 };
 
-extern "C" void parc_mloss_destroy(ParcMotionLoss *h) { delete h; }
+extern "C" void parc_mloss_destroy(ParcMotionLoss *h) { tool::destroy(h); }
 
 extern "C" int parc_mloss_create(const ParcMotionLossParams *p, ParcMotionLoss **out) {
-    if (!p || !out) return fail(PARC_ERR_INVALID, "mloss: null argument");
-    if (p->struct_size != sizeof(ParcMotionLossParams)) return fail(PARC_ERR_INVALID, "ParcMotionLossParams ABI mismatch (struct_size)");
+    PARC_TRY(tool::create_args("mloss", "ParcMotionLossParams", p, out, 2, true));
     const ParcCharModel &cm = p->model;
-    if (cm.num_bodies < 2 || cm.num_bodies > PARC_MAX_BODIES) return fail(PARC_ERR_INVALID, "mloss: num_bodies out of range");
-    if (cm.dof_size < 0 || cm.dof_size > PARC_MAX_DOFS) return fail(PARC_ERR_INVALID, "mloss: dof_size out of range");
     if (!(p->sequence_fps > 0.f)) return fail(PARC_ERR_INVALID, "mloss: sequence_fps must be > 0");
     if (p->num_prev_states < 1) return fail(PARC_ERR_INVALID, "mloss: num_prev_states must be >= 1");
     if (p->loss_fn != PARC_MLOSS_SQUARED_L2 && p->loss_fn != PARC_MLOSS_PSEUDO_HUBER)
         return fail(PARC_ERR_INVALID, "mloss: loss_fn must be PARC_MLOSS_SQUARED_L2 or PARC_MLOSS_PSEUDO_HUBER");
     mloss::Model M;
-    model_zero(M);
-    PARC_TRY(model_tree("mloss", cm, M));
+    PARC_TRY(tool::char_tree("mloss", cm, M));
     int used = 0;                         // the dofs must tile [0, dof_size): every feature column then has one writer
-    for (int b = 1; b < M.B; ++b) {
-        const int dd = cm.joint_type[b] == PARC_JOINT_HINGE ? 1 : (cm.joint_type[b] == PARC_JOINT_SPHERICAL ? 3 : 0);
-        if (dd && (cm.dof_idx[b] < 0 || cm.dof_idx[b] + dd > cm.dof_size)) return fail(PARC_ERR_INVALID, "mloss: dof_idx out of range");
-        used += dd;
-    }
+    PARC_TRY(tool::char_dofs("mloss", cm, used));
     if (used != cm.dof_size) return fail(PARC_ERR_INVALID, "mloss: the joints' dofs do not add up to dof_size");
     for (int t = 0; t < mloss::NT; ++t) M.w[t] = p->weights[t];
     M.inv_dt = p->sequence_fps; M.target_eps = p->target_dir_len_eps; M.nprev = p->num_prev_states;
     M.use_pos = p->use_pos_loss != 0; M.use_target = p->use_target_loss != 0; M.huber = p->loss_fn == PARC_MLOSS_PSEUDO_HUBER;
-    std::unique_ptr<ParcMotionLoss> h(new (std::nothrow) ParcMotionLoss());
-    if (!h) return fail(PARC_ERR_INVALID, "mloss: out of host memory");
-    h->device = p->device; h->host_model = M;
-    HIPCHK(hipSetDevice(p->device));
-    PARC_TRY(model_upload(h->mem, M, h->d_model));
-    PARC_TRY(h->ev.create());
-    *out = h.release();
-    return PARC_OK;
+    return tool::create("mloss", p->device, M, out);
 }
 
 extern "C" int parc_mloss_eval(ParcMotionLoss *h, const ParcMotionLossArgs *a, void *stream) {
@@ -387,8 +367,7 @@ extern "C" int parc_mloss_eval(ParcMotionLoss *h, const ParcMotionLossArgs *a, v
     A.root_pos = a->root_pos; A.root_rot = a->root_rot; A.joint_rot = a->joint_rot; A.contacts = a->contacts;
     A.target_dir = a->target_dir; A.terms = a->terms; A.grad = a->grad;
     HIPCHK(hipEventRecord(h->ev[0], st));
-    hipLaunchKernelGGL(mloss::k_mloss, dim3((unsigned)a->n), dim3(mloss::THREADS), 0, st, h->d_model, A, h->W);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(mloss::k_mloss, dim3((unsigned)a->n), dim3(mloss::THREADS), 0, st, h->d_model, A, h->W));
     HIPCHK(hipEventRecord(h->ev[1], st));
     h->ran = true;
     return PARC_OK;
@@ -396,8 +375,6 @@ extern "C" int parc_mloss_eval(ParcMotionLoss *h, const ParcMotionLossArgs *a, v
 
 extern "C" int parc_mloss_kernel_times(ParcMotionLoss *h, float *ms1) {
     if (!h || !ms1) return fail(PARC_ERR_INVALID, "mloss: null argument");
-    if (!h->ran) return fail(PARC_ERR_STATE, "mloss: nothing evaluated yet");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipEventSynchronize(h->ev[1]));
-    return h->ev.elapsed(ms1[0], 0, 1);
+    const tool::Span spans[] = {{h->ran, 0, 1}};
+    return tool::span_times("mloss: nothing evaluated yet", h->device, h->ev, spans, ms1);
 }

@@ -10,6 +10,7 @@
 // integer atomic per row, read back once per window.
 #pragma once
 #include "parc_mdm.hpp"
+#include "parc_tool_handle.hpp"
 
 namespace mpath {
 using namespace parc;
@@ -201,14 +202,14 @@ __global__ void __launch_bounds__(CW) k_mpath_append(const mdm::Net *Np, const C
 }  // namespace mpath
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------------------
-struct ParcMdmPath {
-    int device = 0;
+// device: the generator's; ev: window w: 4 w .. 4 w + 3 (around k_mpath_cond, around k_mpath_append)
+struct ParcMdmPath : tool::Handle<mdm::EventList> {
     ParcMdmPathParams params{};
     ParcMdm *mdm = nullptr;
     mpath::Cfg cfg{};
     int T = 0, nprev = 0, D = 0, B = 0, FD = 0, start = 0, step = 0, max_frames = 0, max_windows = 0, max_batch = 0;
     size_t lds_cond = 0, lds_app = 0;
-    DeviceArena mem, scene_mem;
+    DeviceArena scene_mem;
     mpath::Scene scene{};
     bool have_scene = false, rolled = false;
     float *d_prev = nullptr, *d_prevstd = nullptr, *d_hf = nullptr, *d_target = nullptr, *d_canon = nullptr, *d_x = nullptr, *d_plan = nullptr;
@@ -216,21 +217,19 @@ struct ParcMdmPath {
     long long *d_row_ids = nullptr, *d_path_ids = nullptr;   // d_path_ids [P] lives with the scene
     int *h_counter = nullptr;                      // pinned
     std::vector<int> ts;
-    mdm::EventList ev;                             // window w: 4 w .. 4 w + 3 (around k_mpath_cond, around k_mpath_append)
     int last_windows = 0, last_launches = 0, last_frames = 0;
-    ~ParcMdmPath() { (void)hipSetDevice(device); if (h_counter) (void)hipHostFree(h_counter); }
+    ~ParcMdmPath() { if (h_counter) (void)hipHostFree(h_counter); }
     mpath::CondOut own() const {
         const int mb = max_batch;
         return mpath::CondOut{d_hf, d_target, d_prevstd, d_ints, d_ints + mb, d_ints + 2 * mb, d_ints + 3 * mb, d_ints + 4 * mb, d_ints + 5 * mb, d_ints + 6 * mb, d_canon};
     }
 };
 
-extern "C" void parc_mpath_destroy(ParcMdmPath *h) { delete h; }
+extern "C" void parc_mpath_destroy(ParcMdmPath *h) { tool::destroy(h); }
 
 extern "C" int parc_mpath_create(const ParcMdmPathParams *p, ParcMdmPath **out) {
     using namespace mpath;
-    if (!p || !out) return fail(PARC_ERR_INVALID, "mpath: null argument");
-    if (p->struct_size != sizeof(ParcMdmPathParams)) return fail(PARC_ERR_INVALID, "ParcMdmPathParams ABI mismatch (struct_size)");
+    PARC_TRY(tool::create_args("mpath", "ParcMdmPathParams", p, out));
     if (!p->mdm) return fail(PARC_ERR_INVALID, "mpath: mdm is null (the generator the rollout drives)");
     ParcMdm *g = p->mdm;
     const int T = g->net.T, nprev = g->net.nprev, B = g->host_model.B;
@@ -250,53 +249,52 @@ extern "C" int parc_mpath_create(const ParcMdmPathParams *p, ParcMdmPath **out) 
     if (p->ddim_stride < 1 || p->ddim_stride > g->params.diffusion_timesteps) return fail(PARC_ERR_INVALID, "mpath: ddim_stride must be 1 .. diffusion_timesteps");
     if (!std::isfinite(p->cfg_scale)) return fail(PARC_ERR_INVALID, "mpath: cfg_scale must be finite");
     if (p->left_foot < 0 || p->left_foot >= B || p->right_foot < 0 || p->right_foot >= B) return fail(PARC_ERR_INVALID, "mpath: left_foot / right_foot body id out of range");
-    std::unique_ptr<ParcMdmPath> h(new (std::nothrow) ParcMdmPath());
-    if (!h) return fail(PARC_ERR_INVALID, "mpath: out of host memory");
-    h->device = g->device; h->params = *p; h->mdm = g;
-    h->T = T; h->nprev = nprev; h->D = g->net.D; h->B = B; h->FD = frame_floats(B); h->start = start; h->step = start - nprev; h->max_batch = g->params.max_batch;
     // the longest rollout (mdm_path.py:340-377): windows until total * dt > max_motion_length, the last one kept to its end
+    const int step = start - nprev;
     const double dt = 1.0 / (double)p->sequence_fps;
     long long total = start;
     int W = 1;
     for (;;) {
-        total += h->step; ++W;
+        total += step; ++W;
         if ((double)total * dt > (double)p->max_motion_length) break;
         if (W >= KEY_WINDOWS) return fail(PARC_ERR_INVALID, "mpath: max_motion_length needs more than " + std::to_string(KEY_WINDOWS) + " windows");
     }
-    h->max_windows = W;
-    h->max_frames = start + (W - 2) * h->step + (T - nprev);
-    Cfg &c = h->cfg;
-    c.lookahead = p->next_node_lookahead; c.lf = p->left_foot; c.rf = p->right_foot;
-    c.target_flag = p->target_condition_key != 0; c.prev_flag = p->prev_state_ind_key != 0; c.max_h = p->max_h; c.done_radius = 0.5f;
-    // torch.linspace(-d n_neg, d n_pos, 31) in fp32: start + step i below the middle, end - step (30 - i) from it on
-    auto linspace = [](float d, int nneg, int npos, float *o) {
-        const float a = 0.f - (float)((double)d * nneg), b = 0.f + (float)((double)d * npos), st = (b - a) / (float)(G - 1);
-        for (int i = 0; i < G; ++i) o[i] = i < G / 2 ? a + st * (float)i : b - st * (float)(G - 1 - i);
-    };
-    linspace(p->grid_dx, p->num_x_neg, p->num_x_pos, c.gx);
-    linspace(p->grid_dy, p->num_y_neg, p->num_y_pos, c.gy);
-    for (int t = 0; t < g->params.diffusion_timesteps; t += p->ddim_stride) h->ts.insert(h->ts.begin(), t);   // reversed(range(0, timesteps, stride))
-    if ((int)h->ts.size() > PARC_MDM_MAX_STEPS) return fail(PARC_ERR_INVALID, "mpath: ddim_stride gives more than PARC_MDM_MAX_STEPS steps");
-    HIPCHK(hipSetDevice(h->device));
-    const long long mb = h->max_batch;
-    PARC_TRY(h->mem.alloc_fill(h->d_prev, mb * nprev * h->FD));
-    PARC_TRY(h->mem.alloc_fill(h->d_prevstd, mb * nprev * h->D));
-    PARC_TRY(h->mem.alloc_fill(h->d_hf, mb * G * G));
-    PARC_TRY(h->mem.alloc_fill(h->d_target, mb * 2));
-    PARC_TRY(h->mem.alloc_fill(h->d_canon, mb * 8));
-    PARC_TRY(h->mem.alloc_fill(h->d_x, mb * T * h->D));
-    PARC_TRY(h->mem.alloc_fill(h->d_ints, mb * 7));
-    PARC_TRY(h->mem.alloc_fill(h->d_counter, h->max_windows));
-    PARC_TRY(h->mem.alloc_fill(h->d_row_ids, mb));
-    HIPCHK(hipHostMalloc((void **)&h->h_counter, sizeof(int)));
-    h->lds_cond = (size_t)(nprev + 1) * ((h->D + 11 * B) | 1) * sizeof(float);
-    h->lds_app = (size_t)CW * (h->D | 1) * sizeof(float);
-    if (h->lds_cond > 160 * 1024) return fail(PARC_ERR_INVALID, "mpath: num_prev_states too large for the conditions kernel's LDS");
-    HIPCHK(hipFuncSetAttribute((const void *)k_mpath_cond, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_cond));
-    HIPCHK(hipFuncSetAttribute((const void *)k_mpath_append, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_app));
-    PARC_TRY(h->ev.ensure(4));
-    *out = h.release();
-    return PARC_OK;
+    std::vector<int> ts;
+    for (int t = 0; t < g->params.diffusion_timesteps; t += p->ddim_stride) ts.insert(ts.begin(), t);   // reversed(range(0, timesteps, stride))
+    if ((int)ts.size() > PARC_MDM_MAX_STEPS) return fail(PARC_ERR_INVALID, "mpath: ddim_stride gives more than PARC_MDM_MAX_STEPS steps");
+    return tool::create("mpath", g->device, out, [&](ParcMdmPath &h) -> int {
+        h.params = *p; h.mdm = g; h.ts = ts;
+        h.T = T; h.nprev = nprev; h.D = g->net.D; h.B = B; h.FD = frame_floats(B); h.start = start; h.step = step; h.max_batch = g->params.max_batch;
+        h.max_windows = W;
+        h.max_frames = start + (W - 2) * step + (T - nprev);
+        Cfg &c = h.cfg;
+        c.lookahead = p->next_node_lookahead; c.lf = p->left_foot; c.rf = p->right_foot;
+        c.target_flag = p->target_condition_key != 0; c.prev_flag = p->prev_state_ind_key != 0; c.max_h = p->max_h; c.done_radius = 0.5f;
+        // torch.linspace(-d n_neg, d n_pos, 31) in fp32: start + step i below the middle, end - step (30 - i) from it on
+        auto linspace = [](float d, int nneg, int npos, float *o) {
+            const float a = 0.f - (float)((double)d * nneg), b = 0.f + (float)((double)d * npos), st = (b - a) / (float)(G - 1);
+            for (int i = 0; i < G; ++i) o[i] = i < G / 2 ? a + st * (float)i : b - st * (float)(G - 1 - i);
+        };
+        linspace(p->grid_dx, p->num_x_neg, p->num_x_pos, c.gx);
+        linspace(p->grid_dy, p->num_y_neg, p->num_y_pos, c.gy);
+        const long long mb = h.max_batch;
+        PARC_TRY(h.mem.alloc_fill(h.d_prev, mb * nprev * h.FD));
+        PARC_TRY(h.mem.alloc_fill(h.d_prevstd, mb * nprev * h.D));
+        PARC_TRY(h.mem.alloc_fill(h.d_hf, mb * G * G));
+        PARC_TRY(h.mem.alloc_fill(h.d_target, mb * 2));
+        PARC_TRY(h.mem.alloc_fill(h.d_canon, mb * 8));
+        PARC_TRY(h.mem.alloc_fill(h.d_x, mb * T * h.D));
+        PARC_TRY(h.mem.alloc_fill(h.d_ints, mb * 7));
+        PARC_TRY(h.mem.alloc_fill(h.d_counter, h.max_windows));
+        PARC_TRY(h.mem.alloc_fill(h.d_row_ids, mb));
+        HIPCHK(hipHostMalloc((void **)&h.h_counter, sizeof(int)));
+        h.lds_cond = (size_t)(nprev + 1) * ((h.D + 11 * B) | 1) * sizeof(float);
+        h.lds_app = (size_t)CW * (h.D | 1) * sizeof(float);
+        if (h.lds_cond > 160 * 1024) return fail(PARC_ERR_INVALID, "mpath: num_prev_states too large for the conditions kernel's LDS");
+        HIPCHK(hipFuncSetAttribute((const void *)k_mpath_cond, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h.lds_cond));
+        HIPCHK(hipFuncSetAttribute((const void *)k_mpath_append, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h.lds_app));
+        return h.ev.ensure(4);
+    });
 }
 
 extern "C" int parc_mpath_set_scene(ParcMdmPath *h, const float *hf_host, int32_t num_terrains, int32_t dim_x, int32_t dim_y, const float *min_points_host, float dx,
@@ -345,17 +343,15 @@ extern "C" int parc_mpath_set_scene(ParcMdmPath *h, const float *hf_host, int32_
 
 static int mpath_launch_cond(ParcMdmPath *h, const float *prev, const mpath::CondOut &O, int first, int ind_val, int *not_done, float *x, const float *noise, int draw,
                              uint64_t seed, unsigned window, hipStream_t st) {
-    hipLaunchKernelGGL(mpath::k_mpath_cond, dim3((unsigned)h->scene.N), dim3(mpath::CW), h->lds_cond, st, h->mdm->d_net, h->mdm->d_model, h->scene, h->cfg, prev, O, first,
-                       ind_val, not_done, x, noise, draw, (unsigned long long)seed, h->d_row_ids, window);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(mpath::k_mpath_cond, dim3((unsigned)h->scene.N), dim3(mpath::CW), h->lds_cond, st, h->mdm->d_net, h->mdm->d_model, h->scene, h->cfg, prev, O, first,
+                       ind_val, not_done, x, noise, draw, (unsigned long long)seed, h->d_row_ids, window));
     return PARC_OK;
 }
 
 static int mpath_launch_append(ParcMdmPath *h, int n, const float *x, const float *prevstd, const int *ind, const float *canon, int guided, int lo, int hi, int off,
                                float *frames, int max_frames, float *prev_next, const int *done, int *final_frame, int total, hipStream_t st) {
-    hipLaunchKernelGGL(mpath::k_mpath_append, dim3(blocks((long long)n * h->T, mpath::CW)), dim3(mpath::CW), h->lds_app, st, h->mdm->d_net, h->mdm->d_model, n, x, prevstd,
-                       ind, canon, guided, lo, hi, off, frames, max_frames, prev_next, h->start - h->nprev, h->start, done, final_frame, total);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(mpath::k_mpath_append, dim3(blocks((long long)n * h->T, mpath::CW)), dim3(mpath::CW), h->lds_app, st, h->mdm->d_net, h->mdm->d_model, n, x, prevstd,
+                       ind, canon, guided, lo, hi, off, frames, max_frames, prev_next, h->start - h->nprev, h->start, done, final_frame, total));
     return PARC_OK;
 }
 
@@ -412,9 +408,8 @@ extern "C" int parc_mpath_rollout(ParcMdmPath *h, const ParcMdmPathRolloutArgs *
         if (a->rel_height_host) { rel = h->d_plan; HIPCHK(hipMemcpyAsync(rel, a->rel_height_host, (size_t)h->scene.P * sizeof(float), hipMemcpyHostToDevice, st)); }
         if (a->heading_host) { head = h->d_plan + h->scene.P; HIPCHK(hipMemcpyAsync(head, a->heading_host, (size_t)h->scene.P * sizeof(float), hipMemcpyHostToDevice, st)); }
         if (rel || head) HIPCHK(hipStreamSynchronize(st));
-        hipLaunchKernelGGL(mpath::k_mpath_begin, dim3(blocks((long long)n * nprev, mpath::CW)), dim3(mpath::CW), 0, st, h->mdm->d_model, h->scene, nprev, h->d_prev, rel, head,
-                           a->heading_mode == PARC_MPATH_HEADING_RANDOM, (unsigned long long)a->seed, h->d_path_ids);
-        HIPCHK(hipGetLastError());
+        PARC_TRY(tool::launch(mpath::k_mpath_begin, dim3(blocks((long long)n * nprev, mpath::CW)), dim3(mpath::CW), 0, st, h->mdm->d_model, h->scene, nprev, h->d_prev, rel, head,
+                           a->heading_mode == PARC_MPATH_HEADING_RANDOM, (unsigned long long)a->seed, h->d_path_ids));
         ++launches;
     } else
         HIPCHK(hipMemcpyAsync(h->d_prev, a->prev_frames, (size_t)n * nprev * h->FD * sizeof(float), hipMemcpyDeviceToDevice, st));

@@ -29,6 +29,7 @@
 #include "parc_char.hpp"
 #include "parc_grid.hpp"
 #include "parc_clip_batch.hpp"
+#include "parc_tool_handle.hpp"
 
 namespace maug {
 using namespace parc;
@@ -375,7 +376,7 @@ __global__ void k_maug_validate(ClipArrays K, Cfg G, PlanD P, long long n, int *
 }  // namespace maug
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------------------
-struct ParcMotionAug {
+struct ParcMotionAug : tool::CharHandle<parc::CharTree, DeviceEvents<8>> {   // mem: d_model, status
     struct Library {                      // what one parc_maug_set_clips loads
         DeviceArena mem;
         ClipArrays K{};
@@ -387,27 +388,18 @@ struct ParcMotionAug {
         int n = 0;
         long long F = 0, cells = 0;
     };
-    int device = 0;
-    parc::CharTree host_model;
     ParcMotionAugParams params{};
-    DeviceArena mem;                      // create .. destroy: d_model, d_status
-    parc::CharTree *d_model = nullptr;
     maug::Cfg cfg{};
     std::unique_ptr<Library> lib;
     std::unique_ptr<Result> res;
-    int *d_status = nullptr;
-    DeviceEvents<8> ev;
+    tool::StatusWords status;             // 0: the run kernels' word (parc_maug_plan_status), 1: the validate pass'
     bool drew = false;
-    ~ParcMotionAug() { (void)hipSetDevice(device); }   // the members release the rest
 };
 
-extern "C" void parc_maug_destroy(ParcMotionAug *h) { delete h; }
+extern "C" void parc_maug_destroy(ParcMotionAug *h) { tool::destroy(h); }
 
 extern "C" int parc_maug_create(const ParcMotionAugParams *p, ParcMotionAug **out) {
-    if (!p || !out) return fail(PARC_ERR_INVALID, "maug: null argument");
-    if (p->struct_size != sizeof(ParcMotionAugParams)) return fail(PARC_ERR_INVALID, "ParcMotionAugParams ABI mismatch (struct_size)");
-    const ParcCharModel &cm = p->model;
-    if (cm.num_bodies < 2 || cm.num_bodies > PARC_MAX_BODIES) return fail(PARC_ERR_INVALID, "maug: num_bodies out of range");
+    PARC_TRY(tool::create_args("maug", "ParcMotionAugParams", p, out, 2, false));
     if (p->mode < PARC_MAUG_HEIGHT_SCALE || p->mode > PARC_MAUG_NONE)
         return fail(PARC_ERR_INVALID, "maug: terrain_aug_type must be HEIGHT_SCALE, BOXES_ALONG_PATH or NONE");
     if (p->terrain_padding_size < 0 || p->terrain_padding_size > PARC_MAUG_MAX_DIM)
@@ -415,8 +407,7 @@ extern "C" int parc_maug_create(const ParcMotionAugParams *p, ParcMotionAug **ou
     const float ranges[][2] = {{p->min_heading_angle, p->max_heading_angle}, {p->x_scale[0], p->x_scale[1]}, {p->y_scale[0], p->y_scale[1]}};
     for (const auto &r : ranges) if (!std::isfinite(r[0]) || !std::isfinite(r[1])) return fail(PARC_ERR_INVALID, "maug: a heading or scale range is not finite");
     parc::CharTree M;
-    model_zero(M);
-    PARC_TRY(model_tree("maug", cm, M));
+    PARC_TRY(tool::char_tree("maug", p->model, M));
     maug::Cfg G{};
     G.mode = p->mode; G.pad = p->terrain_padding_size; G.slice = p->slice_terrain != 0; G.B = M.B;
     G.head0 = p->min_heading_angle; G.head1 = p->max_heading_angle;
@@ -451,15 +442,10 @@ extern "C" int parc_maug_create(const ParcMotionAugParams *p, ParcMotionAug **ou
         G.nb0 = p->min_num_boxes; G.nb1 = p->max_num_boxes;
         G.len0 = p->min_len; G.len1 = p->max_len; G.ang0 = p->min_angle; G.ang1 = p->max_angle; G.bh0 = p->min_h; G.bh1 = p->max_h;
     }
-    std::unique_ptr<ParcMotionAug> h(new (std::nothrow) ParcMotionAug());   // every failure below is a plain return
-    if (!h) return fail(PARC_ERR_INVALID, "maug: out of host memory");
-    h->device = p->device; h->host_model = M; h->params = *p; h->cfg = G;
-    HIPCHK(hipSetDevice(p->device));
-    PARC_TRY(model_upload(h->mem, M, h->d_model));
-    PARC_TRY(h->mem.alloc_fill(h->d_status, 2));
-    PARC_TRY(h->ev.create());
-    *out = h.release();
-    return PARC_OK;
+    return tool::create("maug", p->device, M, out, [&](ParcMotionAug &h) -> int {
+        h.params = *p; h.cfg = G;
+        return h.status.alloc(h.mem, 2);
+    });
 }
 
 // as parc_msamp_set_clips: validate; release the old library (and its results); build the new one in a local; install it last
@@ -491,9 +477,8 @@ extern "C" int parc_maug_set_clips(ParcMotionAug *h, const ParcMotionOptClips *c
     for (int i = 0; i < C; ++i) { run += (float)(len[(size_t)i] / wsum); cdf[(size_t)i] = run; }
     HIPCHK(hipSetDevice(h->device));
     h->res.reset();
-    h->lib.reset();
-    std::unique_ptr<ParcMotionAug::Library> nl(new (std::nothrow) ParcMotionAug::Library());
-    if (!nl) return fail(PARC_ERR_INVALID, "maug: out of host memory");
+    std::unique_ptr<ParcMotionAug::Library> nl;
+    PARC_TRY(tool::renew("maug", h->lib, nl));
     PARC_TRY(clip_batch_upload(nl->mem, nl->K, c, cb, h->host_model.B));
     maug::Lib &L = nl->L;
     if (info->hf_maxmin_host) PARC_TRY(nl->mem.alloc(L.maxmin, 2 * cb.ncell, info->hf_maxmin_host));
@@ -517,7 +502,7 @@ static maug::PlanD maug_plan(const ParcMotionAugPlan *p) {
 
 static int maug_check_plan(ParcMotionAug *h, const ParcMotionAugPlan *p) {
     if (!h || !p) return fail(PARC_ERR_INVALID, "maug: null argument");
-    if (!h->lib) return fail(PARC_ERR_STATE, "maug: parc_maug_set_clips first");
+    if (!h->lib) return tool::no_clips("maug");
     if (p->n < 1) return fail(PARC_ERR_INVALID, "maug: n must be >= 1");
     if (!p->src_clip || !p->start_frame || !p->num_frames || !p->heading || !p->scale || !p->mirror || !p->height_scale || !p->num_boxes ||
         !p->box_frame || !p->boxes)
@@ -531,9 +516,8 @@ extern "C" int parc_maug_draw_plan(ParcMotionAug *h, uint64_t seed, uint64_t fir
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipEventRecord(h->ev[6], st));
     // the one call that writes through the plan's pointers: ParcMotionAugPlan declares them const for its readers, maug_plan casts that away
-    hipLaunchKernelGGL(maug::k_maug_draw, dim3(blocks(plan->n, 64)), dim3(64), 0, st, h->lib->K, h->lib->L, h->cfg, maug_plan(plan), (long long)plan->n,
-                       (unsigned long long)seed, (unsigned long long)first_variation, mirror != 0);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(maug::k_maug_draw, dim3(blocks(plan->n, 64)), dim3(64), 0, st, h->lib->K, h->lib->L, h->cfg, maug_plan(plan), (long long)plan->n,
+                       (unsigned long long)seed, (unsigned long long)first_variation, mirror != 0));
     HIPCHK(hipEventRecord(h->ev[7], st));
     h->drew = true;
     return PARC_OK;
@@ -546,16 +530,11 @@ static int maug_validate(ParcMotionAug *h, const ParcMotionAugPlan *p, hipStream
                                                 "height_scale holds a value that is not finite",
                                                 "num_boxes: outside 0 .. PARC_MAUG_MAX_BOXES", "box_frame: outside its window",
                                                 "boxes holds a value that is not finite"};
-    HIPCHK(hipMemsetAsync(h->d_status + 1, 0, sizeof(int), st));
-    hipLaunchKernelGGL(maug::k_maug_validate, dim3(blocks(p->n, 256)), dim3(256), 0, st, h->lib->K, h->cfg, maug_plan(p), (long long)p->n, h->d_status + 1);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(h->status.clear(1, st));
+    PARC_TRY(tool::launch(maug::k_maug_validate, dim3(blocks(p->n, 256)), dim3(256), 0, st, h->lib->K, h->cfg, maug_plan(p), (long long)p->n, h->status.d + 1));
     int v = 0;
-    HIPCHK(hipMemcpyAsync(&v, h->d_status + 1, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (!v) return PARC_OK;
-    std::string msg;
-    for (int k = 0; k < maug::VB_COUNT; ++k) if (v & (1 << k)) msg += std::string(msg.empty() ? "" : "; ") + names[k];
-    return fail(PARC_ERR_INVALID, "maug: bad plan: " + msg);
+    PARC_TRY(h->status.read(1, st, v));
+    return v ? tool::bad_plan("maug", v, names) : PARC_OK;
 }
 
 template <bool DRAW>
@@ -566,9 +545,8 @@ static int maug_run(ParcMotionAug *h, int n, const ParcMotionAugPlan *plan, unsi
     const maug::Lib &L = h->lib->L;
     const maug::PlanD P = maug_plan(plan);
     const int B = G.B, J = B - 1;
-    h->res.reset();
-    std::unique_ptr<ParcMotionAug::Result> res(new (std::nothrow) ParcMotionAug::Result());
-    if (!res) return fail(PARC_ERR_INVALID, "maug: out of host memory");
+    std::unique_ptr<ParcMotionAug::Result> res;
+    PARC_TRY(tool::renew("maug", h->res, res));
     maug::Run &R = res->R;
     DeviceArena &mem = res->mem;
     PARC_TRY(mem.alloc(R.cnt_f, n)); PARC_TRY(mem.alloc(R.cnt_c, n));
@@ -577,10 +555,8 @@ static int maug_run(ParcMotionAug *h, int n, const ParcMotionAugPlan *plan, unsi
     PARC_TRY(mem.alloc(R.hf_geom, 4LL * n)); PARC_TRY(mem.alloc(R.canon_z, n));
     // 1. frame counts -> offsets; the total comes back in one 8-byte copy
     HIPCHK(hipEventRecord(h->ev[0], st));
-    hipLaunchKernelGGL(maug::k_maug_layout<DRAW>, dim3(blocks(n, 256)), dim3(256), 0, st, K, L, G, P, R.cnt_f, (long long)n, seed, first, h->d_status);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(maug::k_maug_scan, dim3(1), dim3(1024), 0, st, R.cnt_f, R.frame_off, (long long)n);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(maug::k_maug_layout<DRAW>, dim3(blocks(n, 256)), dim3(256), 0, st, K, L, G, P, R.cnt_f, (long long)n, seed, first, h->status.d));
+    PARC_TRY(tool::launch(maug::k_maug_scan, dim3(1), dim3(1024), 0, st, R.cnt_f, R.frame_off, (long long)n));
     HIPCHK(hipEventRecord(h->ev[1], st));
     long long F = 0;
     HIPCHK(hipMemcpyAsync(&F, R.frame_off + n, sizeof(long long), hipMemcpyDeviceToHost, st));
@@ -589,10 +565,8 @@ static int maug_run(ParcMotionAug *h, int n, const ParcMotionAugPlan *plan, unsi
     PARC_TRY(mem.alloc(R.joint_rot, 4 * F * J)); PARC_TRY(mem.alloc(R.contacts, F * B));
     // 2. frames and slices; the dims come back in one small copy
     HIPCHK(hipEventRecord(h->ev[2], st));
-    hipLaunchKernelGGL(maug::k_maug_frames<DRAW>, dim3((unsigned)n), dim3(64), 0, st, h->d_model, K, L, G, P, R, seed, first, mirror, h->d_status);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(maug::k_maug_scan, dim3(1), dim3(1024), 0, st, R.cnt_c, R.cell_off, (long long)n);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(maug::k_maug_frames<DRAW>, dim3((unsigned)n), dim3(64), 0, st, h->d_model, K, L, G, P, R, seed, first, mirror, h->status.d));
+    PARC_TRY(tool::launch(maug::k_maug_scan, dim3(1), dim3(1024), 0, st, R.cnt_c, R.cell_off, (long long)n));
     HIPCHK(hipEventRecord(h->ev[3], st));
     std::vector<int> dims((size_t)2 * n);
     HIPCHK(hipMemcpyAsync(dims.data(), R.hf_dims, dims.size() * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -612,9 +586,8 @@ static int maug_run(ParcMotionAug *h, int n, const ParcMotionAugPlan *plan, unsi
     if (L.maxmin) PARC_TRY(mem.alloc(R.hf_maxmin, 2 * cells));
     // 3. terrain: one wave per variation while every slice of the launch has at most WAVE_CELLS cells, else one workgroup of 256
     HIPCHK(hipEventRecord(h->ev[4], st));
-    hipLaunchKernelGGL(maug::k_maug_terrain<DRAW>, dim3((unsigned)n), dim3(largest <= maug::WAVE_CELLS ? 64 : maug::WG_THREADS), 0, st, K, L, G, P, R, seed, first,
-                       mirror, h->d_status);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(maug::k_maug_terrain<DRAW>, dim3((unsigned)n), dim3(largest <= maug::WAVE_CELLS ? 64 : maug::WG_THREADS), 0, st, K, L, G, P, R, seed, first,
+                       mirror, h->status.d));
     HIPCHK(hipEventRecord(h->ev[5], st));
     res->n = n; res->F = F; res->cells = cells;
     h->res = std::move(res);
@@ -631,7 +604,7 @@ extern "C" int parc_maug_augment_with(ParcMotionAug *h, const ParcMotionAugPlan 
 
 extern "C" int parc_maug_augment(ParcMotionAug *h, int32_t n, uint64_t seed, uint64_t first_variation, int32_t mirror, void *stream, ParcMotionAugSizes *sizes) {
     if (!h) return fail(PARC_ERR_INVALID, "maug: null argument");
-    if (!h->lib) return fail(PARC_ERR_STATE, "maug: parc_maug_set_clips first");
+    if (!h->lib) return tool::no_clips("maug");
     if (n < 1) return fail(PARC_ERR_INVALID, "maug: n must be >= 1");
     HIPCHK(hipSetDevice(h->device));
     return maug_run<true>(h, n, nullptr, (unsigned long long)seed, (unsigned long long)first_variation, mirror != 0, (hipStream_t)stream, sizes);
@@ -658,23 +631,12 @@ extern "C" int parc_maug_get_result(ParcMotionAug *h, const ParcMotionAugOutputs
 extern "C" int parc_maug_plan_status(ParcMotionAug *h, void *stream, int32_t *status) {
     if (!h || !status) return fail(PARC_ERR_INVALID, "maug: null argument");
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    int v = 0;
-    HIPCHK(hipMemcpy(&v, h->d_status, sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemset(h->d_status, 0, sizeof(int)));
-    *status = v;
-    return PARC_OK;
+    return h->status.take(0, (hipStream_t)stream, *status);
 }
 
 extern "C" int parc_maug_kernel_times(ParcMotionAug *h, float *ms4) {
     if (!h || !ms4) return fail(PARC_ERR_INVALID, "maug: null argument");
-    if (!h->drew && !h->res) return fail(PARC_ERR_STATE, "maug: nothing augmented yet");
-    HIPCHK(hipSetDevice(h->device));
-    for (int k = 0; k < 4; ++k) ms4[k] = 0.f;
-    if (h->drew) { HIPCHK(hipEventSynchronize(h->ev[7])); PARC_TRY(h->ev.elapsed(ms4[0], 6, 7)); }
-    if (h->res) {
-        HIPCHK(hipEventSynchronize(h->ev[5]));
-        for (int k = 0; k < 3; ++k) PARC_TRY(h->ev.elapsed(ms4[1 + k], 2 * k, 2 * k + 1));
-    }
-    return PARC_OK;
+    const bool ran = h->res != nullptr;
+    const tool::Span spans[] = {{h->drew, 6, 7}, {ran, 0, 1}, {ran, 2, 3}, {ran, 4, 5}};   // draw; layout, frames, terrain
+    return tool::span_times("maug: nothing augmented yet", h->device, h->ev, spans, ms4);
 }

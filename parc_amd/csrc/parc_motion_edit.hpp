@@ -29,6 +29,7 @@
 #include "parc_math.hpp"
 #include "parc_char.hpp"
 #include "parc_clip_batch.hpp"
+#include "parc_tool_handle.hpp"
 
 namespace medit {
 using namespace parc;
@@ -177,7 +178,7 @@ __global__ void k_medit_gather(ClipArrays K, Work W, long long n_out, int B) {
 }  // namespace medit
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------------
-struct ParcMotionEdit {
+struct ParcMotionEdit : tool::CharHandle<parc::CharTree, DeviceEvents<6>> {   // mem: d_model
     struct Batch {                        // what one parc_medit_set_clips loads; a batch is loaded when the handle holds one
         DeviceArena mem;
         FrameClips K{};
@@ -188,39 +189,23 @@ struct ParcMotionEdit {
         long long F = 0, total = 0;
         bool ran = false;
     };
-    int device = 0;
-    parc::CharTree host_model;
-    DeviceArena mem;                      // create .. destroy: d_model
-    parc::CharTree *d_model = nullptr;
     medit::Cfg cfg{};
     std::unique_ptr<Batch> batch;
-    DeviceEvents<6> ev;
     float kernel_ms[4] = {};
-    ~ParcMotionEdit() { (void)hipSetDevice(device); }   // the members release the rest
 };
 
-extern "C" void parc_medit_destroy(ParcMotionEdit *h) { delete h; }
+extern "C" void parc_medit_destroy(ParcMotionEdit *h) { tool::destroy(h); }
 
 extern "C" int parc_medit_create(const ParcMotionEditParams *p, ParcMotionEdit **out) {
-    if (!p || !out) return fail(PARC_ERR_INVALID, "medit: null argument");
-    if (p->struct_size != sizeof(ParcMotionEditParams)) return fail(PARC_ERR_INVALID, "ParcMotionEditParams ABI mismatch (struct_size)");
-    const ParcCharModel &cm = p->model;
-    if (cm.num_bodies < 1 || cm.num_bodies > PARC_MAX_BODIES) return fail(PARC_ERR_INVALID, "medit: num_bodies out of range");
-    if (cm.dof_size < 0 || cm.dof_size > PARC_MAX_DOFS) return fail(PARC_ERR_INVALID, "medit: dof_size out of range");
+    PARC_TRY(tool::create_args("medit", "ParcMotionEditParams", p, out, 1, true));
     if (!std::isfinite(p->hesitation_val)) return fail(PARC_ERR_INVALID, "medit: hesitation_val must be finite");
     if (p->hesitation_min_seq_len < 1) return fail(PARC_ERR_INVALID, "medit: hesitation_min_seq_len must be >= 1");
     parc::CharTree M;
-    model_zero(M);
-    PARC_TRY(model_tree("medit", cm, M));
-    std::unique_ptr<ParcMotionEdit> h(new (std::nothrow) ParcMotionEdit());   // every failure below is a plain return
-    if (!h) return fail(PARC_ERR_INVALID, "medit: out of host memory");
-    h->device = p->device; h->host_model = M;
-    h->cfg.val = p->hesitation_val; h->cfg.min_len = p->hesitation_min_seq_len;
-    HIPCHK(hipSetDevice(p->device));
-    PARC_TRY(model_upload(h->mem, M, h->d_model));
-    PARC_TRY(h->ev.create());
-    *out = h.release();
-    return PARC_OK;
+    PARC_TRY(tool::char_tree("medit", p->model, M));
+    return tool::create("medit", p->device, M, out, [&](ParcMotionEdit &h) -> int {
+        h.cfg.val = p->hesitation_val; h.cfg.min_len = p->hesitation_min_seq_len;
+        return PARC_OK;
+    });
 }
 
 // as parc_mopt_set_clips: validate; release the old batch; build the new one in a local; install it last
@@ -240,9 +225,8 @@ extern "C" int parc_medit_set_clips(ParcMotionEdit *h, const ParcMotionOptClips 
         row_off[(size_t)i + 1] = row_off[(size_t)i] + T * ((T + 63) / 64);
     }
     HIPCHK(hipSetDevice(h->device));
-    h->batch.reset();
-    std::unique_ptr<ParcMotionEdit::Batch> nb(new (std::nothrow) ParcMotionEdit::Batch());
-    if (!nb) return fail(PARC_ERR_INVALID, "medit: out of host memory");
+    std::unique_ptr<ParcMotionEdit::Batch> nb;
+    PARC_TRY(tool::renew("medit", h->batch, nb));
     FrameClips &K = nb->K;
     medit::Work &W = nb->W;
     DeviceArena &mem = nb->mem;
@@ -273,27 +257,18 @@ extern "C" int parc_medit_set_clips(ParcMotionEdit *h, const ParcMotionOptClips 
     return PARC_OK;
 }
 
-static int medit_check(ParcMotionEdit *h) {
-    if (!h) return fail(PARC_ERR_INVALID, "medit: null handle");
-    if (!h->batch) return fail(PARC_ERR_STATE, "medit: parc_medit_set_clips first");
-    return PARC_OK;
-}
-
 extern "C" int parc_medit_run(ParcMotionEdit *h, int32_t *kept_counts, int32_t *kept_inds, int64_t *total_kept) {
-    if (int rc = medit_check(h)) return rc;
+    PARC_TRY(tool::check_loaded("medit", h, &ParcMotionEdit::batch));
     ParcMotionEdit::Batch &b = *h->batch;
     HIPCHK(hipSetDevice(h->device));
     const long long F = b.F;
     const int C = b.K.C, B = h->host_model.B;
     HIPCHK(hipEventRecord(h->ev[0], 0));
-    hipLaunchKernelGGL(medit::k_medit_fk, dim3(blocks(F, 64)), dim3(64), 0, 0, h->d_model, b.K, b.W);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(medit::k_medit_fk, dim3(blocks(F, 64)), dim3(64), 0, 0, h->d_model, b.K, b.W));
     HIPCHK(hipEventRecord(h->ev[1], 0));
-    hipLaunchKernelGGL(medit::k_medit_pairs, dim3(blocks(F, medit::PAIR_WAVES)), dim3(64 * medit::PAIR_WAVES), 0, 0, b.K, b.W, h->cfg, 3 * B);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(medit::k_medit_pairs, dim3(blocks(F, medit::PAIR_WAVES)), dim3(64 * medit::PAIR_WAVES), 0, 0, b.K, b.W, h->cfg, 3 * B));
     HIPCHK(hipEventRecord(h->ev[2], 0));
-    hipLaunchKernelGGL(medit::k_medit_scan, dim3((unsigned)C), dim3(64), 0, 0, b.K, b.W, h->cfg);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(medit::k_medit_scan, dim3((unsigned)C), dim3(64), 0, 0, b.K, b.W, h->cfg));
     HIPCHK(hipEventRecord(h->ev[3], 0));
     HIPCHK(hipMemcpy(b.counts.data(), b.W.count, (size_t)C * sizeof(int), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(b.kept.data(), b.W.kept, (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
@@ -318,22 +293,15 @@ extern "C" int parc_medit_run(ParcMotionEdit *h, int32_t *kept_counts, int32_t *
     return PARC_OK;
 }
 
-static int medit_check_ran(ParcMotionEdit *h) {
-    if (int rc = medit_check(h)) return rc;
-    if (!h->batch->ran) return fail(PARC_ERR_STATE, "medit: parc_medit_run first");
-    return PARC_OK;
-}
-
 extern "C" int parc_medit_get_frames(ParcMotionEdit *h, float *root_pos, float *root_rot, float *joint_rot, float *contacts) {
-    if (int rc = medit_check_ran(h)) return rc;
+    PARC_TRY(tool::check_ran("medit", h, &ParcMotionEdit::batch));
     if (!root_pos || !root_rot || !joint_rot || !contacts) return fail(PARC_ERR_INVALID, "medit: null output");
     const ParcMotionEdit::Batch &b = *h->batch;
     const int B = h->host_model.B;
     const long long n = b.total, len = 7 + 4 * (B - 1) + B;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipEventRecord(h->ev[4], 0));
-    hipLaunchKernelGGL(medit::k_medit_gather, dim3(blocks(n * len, 256)), dim3(256), 0, 0, b.K, b.W, n, B);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(medit::k_medit_gather, dim3(blocks(n * len, 256)), dim3(256), 0, 0, b.K, b.W, n, B));
     HIPCHK(hipEventRecord(h->ev[5], 0));
     HIPCHK(hipMemcpy(root_pos, b.W.out_root_pos, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(root_rot, b.W.out_root_rot, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost));
@@ -343,7 +311,7 @@ extern "C" int parc_medit_get_frames(ParcMotionEdit *h, float *root_pos, float *
 }
 
 extern "C" int parc_medit_get_pair_rows(ParcMotionEdit *h, int32_t clip, uint64_t *rows) {
-    if (int rc = medit_check_ran(h)) return rc;
+    PARC_TRY(tool::check_ran("medit", h, &ParcMotionEdit::batch));
     const ParcMotionEdit::Batch &b = *h->batch;
     if (clip < 0 || clip >= b.K.C || !rows) return fail(PARC_ERR_INVALID, "medit: bad pair-row request");
     HIPCHK(hipSetDevice(h->device));
@@ -353,7 +321,7 @@ extern "C" int parc_medit_get_pair_rows(ParcMotionEdit *h, int32_t clip, uint64_
 }
 
 extern "C" int parc_medit_get_flags(ParcMotionEdit *h, uint64_t *raw, uint64_t *filtered) {
-    if (int rc = medit_check_ran(h)) return rc;
+    PARC_TRY(tool::check_ran("medit", h, &ParcMotionEdit::batch));
     const ParcMotionEdit::Batch &b = *h->batch;
     HIPCHK(hipSetDevice(h->device));
     const size_t n = (size_t)b.K.C * medit::WORDS * sizeof(uint64_t);
@@ -363,7 +331,5 @@ extern "C" int parc_medit_get_flags(ParcMotionEdit *h, uint64_t *raw, uint64_t *
 }
 
 extern "C" int parc_medit_kernel_times(ParcMotionEdit *h, float *ms4) {
-    if (!h || !ms4) return fail(PARC_ERR_INVALID, "medit: null argument");
-    for (int k = 0; k < 4; ++k) ms4[k] = h->kernel_ms[k];
-    return PARC_OK;
+    return tool::stored_times("medit", h, &ParcMotionEdit::kernel_ms, ms4);
 }

@@ -28,6 +28,7 @@
 #include "parc_char.hpp"
 #include "parc_grid.hpp"
 #include "parc_clip_batch.hpp"
+#include "parc_tool_handle.hpp"
 
 namespace mopt {
 using namespace parc;
@@ -460,41 +461,30 @@ __global__ void k_mopt_cons_sgd(Clips K, const int *clip, float *pts, int n, flo
 }  // namespace mopt
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------------
-struct ParcMotionOpt {
+struct ParcMotionOpt : tool::CharHandle<mopt::Model, DeviceEvents<7>> {   // mem: d_model
     struct Batch {                        // what one parc_mopt_set_clips loads; a batch is loaded when the handle holds one
         DeviceArena mem;
         mopt::Clips K{};
         mopt::Work W{};
         long long F = 0, adam_t = 0, ncons = 0;
     };
-    int device = 0;
-    mopt::Model host_model;
-    DeviceArena mem;                      // create .. destroy: d_model
-    mopt::Model *d_model = nullptr;
     std::unique_ptr<Batch> batch;
     float step_size = 1e-3f;
-    DeviceEvents<7> ev;
     float kernel_ms[6] = {};
-    ~ParcMotionOpt() { (void)hipSetDevice(device); }   // the members release the rest
 };
 
-extern "C" void parc_mopt_destroy(ParcMotionOpt *h) { delete h; }
+extern "C" void parc_mopt_destroy(ParcMotionOpt *h) { tool::destroy(h); }
 
 extern "C" int parc_mopt_create(const ParcMotionOptParams *p, ParcMotionOpt **out) {
-    if (!p || !out) return fail(PARC_ERR_INVALID, "mopt: null argument");
-    if (p->struct_size != sizeof(ParcMotionOptParams)) return fail(PARC_ERR_INVALID, "ParcMotionOptParams ABI mismatch (struct_size)");
+    PARC_TRY(tool::create_args("mopt", "ParcMotionOptParams", p, out, 1, true));
     const ParcCharModel &cm = p->model;
-    if (cm.num_bodies < 1 || cm.num_bodies > PARC_MAX_BODIES) return fail(PARC_ERR_INVALID, "mopt: num_bodies out of range");
-    if (cm.dof_size < 0 || cm.dof_size > PARC_MAX_DOFS) return fail(PARC_ERR_INVALID, "mopt: dof_size out of range");
     if (p->num_points < 1 || p->num_points > PARC_MOPT_MAX_POINTS || !p->points_host || !p->point_body_host)
         return fail(PARC_ERR_INVALID, "mopt: num_points must be in [1, 512] with points and point bodies given");
     mopt::Model M;
-    model_zero(M);
-    PARC_TRY(model_tree("mopt", cm, M));
+    PARC_TRY(tool::char_tree("mopt", cm, M));
     M.NP = PARC_MOPT_NP(cm.dof_size);
+    PARC_TRY(tool::char_dofs("mopt", cm));
     for (int b = 0; b < M.B; ++b) {
-        const int dd = cm.joint_type[b] == PARC_JOINT_HINGE ? 1 : (cm.joint_type[b] == PARC_JOINT_SPHERICAL ? 3 : 0);
-        if (b > 0 && dd && (cm.dof_idx[b] < 0 || cm.dof_idx[b] + dd > cm.dof_size)) return fail(PARC_ERR_INVALID, "mopt: dof_idx out of range");
         for (int k = 0; k < 3; ++k) M.g0off[b][k] = p->geom0_offset[b][k];
         M.g0type[b] = p->geom0_type[b]; M.g0rad[b] = p->geom0_radius[b];
     }
@@ -502,14 +492,10 @@ extern "C" int parc_mopt_create(const ParcMotionOptParams *p, ParcMotionOpt **ou
     for (int t = 0; t < mopt::NT; ++t) M.w[t] = p->weights[t];
     const double dt = 1.0 / 30.0;
     M.max_jerk = (float)((double)p->max_jerk * (dt * dt * dt));
-    std::unique_ptr<ParcMotionOpt> h(new (std::nothrow) ParcMotionOpt());   // every failure below is a plain return
-    if (!h) return fail(PARC_ERR_INVALID, "mopt: out of host memory");
-    h->device = p->device; h->host_model = M; h->step_size = p->step_size;
-    HIPCHK(hipSetDevice(p->device));
-    PARC_TRY(model_upload(h->mem, M, h->d_model));
-    PARC_TRY(h->ev.create());
-    *out = h.release();
-    return PARC_OK;
+    return tool::create("mopt", p->device, M, out, [&](ParcMotionOpt &h) -> int {
+        h.step_size = p->step_size;
+        return PARC_OK;
+    });
 }
 
 // validate; release the old batch (two would double the peak of F x B workspace); build the new one in a local; install it last
@@ -528,9 +514,8 @@ extern "C" int parc_mopt_set_clips(ParcMotionOpt *h, const ParcMotionOptClips *c
     for (long long q = 0; q < ncons; ++q)
         if (c->cons_body_host[q] < 0 || c->cons_body_host[q] >= B) return fail(PARC_ERR_INVALID, "mopt: constraint body out of range");
     HIPCHK(hipSetDevice(h->device));
-    h->batch.reset();
-    std::unique_ptr<ParcMotionOpt::Batch> nb(new (std::nothrow) ParcMotionOpt::Batch());
-    if (!nb) return fail(PARC_ERR_INVALID, "mopt: out of host memory");
+    std::unique_ptr<ParcMotionOpt::Batch> nb;
+    PARC_TRY(tool::renew("mopt", h->batch, nb));
     mopt::Clips &K = nb->K;
     mopt::Work &W = nb->W;
     DeviceArena &mem = nb->mem;
@@ -556,21 +541,14 @@ extern "C" int parc_mopt_set_clips(ParcMotionOpt *h, const ParcMotionOptClips *c
     PARC_TRY(mem.alloc(W.fterms, F * mopt::NT));
     PARC_TRY(mem.alloc(W.terms, (long long)C * mopt::NT));
     nb->F = F; nb->ncons = ncons;
-    hipLaunchKernelGGL(mopt::k_mopt_source, dim3(blocks(F, 64)), dim3(64), 0, 0, h->d_model, K, W);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(mopt::k_mopt_source, dim3(blocks(F, 64)), dim3(64), 0, 0, h->d_model, K, W));
     HIPCHK(hipDeviceSynchronize());
     h->batch = std::move(nb);
     return PARC_OK;
 }
 
-static int mopt_check(ParcMotionOpt *h) {
-    if (!h) return fail(PARC_ERR_INVALID, "mopt: null handle");
-    if (!h->batch) return fail(PARC_ERR_STATE, "mopt: parc_mopt_set_clips first");
-    return PARC_OK;
-}
-
 extern "C" int parc_mopt_set_constraint_points(ParcMotionOpt *h, const float *pts) {
-    if (int rc = mopt_check(h)) return rc;
+    PARC_TRY(tool::check_loaded("mopt", h, &ParcMotionOpt::batch));
     const long long ncons = h->batch->ncons;
     if (ncons && !pts) return fail(PARC_ERR_INVALID, "mopt: null points");
     HIPCHK(hipSetDevice(h->device));
@@ -579,7 +557,7 @@ extern "C" int parc_mopt_set_constraint_points(ParcMotionOpt *h, const float *pt
 }
 
 extern "C" int parc_mopt_set_params(ParcMotionOpt *h, const float *params) {
-    if (int rc = mopt_check(h)) return rc;
+    PARC_TRY(tool::check_loaded("mopt", h, &ParcMotionOpt::batch));
     if (!params) return fail(PARC_ERR_INVALID, "mopt: null params");
     ParcMotionOpt::Batch &b = *h->batch;
     const size_t n = (size_t)b.F * h->host_model.NP;
@@ -592,7 +570,7 @@ extern "C" int parc_mopt_set_params(ParcMotionOpt *h, const float *params) {
 }
 
 extern "C" int parc_mopt_get_params(ParcMotionOpt *h, float *params) {
-    if (int rc = mopt_check(h)) return rc;
+    PARC_TRY(tool::check_loaded("mopt", h, &ParcMotionOpt::batch));
     if (!params) return fail(PARC_ERR_INVALID, "mopt: null params");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemcpy(params, h->batch->W.params, (size_t)h->batch->F * h->host_model.NP * sizeof(float), hipMemcpyDeviceToHost));
@@ -605,26 +583,21 @@ static int mopt_eval(ParcMotionOpt *h, bool timed) {
     const long long F = b.F;
     const int C = b.K.C;
     if (timed) HIPCHK(hipEventRecord(h->ev[0], 0));
-    hipLaunchKernelGGL(mopt::k_mopt_fk, dim3(blocks(F, 64)), dim3(64), 0, 0, h->d_model, b.K, b.W);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(mopt::k_mopt_fk, dim3(blocks(F, 64)), dim3(64), 0, 0, h->d_model, b.K, b.W));
     if (timed) HIPCHK(hipEventRecord(h->ev[1], 0));
-    hipLaunchKernelGGL(mopt::k_mopt_patch, dim3(blocks(C, 64)), dim3(64), 0, 0, b.K, b.W);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(mopt::k_mopt_patch, dim3(blocks(C, 64)), dim3(64), 0, 0, b.K, b.W));
     if (timed) HIPCHK(hipEventRecord(h->ev[2], 0));
-    hipLaunchKernelGGL(mopt::k_mopt_points, dim3((unsigned)F), dim3(mopt::PT_THREADS), 0, 0, h->d_model, b.K, b.W);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(mopt::k_mopt_points, dim3((unsigned)F), dim3(mopt::PT_THREADS), 0, 0, h->d_model, b.K, b.W));
     if (timed) HIPCHK(hipEventRecord(h->ev[3], 0));
-    hipLaunchKernelGGL(mopt::k_mopt_grad, dim3(blocks(F, 64)), dim3(64), 0, 0, h->d_model, b.K, b.W);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(mopt::k_mopt_grad, dim3(blocks(F, 64)), dim3(64), 0, 0, h->d_model, b.K, b.W));
     if (timed) HIPCHK(hipEventRecord(h->ev[4], 0));
-    hipLaunchKernelGGL(mopt::k_mopt_reduce, dim3(blocks((long long)C * mopt::NT, 64)), dim3(64), 0, 0, b.K, b.W);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(mopt::k_mopt_reduce, dim3(blocks((long long)C * mopt::NT, 64)), dim3(64), 0, 0, b.K, b.W));
     if (timed) HIPCHK(hipEventRecord(h->ev[5], 0));
     return PARC_OK;
 }
 
 extern "C" int parc_mopt_loss_and_grad(ParcMotionOpt *h, float *terms, float *grad) {
-    if (int rc = mopt_check(h)) return rc;
+    PARC_TRY(tool::check_loaded("mopt", h, &ParcMotionOpt::batch));
     const ParcMotionOpt::Batch &b = *h->batch;
     HIPCHK(hipSetDevice(h->device));
     if (int rc = mopt_eval(h, false)) return rc;
@@ -635,7 +608,7 @@ extern "C" int parc_mopt_loss_and_grad(ParcMotionOpt *h, float *terms, float *gr
 }
 
 extern "C" int parc_mopt_step(ParcMotionOpt *h, int32_t n_iters, float *terms) {
-    if (int rc = mopt_check(h)) return rc;
+    PARC_TRY(tool::check_loaded("mopt", h, &ParcMotionOpt::batch));
     if (n_iters < 0) return fail(PARC_ERR_INVALID, "mopt: n_iters must be >= 0");
     ParcMotionOpt::Batch &b = *h->batch;
     HIPCHK(hipSetDevice(h->device));
@@ -645,9 +618,8 @@ extern "C" int parc_mopt_step(ParcMotionOpt *h, int32_t n_iters, float *terms) {
         if (int rc = mopt_eval(h, true)) return rc;
         b.adam_t++;
         const double bc1 = 1.0 - pow(0.9, (double)b.adam_t), bc2 = 1.0 - pow(0.999, (double)b.adam_t);
-        hipLaunchKernelGGL(mopt::k_mopt_adam, dim3(blocks(n, 256)), dim3(256), 0, 0, b.W, n, (float)((double)h->step_size / bc1),
-                           (float)sqrt(bc2));
-        HIPCHK(hipGetLastError());
+        PARC_TRY(tool::launch(mopt::k_mopt_adam, dim3(blocks(n, 256)), dim3(256), 0, 0, b.W, n, (float)((double)h->step_size / bc1),
+                           (float)sqrt(bc2)));
         HIPCHK(hipEventRecord(h->ev[6], 0));
         if (terms) HIPCHK(hipMemcpy(terms + (size_t)it * b.K.C * mopt::NT, b.W.terms, (size_t)b.K.C * mopt::NT * sizeof(float),
                                     hipMemcpyDeviceToHost));
@@ -663,17 +635,14 @@ extern "C" int parc_mopt_step(ParcMotionOpt *h, int32_t n_iters, float *terms) {
 }
 
 extern "C" int parc_mopt_kernel_times(ParcMotionOpt *h, float *ms6) {
-    if (!h || !ms6) return fail(PARC_ERR_INVALID, "mopt: null argument");
-    for (int k = 0; k < 6; ++k) ms6[k] = h->kernel_ms[k];
-    return PARC_OK;
+    return tool::stored_times("mopt", h, &ParcMotionOpt::kernel_ms, ms6);
 }
 
 extern "C" int parc_mopt_get_frames(ParcMotionOpt *h, float *root_pos, float *root_rot, float *joint_rot) {
-    if (int rc = mopt_check(h)) return rc;
+    PARC_TRY(tool::check_loaded("mopt", h, &ParcMotionOpt::batch));
     const ParcMotionOpt::Batch &b = *h->batch;
     HIPCHK(hipSetDevice(h->device));
-    hipLaunchKernelGGL(mopt::k_mopt_fk, dim3(blocks(b.F, 64)), dim3(64), 0, 0, h->d_model, b.K, b.W);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(mopt::k_mopt_fk, dim3(blocks(b.F, 64)), dim3(64), 0, 0, h->d_model, b.K, b.W));
     HIPCHK(hipDeviceSynchronize());
     const int B = h->host_model.B, NP = h->host_model.NP;
     std::vector<float> rot((size_t)b.F * B * 4), jr((size_t)b.F * B * 4), par((size_t)b.F * NP);
@@ -689,7 +658,7 @@ extern "C" int parc_mopt_get_frames(ParcMotionOpt *h, float *root_pos, float *ro
 }
 
 extern "C" int parc_mopt_get_source_body(ParcMotionOpt *h, float *body_pos, float *body_rot) {
-    if (int rc = mopt_check(h)) return rc;
+    PARC_TRY(tool::check_loaded("mopt", h, &ParcMotionOpt::batch));
     const ParcMotionOpt::Batch &b = *h->batch;
     HIPCHK(hipSetDevice(h->device));
     const size_t n = (size_t)b.F * h->host_model.B;
@@ -699,7 +668,7 @@ extern "C" int parc_mopt_get_source_body(ParcMotionOpt *h, float *body_pos, floa
 }
 
 extern "C" int parc_mopt_build_constraints(ParcMotionOpt *h, int32_t n, const int32_t *clip, float *pts, int32_t steps, float lr) {
-    if (int rc = mopt_check(h)) return rc;
+    PARC_TRY(tool::check_loaded("mopt", h, &ParcMotionOpt::batch));
     if (n < 0 || steps < 0 || (n > 0 && (!clip || !pts))) return fail(PARC_ERR_INVALID, "mopt: bad constraint arguments");
     if (n == 0) return PARC_OK;
     const mopt::Clips &K = h->batch->K;
@@ -710,8 +679,7 @@ extern "C" int parc_mopt_build_constraints(ParcMotionOpt *h, int32_t n, const in
     PARC_TRY(tmp.alloc(d_clip, n, clip));
     PARC_TRY(tmp.alloc(d_pts, 3LL * n, pts));
     for (int s = 0; s < steps; ++s) {
-        hipLaunchKernelGGL(mopt::k_mopt_cons_sgd, dim3(blocks(n, 64)), dim3(64), 0, 0, K, d_clip, d_pts, n, lr);
-        HIPCHK(hipGetLastError());
+        PARC_TRY(tool::launch(mopt::k_mopt_cons_sgd, dim3(blocks(n, 64)), dim3(64), 0, 0, K, d_clip, d_pts, n, lr));
     }
     HIPCHK(hipMemcpy(pts, d_pts, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return PARC_OK;

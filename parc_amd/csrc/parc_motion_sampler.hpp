@@ -29,6 +29,7 @@
 #include "parc_char.hpp"
 #include "parc_grid.hpp"
 #include "parc_clip_batch.hpp"
+#include "parc_tool_handle.hpp"
 
 namespace msamp {
 using namespace parc;
@@ -347,7 +348,7 @@ __global__ void k_msamp_draw_noise(Cfg G, float *noise, long long n, unsigned lo
 }  // namespace msamp
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------------
-struct ParcMotionSampler {
+struct ParcMotionSampler : tool::CharHandle<parc::CharTree, DeviceEvents<4>> {   // mem: d_model, status, the times / grid tables of cfg
     struct Library {                      // what one parc_msamp_set_clips loads; a library is loaded when the handle holds one
         DeviceArena mem;
         ClipArrays K{};                  // the frames and terrains
@@ -355,25 +356,16 @@ struct ParcMotionSampler {
         std::vector<int> clip_windows;    // num_frames - T per clip
         int bit_words = 0;                // words of the largest terrain's cell bitset
     };
-    int device = 0;
-    parc::CharTree host_model;
-    DeviceArena mem;                      // create .. destroy: d_model, d_status, the times / grid tables of cfg
-    parc::CharTree *d_model = nullptr;
     msamp::Cfg cfg{};
     std::unique_ptr<Library> lib;
-    int *d_status = nullptr;
-    DeviceEvents<4> ev;
+    tool::StatusWords status;             // one word
     bool timed = false;
-    ~ParcMotionSampler() { (void)hipSetDevice(device); }   // the members release the rest
 };
 
-extern "C" void parc_msamp_destroy(ParcMotionSampler *h) { delete h; }
+extern "C" void parc_msamp_destroy(ParcMotionSampler *h) { tool::destroy(h); }
 
 extern "C" int parc_msamp_create(const ParcMotionSamplerParams *p, ParcMotionSampler **out) {
-    if (!p || !out) return fail(PARC_ERR_INVALID, "msamp: null argument");
-    if (p->struct_size != sizeof(ParcMotionSamplerParams)) return fail(PARC_ERR_INVALID, "ParcMotionSamplerParams ABI mismatch (struct_size)");
-    const ParcCharModel &cm = p->model;
-    if (cm.num_bodies < 2 || cm.num_bodies > PARC_MAX_BODIES) return fail(PARC_ERR_INVALID, "msamp: num_bodies out of range");
+    PARC_TRY(tool::create_args("msamp", "ParcMotionSamplerParams", p, out, 2, false));
     if (p->num_frames < 1 || p->num_frames > PARC_MSAMP_MAX_FRAMES || !p->times_host)
         return fail(PARC_ERR_INVALID, "msamp: the window must have 1 .. " + std::to_string(PARC_MSAMP_MAX_FRAMES) + " frames");
     if (p->ref_frame < 0 || p->ref_frame >= p->num_frames) return fail(PARC_ERR_INVALID, "msamp: num_prev_states must be in [1, T]");
@@ -387,28 +379,21 @@ extern "C" int parc_msamp_create(const ParcMotionSamplerParams *p, ParcMotionSam
         return fail(PARC_ERR_INVALID, "msamp: max_num_boxes must be in [0, " + std::to_string(PARC_MSAMP_MAX_BOXES) + "], hf_max_maxpool_size >= 0");
     if (!(p->timestep > 0.f) || !(p->dx > 0.f)) return fail(PARC_ERR_INVALID, "msamp: sequence_fps and horizontal_scale must be > 0");
     parc::CharTree M;
-    model_zero(M);
-    PARC_TRY(model_tree("msamp", cm, M));
-    std::unique_ptr<ParcMotionSampler> h(new (std::nothrow) ParcMotionSampler());   // every failure below is a plain return
-    if (!h) return fail(PARC_ERR_INVALID, "msamp: out of host memory");
-    h->device = p->device; h->host_model = M;
-    msamp::Cfg &G = h->cfg;
-    G.T = p->num_frames; G.ref = p->ref_frame; G.autoreg = p->autoregressive; G.zstyle = p->relative_z_style; G.aug = p->aug_mode;
-    G.Gx = p->grid_dim_x; G.Gy = p->grid_dim_y; G.nxn = p->num_x_neg; G.nyn = p->num_y_neg; G.maxb = p->max_num_boxes;
-    G.max_pool = p->hf_max_maxpool_size; G.B = M.B;
-    G.timestep = p->timestep; G.duration = p->sequence_duration; G.gminx = p->grid_min_x; G.gminy = p->grid_min_y; G.dx = p->dx;
-    G.max_h = p->max_h; G.box_min = p->box_min_len; G.box_max = p->box_max_len; G.pool_chance = p->hf_maxpool_chance;
-    G.height_chance = p->hf_change_height_chance; G.noise_scale = p->future_pos_noise_scale; G.fw_min = p->future_window_min;
-    G.fw_max = p->future_window_max;
-    HIPCHK(hipSetDevice(p->device));
-    PARC_TRY(model_upload(h->mem, M, h->d_model));
-    PARC_TRY(h->mem.alloc_fill(h->d_status, 1));
-    PARC_TRY(h->mem.alloc(G.times, p->num_frames, p->times_host));
-    PARC_TRY(h->mem.alloc(G.gridx, p->grid_dim_x, p->grid_x_host));
-    PARC_TRY(h->mem.alloc(G.gridy, p->grid_dim_y, p->grid_y_host));
-    PARC_TRY(h->ev.create());
-    *out = h.release();
-    return PARC_OK;
+    PARC_TRY(tool::char_tree("msamp", p->model, M));
+    return tool::create("msamp", p->device, M, out, [&](ParcMotionSampler &h) -> int {
+        msamp::Cfg &G = h.cfg;
+        G.T = p->num_frames; G.ref = p->ref_frame; G.autoreg = p->autoregressive; G.zstyle = p->relative_z_style; G.aug = p->aug_mode;
+        G.Gx = p->grid_dim_x; G.Gy = p->grid_dim_y; G.nxn = p->num_x_neg; G.nyn = p->num_y_neg; G.maxb = p->max_num_boxes;
+        G.max_pool = p->hf_max_maxpool_size; G.B = M.B;
+        G.timestep = p->timestep; G.duration = p->sequence_duration; G.gminx = p->grid_min_x; G.gminy = p->grid_min_y; G.dx = p->dx;
+        G.max_h = p->max_h; G.box_min = p->box_min_len; G.box_max = p->box_max_len; G.pool_chance = p->hf_maxpool_chance;
+        G.height_chance = p->hf_change_height_chance; G.noise_scale = p->future_pos_noise_scale; G.fw_min = p->future_window_min;
+        G.fw_max = p->future_window_max;
+        PARC_TRY(h.status.alloc(h.mem, 1));
+        PARC_TRY(h.mem.alloc(G.times, p->num_frames, p->times_host));
+        PARC_TRY(h.mem.alloc(G.gridx, p->grid_dim_x, p->grid_x_host));
+        return h.mem.alloc(G.gridy, p->grid_dim_y, p->grid_y_host);
+    });
 }
 
 // as parc_mopt_set_clips: validate; release the old library; build the new one in a local; install it last (never a half-filled one)
@@ -464,9 +449,8 @@ extern "C" int parc_msamp_set_clips(ParcMotionSampler *h, const ParcMotionOptCli
         if ((int)((X * Y + 31) / 32) > bit_words) bit_words = (int)((X * Y + 31) / 32);
     }
     HIPCHK(hipSetDevice(h->device));
-    h->lib.reset();
-    std::unique_ptr<ParcMotionSampler::Library> nl(new (std::nothrow) ParcMotionSampler::Library());
-    if (!nl) return fail(PARC_ERR_INVALID, "msamp: out of host memory");
+    std::unique_ptr<ParcMotionSampler::Library> nl;
+    PARC_TRY(tool::renew("msamp", h->lib, nl));
     ClipArrays &K = nl->K;
     msamp::Lib &L = nl->L;
     DeviceArena &mem = nl->mem;
@@ -498,7 +482,7 @@ static msamp::OutD msamp_out(const ParcMotionSamplerOutputs *o) {
 
 static int msamp_check_plan(ParcMotionSampler *h, const ParcMotionSamplerPlan *p, bool hf) {
     if (!h || !p) return fail(PARC_ERR_INVALID, "msamp: null argument");
-    if (!h->lib) return fail(PARC_ERR_STATE, "msamp: parc_msamp_set_clips first");
+    if (!h->lib) return tool::no_clips("msamp");
     if (p->n < 1) return fail(PARC_ERR_INVALID, "msamp: n must be >= 1");
     if (!p->motion_id || !p->t0 || !p->t_future || !p->future_pos_noise) return fail(PARC_ERR_INVALID, "msamp: null plan array");
     if (hf && h->cfg.aug == PARC_MSAMP_AUG_MAXPOOL_AND_BOXES &&
@@ -515,14 +499,12 @@ static int msamp_launch(ParcMotionSampler *h, const ParcMotionSamplerPlan *plan,
     if ((out->target_pos == nullptr) != (out->target_rot == nullptr)) return fail(PARC_ERR_INVALID, "msamp: target_pos and target_rot go together");
     const msamp::PlanD P = msamp_plan(plan);
     const msamp::OutD O = msamp_out(out);
-    hipLaunchKernelGGL(msamp::k_msamp_window, dim3((unsigned)plan->n), dim3(64), msamp::win_lds_bytes(G.T, G.B), st, h->d_model, h->lib->K, h->lib->L, G, P, O,
-                       -1, h->d_status);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(msamp::k_msamp_window, dim3((unsigned)plan->n), dim3(64), msamp::win_lds_bytes(G.T, G.B), st, h->d_model, h->lib->K, h->lib->L, G, P, O,
+                       -1, h->status.d));
     HIPCHK(hipEventRecord(h->ev[2], st));
     if (out->hfs) {
-        hipLaunchKernelGGL(msamp::k_msamp_hf, dim3((unsigned)plan->n), dim3(msamp::HF_THREADS), (size_t)h->lib->bit_words * sizeof(unsigned), st, h->lib->K, h->lib->L, G, P, O,
-                           h->d_status);
-        HIPCHK(hipGetLastError());
+        PARC_TRY(tool::launch(msamp::k_msamp_hf, dim3((unsigned)plan->n), dim3(msamp::HF_THREADS), (size_t)h->lib->bit_words * sizeof(unsigned), st, h->lib->K, h->lib->L, G, P, O,
+                           h->status.d));
     }
     HIPCHK(hipEventRecord(h->ev[3], st));
     h->timed = true;
@@ -534,14 +516,12 @@ static int msamp_draw(ParcMotionSampler *h, uint64_t seed, const ParcMotionSampl
     if (!plan->change_height || !plan->height_value || !plan->pool_kind || !plan->pool_size || !plan->num_boxes || (G.maxb > 0 && !plan->boxes))
         return fail(PARC_ERR_INVALID, "msamp: draw_plan fills every array of the plan (noise may be NULL outside NOISE mode)");
     const long long n = plan->n;
-    hipLaunchKernelGGL(msamp::k_msamp_draw, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, h->lib->K, h->lib->L, G, msamp_plan(plan), n,
-                       (unsigned long long)seed);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(msamp::k_msamp_draw, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, h->lib->K, h->lib->L, G, msamp_plan(plan), n,
+                       (unsigned long long)seed));
     if (plan->noise) {
         const long long items = n * (((long long)G.Gx * G.Gy + 3) / 4);
-        hipLaunchKernelGGL(msamp::k_msamp_draw_noise, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, G, (float *)plan->noise, n,
-                           (unsigned long long)seed);
-        HIPCHK(hipGetLastError());
+        PARC_TRY(tool::launch(msamp::k_msamp_draw_noise, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, G, (float *)plan->noise, n,
+                           (unsigned long long)seed));
     }
     return PARC_OK;
 }
@@ -574,35 +554,26 @@ extern "C" int parc_msamp_sample(ParcMotionSampler *h, uint64_t seed, const Parc
 
 extern "C" int parc_msamp_enumerate(ParcMotionSampler *h, int32_t clip, const ParcMotionSamplerOutputs *out, void *stream) {
     if (!h || !out) return fail(PARC_ERR_INVALID, "msamp: null argument");
-    if (!h->lib) return fail(PARC_ERR_STATE, "msamp: parc_msamp_set_clips first");
+    if (!h->lib) return tool::no_clips("msamp");
     if (clip < 0 || clip >= h->lib->K.C) return fail(PARC_ERR_INVALID, "msamp: clip out of range");
     if (out->hfs || out->floor_heights || out->target_pos || out->target_rot || out->hf_bounds)
         return fail(PARC_ERR_INVALID, "msamp: enumerate writes the motion outputs only");
     HIPCHK(hipSetDevice(h->device));
     const msamp::Cfg &G = h->cfg;
     msamp::PlanD P{};
-    hipLaunchKernelGGL(msamp::k_msamp_window, dim3((unsigned)h->lib->clip_windows[(size_t)clip]), dim3(64), msamp::win_lds_bytes(G.T, G.B),
-                       (hipStream_t)stream, h->d_model, h->lib->K, h->lib->L, G, P, msamp_out(out), (int)clip, h->d_status);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(msamp::k_msamp_window, dim3((unsigned)h->lib->clip_windows[(size_t)clip]), dim3(64), msamp::win_lds_bytes(G.T, G.B),
+                       (hipStream_t)stream, h->d_model, h->lib->K, h->lib->L, G, P, msamp_out(out), (int)clip, h->status.d));
     return PARC_OK;
 }
 
 extern "C" int parc_msamp_plan_status(ParcMotionSampler *h, void *stream, int32_t *status) {
     if (!h || !status) return fail(PARC_ERR_INVALID, "msamp: null argument");
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    int v = 0;
-    HIPCHK(hipMemcpy(&v, h->d_status, sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemset(h->d_status, 0, sizeof(int)));
-    *status = v;
-    return PARC_OK;
+    return h->status.take(0, (hipStream_t)stream, *status);
 }
 
 extern "C" int parc_msamp_kernel_times(ParcMotionSampler *h, float *ms3) {
     if (!h || !ms3) return fail(PARC_ERR_INVALID, "msamp: null argument");
-    if (!h->timed) return fail(PARC_ERR_STATE, "msamp: nothing sampled yet");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipEventSynchronize(h->ev[3]));
-    for (int k = 0; k < 3; ++k) PARC_TRY(h->ev.elapsed(ms3[k], k, k + 1));
-    return PARC_OK;
+    const tool::Span spans[] = {{h->timed, 0, 1}, {h->timed, 1, 2}, {h->timed, 2, 3}};   // draw, window, hf
+    return tool::span_times("msamp: nothing sampled yet", h->device, h->ev, spans, ms3);
 }

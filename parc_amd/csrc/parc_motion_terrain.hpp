@@ -31,6 +31,7 @@
 #include "parc_char.hpp"
 #include "parc_grid.hpp"
 #include "parc_clip_batch.hpp"
+#include "parc_tool_handle.hpp"
 
 namespace mterr {
 using namespace parc;
@@ -369,7 +370,7 @@ __global__ void __launch_bounds__(PT_THREADS) k_mterr_point_sdf(const CharPoints
 }  // namespace mterr
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------------
-struct ParcMotionTerrain {
+struct ParcMotionTerrain : tool::CharHandle<parc::CharPoints, DeviceEvents<8>> {   // mem: d_model
     struct Batch {                        // what one parc_mterr_set_clips loads; a batch is loaded when the handle holds one
         DeviceArena mem;
         FrameClips K{};
@@ -379,47 +380,31 @@ struct ParcMotionTerrain {
         long long F = 0, ncell = 0, total = 0;
         bool ran = false;
     };
-    int device = 0;
-    parc::CharPoints host_model;
-    DeviceArena mem;                      // create .. destroy: d_model
-    parc::CharPoints *d_model = nullptr;
     mterr::Cfg cfg{};
     std::unique_ptr<Batch> batch;
     DeviceArena inds;                     // d_inds alone: released and allocated anew when it must grow
     int *d_inds = nullptr;                // [inds_cap][2]: parc_mterr_get_mask_inds' output
     long long inds_cap = 0;
-    DeviceEvents<8> ev;
     float kernel_ms[6] = {};
-    ~ParcMotionTerrain() { (void)hipSetDevice(device); }   // the members release the rest
 };
 
-extern "C" void parc_mterr_destroy(ParcMotionTerrain *h) { delete h; }
+extern "C" void parc_mterr_destroy(ParcMotionTerrain *h) { tool::destroy(h); }
 
 extern "C" int parc_mterr_create(const ParcMotionTerrainParams *p, ParcMotionTerrain **out) {
-    if (!p || !out) return fail(PARC_ERR_INVALID, "mterr: null argument");
-    if (p->struct_size != sizeof(ParcMotionTerrainParams)) return fail(PARC_ERR_INVALID, "ParcMotionTerrainParams ABI mismatch (struct_size)");
-    const ParcCharModel &cm = p->model;
-    if (cm.num_bodies < 1 || cm.num_bodies > PARC_MAX_BODIES) return fail(PARC_ERR_INVALID, "mterr: num_bodies out of range");
-    if (cm.dof_size < 0 || cm.dof_size > PARC_MAX_DOFS) return fail(PARC_ERR_INVALID, "mterr: dof_size out of range");
+    PARC_TRY(tool::create_args("mterr", "ParcMotionTerrainParams", p, out, 1, true));
     if (p->num_points < 1 || p->num_points > PARC_MOPT_MAX_POINTS || !p->points_host || !p->point_body_host)
         return fail(PARC_ERR_INVALID, "mterr: num_points must be in [1, 512] with points and point bodies given");
     if (p->sdf_mode != PARC_MTERR_SDF_PRUNED && p->sdf_mode != PARC_MTERR_SDF_BRUTE) return fail(PARC_ERR_INVALID, "mterr: unknown sdf_mode");
     parc::CharPoints M;
-    model_zero(M);
-    PARC_TRY(model_tree("mterr", cm, M));
+    PARC_TRY(tool::char_tree("mterr", p->model, M));
     PARC_TRY(model_points("mterr", M, p->num_points, p->points_host, p->point_body_host, p->contact_body_id));
     int sort_n = 1;
     while (sort_n < M.P) sort_n <<= 1;
-    std::unique_ptr<ParcMotionTerrain> h(new (std::nothrow) ParcMotionTerrain());   // every failure below is a plain return
-    if (!h) return fail(PARC_ERR_INVALID, "mterr: out of host memory");
-    h->device = p->device; h->host_model = M;
-    h->cfg.sdf_mode = p->sdf_mode; h->cfg.sort_n = sort_n;
-    h->cfg.z_buf = p->z_buf; h->cfg.jump_buf = (float)p->jump_buf; h->cfg.max_jerk = (float)p->max_jerk;
-    HIPCHK(hipSetDevice(p->device));
-    PARC_TRY(model_upload(h->mem, M, h->d_model));
-    PARC_TRY(h->ev.create());
-    *out = h.release();
-    return PARC_OK;
+    return tool::create("mterr", p->device, M, out, [&](ParcMotionTerrain &h) -> int {
+        h.cfg.sdf_mode = p->sdf_mode; h.cfg.sort_n = sort_n;
+        h.cfg.z_buf = p->z_buf; h.cfg.jump_buf = (float)p->jump_buf; h.cfg.max_jerk = (float)p->max_jerk;
+        return PARC_OK;
+    });
 }
 
 // as parc_mopt_set_clips: validate; release the old batch; build the new one in a local; install it last
@@ -436,9 +421,8 @@ extern "C" int parc_mterr_set_clips(ParcMotionTerrain *h, const ParcMotionOptCli
     const int C = cb.C, B = h->host_model.B, P = h->host_model.P;
     const long long F = cb.F, ncell = cb.ncell;
     HIPCHK(hipSetDevice(h->device));
-    h->batch.reset();
-    std::unique_ptr<ParcMotionTerrain::Batch> nb(new (std::nothrow) ParcMotionTerrain::Batch());
-    if (!nb) return fail(PARC_ERR_INVALID, "mterr: out of host memory");
+    std::unique_ptr<ParcMotionTerrain::Batch> nb;
+    PARC_TRY(tool::renew("mterr", h->batch, nb));
     FrameClips &K = nb->K;
     mterr::Work &W = nb->W;
     DeviceArena &mem = nb->mem;
@@ -462,33 +446,22 @@ extern "C" int parc_mterr_set_clips(ParcMotionTerrain *h, const ParcMotionOptCli
     return PARC_OK;
 }
 
-static int mterr_check(ParcMotionTerrain *h) {
-    if (!h) return fail(PARC_ERR_INVALID, "mterr: null handle");
-    if (!h->batch) return fail(PARC_ERR_STATE, "mterr: parc_mterr_set_clips first");
-    return PARC_OK;
-}
-
 extern "C" int parc_mterr_run(ParcMotionTerrain *h, float *clip_out, int32_t *mask_counts, float *hf_maxmin, int64_t *total_inds) {
-    if (int rc = mterr_check(h)) return rc;
+    PARC_TRY(tool::check_loaded("mterr", h, &ParcMotionTerrain::batch));
     ParcMotionTerrain::Batch &b = *h->batch;
     HIPCHK(hipSetDevice(h->device));
     const long long F = b.F, ncell = b.ncell;
     const int C = b.K.C;
     HIPCHK(hipEventRecord(h->ev[0], 0));
-    hipLaunchKernelGGL(mterr::k_mterr_fk, dim3(blocks(F, 64)), dim3(64), 0, 0, h->d_model, b.K, b.W);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(mterr::k_mterr_fk, dim3(blocks(F, 64)), dim3(64), 0, 0, h->d_model, b.K, b.W));
     HIPCHK(hipEventRecord(h->ev[1], 0));
-    hipLaunchKernelGGL(mterr::k_mterr_init, dim3(blocks(ncell, 256)), dim3(256), 0, 0, ncell, b.W);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(mterr::k_mterr_init, dim3(blocks(ncell, 256)), dim3(256), 0, 0, ncell, b.W));
     HIPCHK(hipEventRecord(h->ev[2], 0));
-    hipLaunchKernelGGL(mterr::k_mterr_points, dim3((unsigned)F), dim3(mterr::PT_THREADS), 0, 0, h->d_model, b.K, b.W, h->cfg);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(mterr::k_mterr_points, dim3((unsigned)F), dim3(mterr::PT_THREADS), 0, 0, h->d_model, b.K, b.W, h->cfg));
     HIPCHK(hipEventRecord(h->ev[3], 0));
-    hipLaunchKernelGGL(mterr::k_mterr_reduce, dim3(blocks(C, 64)), dim3(64), 0, 0, b.K, b.W, h->host_model.B);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(mterr::k_mterr_reduce, dim3(blocks(C, 64)), dim3(64), 0, 0, b.K, b.W, h->host_model.B));
     HIPCHK(hipEventRecord(h->ev[4], 0));
-    hipLaunchKernelGGL(mterr::k_mterr_cells, dim3(blocks(ncell, 256)), dim3(256), 0, 0, b.K, b.W, h->cfg, ncell);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(mterr::k_mterr_cells, dim3(blocks(ncell, 256)), dim3(256), 0, 0, b.K, b.W, h->cfg, ncell));
     HIPCHK(hipEventRecord(h->ev[5], 0));
     HIPCHK(hipMemcpy(b.counts.data(), b.W.cnt, (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
     long long tot = 0;                                        // exclusive scan of the per-frame counts, in frame order
@@ -504,14 +477,8 @@ extern "C" int parc_mterr_run(ParcMotionTerrain *h, float *clip_out, int32_t *ma
     return PARC_OK;
 }
 
-static int mterr_check_ran(ParcMotionTerrain *h) {
-    if (int rc = mterr_check(h)) return rc;
-    if (!h->batch->ran) return fail(PARC_ERR_STATE, "mterr: parc_mterr_run first");
-    return PARC_OK;
-}
-
 extern "C" int parc_mterr_get_mask_inds(ParcMotionTerrain *h, int32_t *inds) {
-    if (int rc = mterr_check_ran(h)) return rc;
+    PARC_TRY(tool::check_ran("mterr", h, &ParcMotionTerrain::batch));
     const ParcMotionTerrain::Batch &b = *h->batch;
     if (!inds && b.total > 0) return fail(PARC_ERR_INVALID, "mterr: null output");
     h->kernel_ms[5] = 0.f;
@@ -524,15 +491,14 @@ extern "C" int parc_mterr_get_mask_inds(ParcMotionTerrain *h, int32_t *inds) {
         h->inds_cap = b.total;
     }
     HIPCHK(hipEventRecord(h->ev[6], 0));
-    hipLaunchKernelGGL(mterr::k_mterr_gather, dim3((unsigned)b.F), dim3(256), 0, 0, b.K, b.W, h->host_model.P, h->d_inds);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(mterr::k_mterr_gather, dim3((unsigned)b.F), dim3(256), 0, 0, b.K, b.W, h->host_model.P, h->d_inds));
     HIPCHK(hipEventRecord(h->ev[7], 0));
     HIPCHK(hipMemcpy(inds, h->d_inds, (size_t)b.total * 2 * sizeof(int), hipMemcpyDeviceToHost));
     return h->ev.elapsed(h->kernel_ms[5], 6, 7);
 }
 
 extern "C" int parc_mterr_get_min_heights(ParcMotionTerrain *h, float *min_heights, int32_t *touched) {
-    if (int rc = mterr_check_ran(h)) return rc;
+    PARC_TRY(tool::check_ran("mterr", h, &ParcMotionTerrain::batch));
     HIPCHK(hipSetDevice(h->device));
     const mterr::Work &W = h->batch->W;
     const size_t n = (size_t)h->batch->ncell;
@@ -546,7 +512,7 @@ extern "C" int parc_mterr_get_min_heights(ParcMotionTerrain *h, float *min_heigh
 }
 
 extern "C" int parc_mterr_point_sdf(ParcMotionTerrain *h, int64_t frame0, int32_t num_frames, float *ground, float *air) {
-    if (int rc = mterr_check_ran(h)) return rc;
+    PARC_TRY(tool::check_ran("mterr", h, &ParcMotionTerrain::batch));
     const ParcMotionTerrain::Batch &b = *h->batch;
     if (num_frames < 1 || frame0 < 0 || frame0 + num_frames > b.F || !ground || !air) return fail(PARC_ERR_INVALID, "mterr: bad point_sdf range");
     HIPCHK(hipSetDevice(h->device));
@@ -554,16 +520,13 @@ extern "C" int parc_mterr_point_sdf(ParcMotionTerrain *h, int64_t frame0, int32_
     DeviceArena tmp;                      // this call's output
     float *d = nullptr;
     PARC_TRY(tmp.alloc(d, 2 * (long long)n));
-    hipLaunchKernelGGL(mterr::k_mterr_point_sdf, dim3((unsigned)num_frames), dim3(mterr::PT_THREADS), 0, 0, h->d_model, b.K, b.W, h->cfg,
-                       (long long)frame0, d, d + n);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(mterr::k_mterr_point_sdf, dim3((unsigned)num_frames), dim3(mterr::PT_THREADS), 0, 0, h->d_model, b.K, b.W, h->cfg,
+                       (long long)frame0, d, d + n));
     HIPCHK(hipMemcpy(ground, d, n * sizeof(float), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(air, d + n, n * sizeof(float), hipMemcpyDeviceToHost));
     return PARC_OK;
 }
 
 extern "C" int parc_mterr_kernel_times(ParcMotionTerrain *h, float *ms6) {
-    if (!h || !ms6) return fail(PARC_ERR_INVALID, "mterr: null argument");
-    for (int k = 0; k < 6; ++k) ms6[k] = h->kernel_ms[k];
-    return PARC_OK;
+    return tool::stored_times("mterr", h, &ParcMotionTerrain::kernel_ms, ms6);
 }

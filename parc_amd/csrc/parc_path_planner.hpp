@@ -28,6 +28,7 @@
 #include "../../include/parc_env.h"
 #include "parc_common.hpp"
 #include "parc_math.hpp"
+#include "parc_tool_handle.hpp"
 
 namespace pplan {
 using namespace parc;
@@ -390,26 +391,22 @@ __global__ void __launch_bounds__(64) k_pp_graph(Cfg G, const float *hf, int q0,
 }  // namespace pplan
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------------
-struct ParcPathPlanner {
+struct ParcPathPlanner : tool::Handle<DeviceEvents<3>> {   // mem: unused, the buffers are the batch's
     struct Batch {                        // the buffers of up to cap queries; they exist once the handle holds one
         DeviceArena mem;
         pplan::Bufs B{};
         int cap = 0, last_q = 0;          // last_q: queries of the last completed run (0 = none), what parc_pathplan_get_graph may read
     };
-    int device = 0;
     pplan::Cfg cfg{};
     std::unique_ptr<Batch> batch;
-    DeviceEvents<3> ev;
     float graph_ms = 0.f;
     bool timed = false;
-    ~ParcPathPlanner() { (void)hipSetDevice(device); }   // the members release the rest
 };
 
-extern "C" void parc_pathplan_destroy(ParcPathPlanner *h) { delete h; }
+extern "C" void parc_pathplan_destroy(ParcPathPlanner *h) { tool::destroy(h); }
 
 extern "C" int parc_pathplan_create(const ParcPathPlanParams *p, ParcPathPlanner **out) {
-    if (!p || !out) return fail(PARC_ERR_INVALID, "pathplan: null argument");
-    if (p->struct_size != sizeof(ParcPathPlanParams)) return fail(PARC_ERR_INVALID, "ParcPathPlanParams ABI mismatch (struct_size)");
+    PARC_TRY(tool::create_args("pathplan", "ParcPathPlanParams", p, out));
     if (p->dim_x < 4 || p->dim_y < 4 || p->dim_x > PARC_PATHPLAN_MAX_DIM || p->dim_y > PARC_PATHPLAN_MAX_DIM)
         return fail(PARC_ERR_INVALID, "pathplan: the grid is " + std::to_string(p->dim_x) + " x " + std::to_string(p->dim_y) + ", the planner takes 4 .. " +
                                           std::to_string(PARC_PATHPLAN_MAX_DIM) + " cells a side (PARC_PATHPLAN_MAX_DIM: a query's search state lives in LDS)");
@@ -420,34 +417,30 @@ extern "C" int parc_pathplan_create(const ParcPathPlanParams *p, ParcPathPlanner
         return fail(PARC_ERR_INVALID, "pathplan: max_jump_xy_dist / dx gives a jump window radius of " + std::to_string((long long)rr) + " cells, above the limit of " +
                                           std::to_string(PARC_PATHPLAN_MAX_JUMP_RADIUS) + " (PARC_PATHPLAN_MAX_JUMP_RADIUS)");
     if (p->max_expansions < 1 || p->max_nodes < 1 || p->max_points < 1) return fail(PARC_ERR_INVALID, "pathplan: max_expansions, max_nodes and max_points must be >= 1");
-    std::unique_ptr<ParcPathPlanner> h(new (std::nothrow) ParcPathPlanner());   // every failure below is a plain return
-    if (!h) return fail(PARC_ERR_INVALID, "pathplan: out of host memory");
-    h->device = p->device;
-    pplan::Cfg &G = h->cfg;
-    G.X = p->dim_x; G.Y = p->dim_y; G.R = (int)rr; G.simplify = p->simplify_terrain; G.max_expansions = p->max_expansions;
-    G.max_nodes = p->max_nodes; G.max_points = p->max_points; G.use_bumpy = p->w_bumpy != 0.0;
-    G.dx = p->dx; G.dy = p->dy; G.minx = p->min_point[0]; G.miny = p->min_point[1];
-    // the reference compares and multiplies its Python-float settings as fp32 weak scalars
-    G.max_z = (float)p->max_z_diff; G.max_jxy = (float)p->max_jump_xy_dist; G.max_jz = (float)p->max_jump_z_diff; G.min_jz = (float)p->min_jump_z_diff;
-    G.w_z = (float)p->w_z; G.w_xy = (float)p->w_xy; G.noise_w = (float)(p->uniform_cost_max - p->uniform_cost_min); G.noise_min = (float)p->uniform_cost_min;
-    G.max_cost = (float)p->max_cost; G.draw_thr = (float)(p->min_start_end_xy_dist - 1e-4);
-    G.w_bumpy = p->w_bumpy; G.max_bumpy = p->max_bumpy; G.dxd = (double)p->dx;
-    G.split = sqrt((double)p->dx * (double)p->dx + (double)p->dy * (double)p->dy) + 1e-3;
-    HIPCHK(hipSetDevice(p->device));
-    PARC_TRY(h->ev.create());
-    if (hipFuncSetAttribute((const void *)pplan::k_pp_search, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pplan::search_lds(G.X * G.Y)) != hipSuccess)
-        return fail(PARC_ERR_HIP, "pathplan: the search kernel's LDS request was refused");
-    *out = h.release();
-    return PARC_OK;
+    return tool::create("pathplan", p->device, out, [&](ParcPathPlanner &h) -> int {
+        pplan::Cfg &G = h.cfg;
+        G.X = p->dim_x; G.Y = p->dim_y; G.R = (int)rr; G.simplify = p->simplify_terrain; G.max_expansions = p->max_expansions;
+        G.max_nodes = p->max_nodes; G.max_points = p->max_points; G.use_bumpy = p->w_bumpy != 0.0;
+        G.dx = p->dx; G.dy = p->dy; G.minx = p->min_point[0]; G.miny = p->min_point[1];
+        // the reference compares and multiplies its Python-float settings as fp32 weak scalars
+        G.max_z = (float)p->max_z_diff; G.max_jxy = (float)p->max_jump_xy_dist; G.max_jz = (float)p->max_jump_z_diff; G.min_jz = (float)p->min_jump_z_diff;
+        G.w_z = (float)p->w_z; G.w_xy = (float)p->w_xy; G.noise_w = (float)(p->uniform_cost_max - p->uniform_cost_min); G.noise_min = (float)p->uniform_cost_min;
+        G.max_cost = (float)p->max_cost; G.draw_thr = (float)(p->min_start_end_xy_dist - 1e-4);
+        G.w_bumpy = p->w_bumpy; G.max_bumpy = p->max_bumpy; G.dxd = (double)p->dx;
+        G.split = sqrt((double)p->dx * (double)p->dx + (double)p->dy * (double)p->dy) + 1e-3;
+        PARC_TRY(h.ev.create());
+        if (hipFuncSetAttribute((const void *)pplan::k_pp_search, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pplan::search_lds(G.X * G.Y)) != hipSuccess)
+            return fail(PARC_ERR_HIP, "pathplan: the search kernel's LDS request was refused");
+        return PARC_OK;
+    });
 }
 
 // Buffers for Q queries: kept while they are large enough; otherwise the old ones are released first, the new ones built in a local and
 // installed last, so a failed allocation leaves the handle without buffers (and without a last batch), never with some of them.
 static int pplan_reserve(ParcPathPlanner *h, int Q) {
     if (h->batch && Q <= h->batch->cap) return PARC_OK;
-    h->batch.reset();
-    std::unique_ptr<ParcPathPlanner::Batch> nb(new (std::nothrow) ParcPathPlanner::Batch());
-    if (!nb) return fail(PARC_ERR_INVALID, "pathplan: out of host memory");
+    std::unique_ptr<ParcPathPlanner::Batch> nb;
+    PARC_TRY(tool::renew("pathplan", h->batch, nb));
     const pplan::Cfg &G = h->cfg;
     const long long N = (long long)G.X * G.Y;
     pplan::Bufs &B = nb->B;
@@ -487,13 +480,11 @@ extern "C" int parc_pathplan_run(ParcPathPlanner *h, int32_t Q, const float *hf_
         HIPCHK(hipMemcpy(B.goal, goal_host, (size_t)Q * 2 * sizeof(int), hipMemcpyHostToDevice));
     }
     HIPCHK(hipEventRecord(h->ev[0], 0));
-    hipLaunchKernelGGL(pplan::k_pp_prepare, dim3((unsigned)Q), dim3(64), (size_t)N * sizeof(float), 0, G, B, start_host ? 1 : 0, (unsigned long long)seed,
-                       (unsigned long long)first_query);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(pplan::k_pp_prepare, dim3((unsigned)Q), dim3(64), (size_t)N * sizeof(float), 0, G, B, start_host ? 1 : 0, (unsigned long long)seed,
+                       (unsigned long long)first_query));
     HIPCHK(hipEventRecord(h->ev[1], 0));
-    hipLaunchKernelGGL(pplan::k_pp_search, dim3((unsigned)Q), dim3(64), pplan::search_lds((int)N), 0, G, B, (unsigned long long)seed,
-                       (unsigned long long)first_query);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(pplan::k_pp_search, dim3((unsigned)Q), dim3(64), pplan::search_lds((int)N), 0, G, B, (unsigned long long)seed,
+                       (unsigned long long)first_query));
     HIPCHK(hipEventRecord(h->ev[2], 0));
     HIPCHK(hipEventSynchronize(h->ev[2]));
     h->timed = true;
@@ -528,9 +519,8 @@ extern "C" int parc_pathplan_get_graph(ParcPathPlanner *h, int32_t q0, int32_t n
     PARC_TRY(tmp.alloc(d_jump, cells * PARC_PATHPLAN_JUMP_WORDS));
     PARC_TRY(t.create());
     HIPCHK(hipEventRecord(t[0], 0));
-    hipLaunchKernelGGL(pplan::k_pp_graph, dim3((unsigned)n), dim3(64), (size_t)G.X * G.Y * sizeof(float) + (size_t)((G.X * G.Y + 31) / 32) * 4, 0, G, h->batch->B.hf,
-                       (int)q0, d_nbr, d_cliff, d_jump);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(pplan::k_pp_graph, dim3((unsigned)n), dim3(64), (size_t)G.X * G.Y * sizeof(float) + (size_t)((G.X * G.Y + 31) / 32) * 4, 0, G, h->batch->B.hf,
+                       (int)q0, d_nbr, d_cliff, d_jump));
     HIPCHK(hipEventRecord(t[1], 0));
     HIPCHK(hipMemcpy(nbr_host, d_nbr, (size_t)cells, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(cliff_host, d_cliff, (size_t)cells, hipMemcpyDeviceToHost));
@@ -540,9 +530,8 @@ extern "C" int parc_pathplan_get_graph(ParcPathPlanner *h, int32_t q0, int32_t n
 
 extern "C" int parc_pathplan_kernel_times(ParcPathPlanner *h, float *ms3) {
     if (!h || !ms3) return fail(PARC_ERR_INVALID, "pathplan: null argument");
-    if (!h->timed) return fail(PARC_ERR_STATE, "pathplan: nothing planned yet");
-    HIPCHK(hipSetDevice(h->device));
-    for (int k = 0; k < 2; ++k) PARC_TRY(h->ev.elapsed(ms3[k], k, k + 1));
+    const tool::Span spans[] = {{h->timed, 0, 1}, {h->timed, 1, 2}};   // prepare, search
+    PARC_TRY(tool::span_times("pathplan: nothing planned yet", h->device, h->ev, spans, ms3));
     ms3[2] = h->graph_ms;
     return PARC_OK;
 }

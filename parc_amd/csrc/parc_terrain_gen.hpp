@@ -25,6 +25,7 @@
 #include "../../include/parc_env.h"
 #include "parc_common.hpp"
 #include "parc_math.hpp"
+#include "parc_tool_handle.hpp"
 
 namespace tgen {
 using namespace parc;
@@ -280,21 +281,16 @@ __global__ void k_tgen_validate_steps(const float *stairs, long long count, floa
 }  // namespace tgen
 
 // ---- C-ABI --------------------------------------------------------------------------------------------------------------------------
-struct ParcTerrainGen {
-    int device = 0;
+struct ParcTerrainGen : tool::Handle<DeviceEvents<4>> {   // mem: status
     tgen::Cfg cfg{};
-    DeviceArena mem;                      // create .. destroy: d_status
-    int *d_status = nullptr;
-    DeviceEvents<4> ev;
+    tool::StatusWords status;             // one word: the validate pass'
     bool drew = false, ran = false;
-    ~ParcTerrainGen() { (void)hipSetDevice(device); }   // the members release the rest
 };
 
-extern "C" void parc_tgen_destroy(ParcTerrainGen *h) { delete h; }
+extern "C" void parc_tgen_destroy(ParcTerrainGen *h) { tool::destroy(h); }
 
 extern "C" int parc_tgen_create(const ParcTerrainGenParams *p, ParcTerrainGen **out) {
-    if (!p || !out) return fail(PARC_ERR_INVALID, "tgen: null argument");
-    if (p->struct_size != sizeof(ParcTerrainGenParams)) return fail(PARC_ERR_INVALID, "ParcTerrainGenParams ABI mismatch (struct_size)");
+    PARC_TRY(tool::create_args("tgen", "ParcTerrainGenParams", p, out));
     if (p->mode < PARC_TGEN_BOXES || p->mode > PARC_TGEN_STAIRS) return fail(PARC_ERR_INVALID, "tgen: mode must be PARC_TGEN_BOXES, PATHS or STAIRS");
     if (p->dim_x < 4 || p->dim_y < 4 || p->dim_x > PARC_TGEN_MAX_DIM || p->dim_y > PARC_TGEN_MAX_DIM)
         return fail(PARC_ERR_INVALID, "tgen: a " + std::to_string(p->dim_x) + " x " + std::to_string(p->dim_y) + " grid; sides must be 4 .. PARC_TGEN_MAX_DIM = " +
@@ -309,21 +305,17 @@ extern "C" int parc_tgen_create(const ParcTerrainGenParams *p, ParcTerrainGen **
         return fail(PARC_ERR_INVALID, "tgen: maxpool_size = " + std::to_string(p->maxpool_size) + " must be 0 .. PARC_TGEN_MAX_POOL = " + std::to_string(PARC_TGEN_MAX_POOL));
     if (p->mode == PARC_TGEN_STAIRS && (p->num_stairs < 1 || p->num_stairs > PARC_TGEN_MAX_STAIRS))
         return fail(PARC_ERR_INVALID, "tgen: num_stairs = " + std::to_string(p->num_stairs) + " must be 1 .. PARC_TGEN_MAX_STAIRS = " + std::to_string(PARC_TGEN_MAX_STAIRS));
-    std::unique_ptr<ParcTerrainGen> h(new (std::nothrow) ParcTerrainGen());   // every failure below is a plain return
-    if (!h) return fail(PARC_ERR_INVALID, "tgen: out of host memory");
-    h->device = p->device;
-    tgen::Cfg &G = h->cfg;
-    G.mode = p->mode; G.X = p->dim_x; G.Y = p->dim_y; G.nb = p->num_boxes; G.np = p->num_terrain_paths; G.pool = p->maxpool_size; G.ns = p->num_stairs;
-    G.dx = p->dx; G.dy = p->dy; G.minx = p->min_point[0]; G.miny = p->min_point[1];
-    G.bh0 = p->min_box_h; G.bh1 = p->max_box_h; G.len0 = p->box_min_len; G.len1 = p->box_max_len; G.ang0 = p->min_box_angle; G.ang1 = p->max_box_angle;
-    G.ph0 = p->path_min_height; G.ph1 = p->path_max_height; G.floor_h = p->floor_height;
-    G.sh0 = p->min_stair_start_height; G.sh1 = p->max_stair_start_height; G.st0 = p->min_step_height; G.st1 = p->max_step_height;
-    G.th0 = p->min_stair_thickness; G.th1 = p->max_stair_thickness;
-    HIPCHK(hipSetDevice(h->device));
-    PARC_TRY(h->mem.alloc_fill(h->d_status, 1));
-    PARC_TRY(h->ev.create());
-    *out = h.release();
-    return PARC_OK;
+    return tool::create("tgen", p->device, out, [&](ParcTerrainGen &h) -> int {
+        tgen::Cfg &G = h.cfg;
+        G.mode = p->mode; G.X = p->dim_x; G.Y = p->dim_y; G.nb = p->num_boxes; G.np = p->num_terrain_paths; G.pool = p->maxpool_size; G.ns = p->num_stairs;
+        G.dx = p->dx; G.dy = p->dy; G.minx = p->min_point[0]; G.miny = p->min_point[1];
+        G.bh0 = p->min_box_h; G.bh1 = p->max_box_h; G.len0 = p->box_min_len; G.len1 = p->box_max_len; G.ang0 = p->min_box_angle; G.ang1 = p->max_box_angle;
+        G.ph0 = p->path_min_height; G.ph1 = p->path_max_height; G.floor_h = p->floor_height;
+        G.sh0 = p->min_stair_start_height; G.sh1 = p->max_stair_start_height; G.st0 = p->min_step_height; G.st1 = p->max_step_height;
+        G.th0 = p->min_stair_thickness; G.th1 = p->max_stair_thickness;
+        PARC_TRY(h.status.alloc(h.mem, 1));
+        return h.ev.create();
+    });
 }
 
 static tgen::PlanD tgen_plan(const ParcTerrainGenPlan *p) {
@@ -352,12 +344,11 @@ static int tgen_launch(ParcTerrainGen *h, int n, const tgen::PlanD &P, float *hf
     const tgen::Cfg &G = h->cfg;
     HIPCHK(hipEventRecord(h->ev[2], st));
     if (G.mode == PARC_TGEN_BOXES)
-        hipLaunchKernelGGL(tgen::k_tgen_boxes<DRAW>, dim3((unsigned)n), dim3(64), 0, st, G, P, hf, seed, first);
+        PARC_TRY(tool::launch(tgen::k_tgen_boxes<DRAW>, dim3((unsigned)n), dim3(64), 0, st, G, P, hf, seed, first));
     else if (G.mode == PARC_TGEN_STAIRS)
-        hipLaunchKernelGGL(tgen::k_tgen_stairs<DRAW>, dim3((unsigned)n), dim3(64), 0, st, G, P, hf, seed, first);
+        PARC_TRY(tool::launch(tgen::k_tgen_stairs<DRAW>, dim3((unsigned)n), dim3(64), 0, st, G, P, hf, seed, first));
     else
-        hipLaunchKernelGGL(tgen::k_tgen_paths<DRAW>, dim3((unsigned)n), dim3(64), (size_t)G.X * G.Y * 2 * sizeof(float), st, G, P, hf, seed, first);
-    HIPCHK(hipGetLastError());
+        PARC_TRY(tool::launch(tgen::k_tgen_paths<DRAW>, dim3((unsigned)n), dim3(64), (size_t)G.X * G.Y * 2 * sizeof(float), st, G, P, hf, seed, first));
     HIPCHK(hipEventRecord(h->ev[3], st));
     h->ran = true;
     return PARC_OK;
@@ -371,9 +362,8 @@ extern "C" int parc_tgen_draw_plan(ParcTerrainGen *h, uint64_t seed, uint64_t fi
     const long long items = G.mode == PARC_TGEN_BOXES ? n * G.nb : (G.mode == PARC_TGEN_STAIRS ? n * G.ns : n * G.np * (tgen::PTS / 4));
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipEventRecord(h->ev[0], st));
-    hipLaunchKernelGGL(tgen::k_tgen_draw, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, G, tgen_plan(plan), n, (unsigned long long)seed,
-                       (unsigned long long)first_terrain);
-    HIPCHK(hipGetLastError());
+    PARC_TRY(tool::launch(tgen::k_tgen_draw, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, G, tgen_plan(plan), n, (unsigned long long)seed,
+                       (unsigned long long)first_terrain));
     HIPCHK(hipEventRecord(h->ev[1], st));
     h->drew = true;
     return PARC_OK;
@@ -384,6 +374,7 @@ static int tgen_validate(ParcTerrainGen *h, const ParcTerrainGenPlan *p, hipStre
     const tgen::Cfg &G = h->cfg;
     const long long n = p->n;
     struct Field { const char *name; const float *a; long long count; };
+    constexpr int STEPS_BIT = 8;           // above the fields' bits (a mode has at most five)
     std::vector<Field> f;
     if (G.mode == PARC_TGEN_BOXES) f.push_back({"boxes", p->boxes, n * G.nb * tgen::BF});
     else if (G.mode == PARC_TGEN_STAIRS) f.push_back({"stairs", p->stairs, n * G.ns * tgen::SF});
@@ -392,23 +383,20 @@ static int tgen_validate(ParcTerrainGen *h, const ParcTerrainGenPlan *p, hipStre
         f.push_back({"path_angle", p->path_angle, n * G.np}); f.push_back({"path_turn", p->path_turn, n * G.np * tgen::PTS});
         f.push_back({"path_height", p->path_height, n * G.np});
     }
-    HIPCHK(hipMemsetAsync(h->d_status, 0, sizeof(int), st));
+    PARC_TRY(h->status.clear(0, st));
     for (size_t k = 0; k < f.size(); ++k) {
-        hipLaunchKernelGGL(tgen::k_tgen_validate, dim3((unsigned)((f[k].count + 255) / 256)), dim3(256), 0, st, f[k].a, f[k].count, 1 << k, h->d_status);
-        HIPCHK(hipGetLastError());
+        PARC_TRY(tool::launch(tgen::k_tgen_validate, dim3((unsigned)((f[k].count + 255) / 256)), dim3(256), 0, st, f[k].a, f[k].count, 1 << k, h->status.d));
     }
     if (G.mode == PARC_TGEN_STAIRS) {
-        hipLaunchKernelGGL(tgen::k_tgen_validate_steps, dim3((unsigned)((n * G.ns + 255) / 256)), dim3(256), 0, st, p->stairs, n * G.ns, G.dx, 1 << 8, h->d_status);
-        HIPCHK(hipGetLastError());
+        PARC_TRY(tool::launch(tgen::k_tgen_validate_steps, dim3((unsigned)((n * G.ns + 255) / 256)), dim3(256), 0, st, p->stairs, n * G.ns, G.dx, 1 << STEPS_BIT, h->status.d));
     }
     int v = 0;
-    HIPCHK(hipMemcpyAsync(&v, h->d_status, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    PARC_TRY(h->status.read(0, st, v));
     if (!v) return PARC_OK;
-    std::string msg;
-    for (size_t k = 0; k < f.size(); ++k) if (v & (1 << k)) msg += std::string(msg.empty() ? "" : "; ") + f[k].name + " holds a value that is not finite";
-    if (v & (1 << 8)) msg += std::string(msg.empty() ? "" : "; ") + "stairs: a stair needs more than PARC_TGEN_MAX_STEPS = " + std::to_string(PARC_TGEN_MAX_STEPS) + " steps";
-    return fail(PARC_ERR_INVALID, "tgen: bad plan: " + msg);
+    std::string names[STEPS_BIT + 1];      // bit k: field k; the last: the stairs' step count
+    for (size_t k = 0; k < f.size(); ++k) names[k] = std::string(f[k].name) + " holds a value that is not finite";
+    names[STEPS_BIT] = "stairs: a stair needs more than PARC_TGEN_MAX_STEPS = " + std::to_string(PARC_TGEN_MAX_STEPS) + " steps";
+    return tool::bad_plan("tgen", v, names);
 }
 
 extern "C" int parc_tgen_generate_with(ParcTerrainGen *h, const ParcTerrainGenPlan *plan, float *hf, int32_t validate, void *stream) {
@@ -428,10 +416,6 @@ extern "C" int parc_tgen_generate(ParcTerrainGen *h, int32_t n, uint64_t seed, u
 
 extern "C" int parc_tgen_kernel_times(ParcTerrainGen *h, float *ms2) {
     if (!h || !ms2) return fail(PARC_ERR_INVALID, "tgen: null argument");
-    if (!h->drew && !h->ran) return fail(PARC_ERR_STATE, "tgen: nothing generated yet");
-    HIPCHK(hipSetDevice(h->device));
-    ms2[0] = ms2[1] = 0.f;
-    if (h->drew) { HIPCHK(hipEventSynchronize(h->ev[1])); PARC_TRY(h->ev.elapsed(ms2[0], 0, 1)); }
-    if (h->ran) { HIPCHK(hipEventSynchronize(h->ev[3])); PARC_TRY(h->ev.elapsed(ms2[1], 2, 3)); }
-    return PARC_OK;
+    const tool::Span spans[] = {{h->drew, 0, 1}, {h->ran, 2, 3}};   // draw, generate
+    return tool::span_times("tgen: nothing generated yet", h->device, h->ev, spans, ms2);
 }

@@ -1,10 +1,11 @@
 // parc_tools.hip -- the stage-2 motion tools and the learner's kernels of include/parc_env.h as one translation unit, apart from the env
 // (parc_env.hip) and the dynamics (parc_dynamics.hip).
-// Every header includes what it uses; the order below does not matter.  The first three are what the tools share; no tool header
+// Every header includes what it uses; the order below does not matter.  The first four are what the tools share; no tool header
 // includes another tool's, but for the path rollout, which runs the generator.
 #include "parc_char.hpp"             // the character as the motion tools see it: CharTree / CharPoints, fk_frame, the vector helpers
 #include "parc_grid.hpp"             // heightfield helpers of more than one tool: to_i64, grid_index, sd_box
 #include "parc_clip_batch.hpp"       // the clip batch: the device views ClipArrays / FrameClips, validation and upload
+#include "parc_tool_handle.hpp"      // the host skeleton of a handle: checked launch, create, slots, state guards, status words, kernel times
 #include "parc_motion_opt.hpp"       // parc_mopt_*: the batched kinematic motion optimiser
 #include "parc_motion_terrain.hpp"   // parc_mterr_*: motion-terrain analysis
 #include "parc_motion_edit.hpp"      // parc_medit_*: stage 2's hesitation-frame removal

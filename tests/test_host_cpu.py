@@ -385,10 +385,10 @@ def test_tool_headers_include_only_the_shared_headers():
     """No motion tool is written against another tool's types: a tool header includes the C-ABI header and the shared headers only
     (the path rollout also the generator, which it runs), and mopt:: is spelled in the optimiser alone.  Source text only."""
     csrc = os.path.join(REPO, "parc_amd", "csrc")
-    tools = ["parc_motion_opt", "parc_motion_terrain", "parc_motion_sampler", "parc_motion_aug", "parc_mdm", "parc_mdm_path",
-             "parc_path_planner", "parc_terrain_gen", "parc_learner"]
+    tools = ["parc_motion_opt", "parc_motion_terrain", "parc_motion_edit", "parc_motion_sampler", "parc_motion_aug", "parc_mdm", "parc_mdm_path",
+             "parc_mdm_loss", "parc_path_planner", "parc_terrain_gen", "parc_learner"]
     shared = {"../../include/parc_env.h", "parc_common.hpp", "parc_math.hpp", "parc_char.hpp", "parc_grid.hpp", "parc_clip_batch.hpp",
-              "parc_motion_table.hpp"}
+              "parc_motion_table.hpp", "parc_tool_handle.hpp"}
     for t in tools:
         with open(os.path.join(csrc, t + ".hpp")) as f:
             inc = re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), re.M)

@@ -230,3 +230,71 @@ def test_a_failed_create_leaves_no_handle():
     o.__del__()
     o.__del__()
     assert o._h is None and calls == ["create", "destroy"]
+
+
+# ---- the native side of a handle: what every parc_*_create and parc_*_kernel_times refuses before it touches a device ----------------
+CREATES = {"mopt": L.ParcMotionOptParams, "mterr": L.ParcMotionTerrainParams, "medit": L.ParcMotionEditParams, "msamp": L.ParcMotionSamplerParams,
+           "maug": L.ParcMotionAugParams, "pathplan": L.ParcPathPlanParams, "tgen": L.ParcTerrainGenParams, "mdm": L.ParcMdmParams,
+           "mpath": L.ParcMdmPathParams, "mloss": L.ParcMotionLossParams}
+WITH_CHAR = ("mopt", "mterr", "medit", "msamp", "maug", "mdm", "mloss")       # the tools whose parameters hold a ParcCharModel
+MIN_TWO_BODIES = ("msamp", "maug", "mdm", "mloss")
+CHECK_DOF_SIZE = ("mopt", "mterr", "medit", "mloss")
+
+
+def refused(pre, params, message):
+    """parc_<pre>_create(params) is PARC_ERR_INVALID with exactly `message`, and the out handle stays null."""
+    lib = L.load()
+    out = C.c_void_p()
+    rc = getattr(lib, f"parc_{pre}_create")(None if params is None else C.byref(params), C.byref(out))
+    assert rc == -1 and lib.parc_last_error().decode() == message and not out.value, (pre, rc, lib.parc_last_error().decode())
+
+
+def sized(pre, num_bodies=2, dof_size=0):
+    p = CREATES[pre]()
+    p.struct_size = C.sizeof(p)
+    if pre in WITH_CHAR:
+        p.model.num_bodies, p.model.dof_size = num_bodies, dof_size
+    return p
+
+
+def test_the_character_tools_are_the_ones_with_a_model():
+    assert sorted(WITH_CHAR) == sorted(pre for pre, t in CREATES.items() if any(f[0] == "model" and f[1] is L.ParcCharModel for f in t._fields_))
+
+
+@pytest.mark.parametrize("pre", CREATES)
+def test_create_refuses_null_and_a_wrong_struct_size(pre):
+    refused(pre, None, f"{pre}: null argument")
+    p = sized(pre)
+    p.struct_size += 1
+    refused(pre, p, f"{CREATES[pre].__name__} ABI mismatch (struct_size)")
+    lib = L.load()                                          # a null out pointer is the same refusal
+    assert getattr(lib, f"parc_{pre}_create")(C.byref(sized(pre)), None) == -1 and lib.parc_last_error().decode() == f"{pre}: null argument"
+
+
+@pytest.mark.parametrize("pre", WITH_CHAR)
+def test_create_checks_the_body_count_against_the_tools_minimum(pre):
+    refused(pre, sized(pre, num_bodies=0), f"{pre}: num_bodies out of range")
+    refused(pre, sized(pre, num_bodies=L.MAX_BODIES + 1), f"{pre}: num_bodies out of range")
+    lib = L.load()
+    out = C.c_void_p()
+    rc = getattr(lib, f"parc_{pre}_create")(C.byref(sized(pre, num_bodies=1)), C.byref(out))
+    assert rc == -1 and not out.value                       # (a zeroed struct is refused by every tool, further down)
+    assert (lib.parc_last_error().decode() == f"{pre}: num_bodies out of range") == (pre in MIN_TWO_BODIES), pre
+
+
+@pytest.mark.parametrize("pre", WITH_CHAR)
+def test_create_checks_dof_size_where_the_tool_does(pre):
+    lib = L.load()
+    out = C.c_void_p()
+    for bad in (L.MAX_DOFS + 1, -1):
+        rc = getattr(lib, f"parc_{pre}_create")(C.byref(sized(pre, dof_size=bad)), C.byref(out))
+        assert rc == -1 and not out.value
+        assert (lib.parc_last_error().decode() == f"{pre}: dof_size out of range") == (pre in CHECK_DOF_SIZE), pre
+
+
+@pytest.mark.parametrize("pre", CREATES)
+def test_kernel_times_refuses_a_null_handle(pre):
+    lib = L.load()
+    buf = (C.c_float * 8)(*([7.0] * 8))
+    assert getattr(lib, f"parc_{pre}_kernel_times")(None, buf) == -1 and lib.parc_last_error().decode() == f"{pre}: null argument"
+    assert list(buf) == [7.0] * 8
