@@ -1058,6 +1058,63 @@ int parc_mpath_kernel_times(ParcMdmPath *h, float *ms2);
 /* max_frames, max_windows, FD; then of the last rollout: windows, kernel launches, frames per row. */
 int parc_mpath_describe(ParcMdmPath *h, int64_t *out6);
 
+/* ---- rollout selection: score, filter and rank the rows of a rollout on the device (parc_msel_*) ---------------------
+ * The end of mdm_path.generate_frames_until_end_of_path (mdm_path.py:386-433) and the acceptance test of parc_2_kin_gen.py:389-404.  A
+ * row's motion is frames[0:final_frame] as Python slices it (-1 drops the last frame).  With slice_terrain it is scored on its own slice
+ * of its terrain (terrain_util.slice_terrain_around_motion, localize=False: the root's xy bounds -+ slice_padding, rounded to grid
+ * points; cells beyond the terrain repeat its edge cells), else on the whole terrain; base_z is the lowest height of that view - 10.
+ * contact = w_contact x sum, pen = w_pen x sum, total = contact + pen (+ not_finished_penalty where final_frame < 0, + noise); a row is
+ * valid when all three lie under their thresholds.  The rows of a path are ranked by total, ascending and stable, NaN last.  The scene,
+ * the character and the layout of the frame buffer are the path handle's.  A row's results do not depend on its batch. */
+#define PARC_MSEL_MAX_SLICE_DIM 1024             /* cells per side of a slice */
+#define PARC_MSEL_STATUS_NONFINITE 1             /* a root position of the row's motion is not finite */
+#define PARC_MSEL_STATUS_TOO_LARGE 2             /* a side of the slice exceeds PARC_MSEL_MAX_SLICE_DIM */
+#define PARC_MSEL_STATUS_EMPTY 4                 /* the row's motion has no frame */
+#define PARC_MSEL_RUN_LAUNCHES 4                 /* kernel launches of one parc_msel_run */
+typedef struct ParcPathSelect ParcPathSelect;
+typedef struct {
+    uint32_t struct_size;                    /* sizeof(ParcPathSelectParams) */
+    ParcMdmPath *mpath;                      /* the path handle: its scene, character, max_batch and max_frames; it must outlive this handle */
+    int32_t num_points;                      /* as ParcMotionTerrainParams */
+    const float *points_host;                /* [num_points][3] body-local */
+    const int32_t *point_body_host;          /* [num_points] */
+    int32_t contact_body_id[PARC_MAX_BODIES];/* column of a frame's contacts of each body, -1 = not scored */
+    float w_contact, w_pen;                  /* MDMPathSettings */
+    float not_finished_penalty;              /* reference: 100 */
+    float slice_padding;                     /* reference: 1.2 */
+    int32_t sdf_mode;                        /* PARC_MTERR_SDF_* */
+} ParcPathSelectParams;
+typedef struct {
+    const float *frames;                     /* device [n][frame_stride][FD], parc_mpath_rollout's layout; n = the scene's rows */
+    int32_t num_frames;                      /* frames of the rollout, 1 .. min(frame_stride, the path handle's max_frames) */
+    int32_t frame_stride;                    /* frames a row of the buffer holds */
+    const int32_t *final_frame;              /* device [n] */
+    const float *noise;                      /* device [n] added to the totals, or NULL */
+    int32_t slice_terrain;
+    float max_contact_loss, max_pen_loss, max_total_loss;   /* INFINITY = off */
+} ParcPathSelectArgs;
+typedef struct {                             /* host arrays, NULL = not copied */
+    float *contact_loss, *pen_loss, *total_loss;   /* [n] weighted; total as ranked; NaN for a row with a status bit */
+    int32_t *valid, *status, *num_frames;    /* [n] */
+    float *slice_min_point;                  /* [n][2]: of the view the row was scored on (the terrain's without slice_terrain) */
+    int32_t *slice_dims;                     /* [n][2] */
+    int32_t *order;                          /* [n]: the rows of path 0 sorted, then those of path 1, ... */
+    int32_t *num_valid;                      /* [P] */
+} ParcPathSelectResults;
+int parc_msel_create(const ParcPathSelectParams *p, ParcPathSelect **out);
+void parc_msel_destroy(ParcPathSelect *h);
+/* k_msel_bounds, k_msel_fk, k_msel_score, k_msel_rank on the stream; no host sync.  PARC_ERR_STATE without a scene. */
+int parc_msel_run(ParcPathSelect *h, const ParcPathSelectArgs *a, void *stream);
+/* The last run's results to the host (waits for the stream). */
+int parc_msel_results(ParcPathSelect *h, const ParcPathSelectResults *r, void *stream);
+/* The heightfields of the views of the named rows, packed one after the other (row i: dims[0] x dims[1] floats, none for a row with a
+ * status bit): the sliced_hf of terrain_util.py:1613.  One launch; capacity = the floats hf_host holds. */
+int parc_msel_gather(ParcPathSelect *h, const int32_t *rows_host, int32_t count, float *hf_host, int64_t capacity, void *stream);
+/* Device ms of the last run: bounds, fk, score, rank, and gather (the last parc_msel_gather; 0 = none).  Waits for the events. */
+int parc_msel_kernel_times(ParcPathSelect *h, float *ms5);
+/* launches of the last run, max rows, max frames, PARC_MSEL_MAX_SLICE_DIM, sample points, rows of the last run. */
+int parc_msel_describe(ParcPathSelect *h, int64_t *out6);
+
 /* Hesitation-frame removal for B clips at once: the reference's medit_lib.remove_hesitation_frames
  * (util/motion_edit_lib.py:804-878), the step of stage 2 between the optimiser and compute_hf_extra_vals.  Its own handle.  The clips use
  * the optimiser's layout (ParcMotionOptClips; the heightfield arrays are validated and otherwise unused, the constraint fields ignored).

@@ -1,6 +1,6 @@
 // parc_grid.hpp — the heightfield helpers that more than one motion tool uses (the optimiser, the analyser, the sampler and the
 // augmenter): the reference's float -> int64 conversion, its grid index and its box SDF.  What one tool alone
-// uses (sd_box_grad and patch_sdf of the optimiser, terrain_sdf and the linspace Axis of the analyser) stays with that tool.
+// uses (sd_box_grad and patch_sdf of the optimiser, terrain_sdf and the linspace Axis of the analyser, which the rollout selection takes from the analyser's header) stays with that tool.
 #pragma once
 #include <hip/hip_runtime.h>
 

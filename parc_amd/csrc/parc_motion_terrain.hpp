@@ -106,7 +106,15 @@ __device__ __forceinline__ float centre(const Axis &a, long long i) {
 // |y| + |min x| + |min y| + r max(dx, dy)), is about 80 fp32 ulps of the largest coordinate involved: it covers the rounding of the
 // linspace centres (<= 2 ulps of |min| + i dx, i <= the point's cell + r), of the bound itself and of the cell SDFs.
 // Cells outside the grid do not exist (rings are clipped).
-__device__ __forceinline__ void terrain_sdf(V3 x, const float *hf, long long X, long long Y, float mnx, float mny, float dx, float dy,
+// The heights come through `H`: hf.row(i)[j] is the height of cell (i, j).  HfContig is the clip's own [X][Y] array; the path selection
+// (parc_mpath_select.hpp) reads a slice of a terrain through two index tables.
+struct HfContig {
+    const float *hf;
+    long long Y;
+    __device__ __forceinline__ const float *row(long long i) const { return hf + i * Y; }
+};
+template <typename H>
+__device__ __forceinline__ void terrain_sdf(V3 x, const H &hf, long long X, long long Y, float mnx, float mny, float dx, float dy,
                                             float base_z, int brute, float &out_g, float &out_a) {
     const float hx = dx / 2.f, hy = dy / 2.f, top_z = -base_z;
     const Axis ax = make_axis(mnx, dx, X), ay = make_axis(mny, dy, Y);
@@ -114,7 +122,7 @@ __device__ __forceinline__ void terrain_sdf(V3 x, const float *hf, long long X, 
     if (brute) {
         for (long long i = 0; i < X; ++i) {
             const float cx = centre(ax, i);
-            const float *row = hf + i * Y;
+            const auto row = hf.row(i);
             for (long long j = 0; j < Y; ++j) {
                 const float cy = centre(ay, j), h = row[j];
                 bg = fminf(bg, ground_sd(x, cx, cy, hx, hy, h, base_z));
@@ -146,7 +154,7 @@ __device__ __forceinline__ void terrain_sdf(V3 x, const float *hf, long long X, 
             const long long jb = edge_row ? (cj + r < Y - 1 ? cj + r : Y - 1) : cj + r;
             const long long step = edge_row ? 1 : 2 * r;
             const float cx = centre(ax, i);
-            const float *row = hf + i * Y;
+            const auto row = hf.row(i);
             for (long long j = ja; j <= jb; j += step) {
                 if (j < 0 || j >= Y) continue;
                 const float cy = centre(ay, j), h = row[j];
@@ -156,6 +164,10 @@ __device__ __forceinline__ void terrain_sdf(V3 x, const float *hf, long long X, 
         }
     }
     out_g = bg; out_a = ba;
+}
+__device__ __forceinline__ void terrain_sdf(V3 x, const float *hf, long long X, long long Y, float mnx, float mny, float dx, float dy,
+                                            float base_z, int brute, float &out_g, float &out_a) {
+    terrain_sdf(x, HfContig{hf, Y}, X, Y, mnx, mny, dx, dy, base_z, brute, out_g, out_a);
 }
 
 // compute_motion_loss: base_z = torch.min(hf).item() - 10.0 (a Python float), used by fp32 tensor ops

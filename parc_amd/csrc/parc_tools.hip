@@ -1,7 +1,8 @@
 // parc_tools.hip -- the stage-2 motion tools and the learner's kernels of include/parc_env.h as one translation unit, apart from the env
 // (parc_env.hip) and the dynamics (parc_dynamics.hip).
 // Every header includes what it uses; the order below does not matter.  The first four are what the tools share; no tool header
-// includes another tool's, but for the path rollout, which runs the generator.
+// includes another tool's, but for the path rollout, which runs the generator, and the rollout selection, which reads the path handle's
+// scene and scores with the analyser's SDF search.
 #include "parc_char.hpp"             // the character as the motion tools see it: CharTree / CharPoints, fk_frame, the vector helpers
 #include "parc_grid.hpp"             // heightfield helpers of more than one tool: to_i64, grid_index, sd_box
 #include "parc_clip_batch.hpp"       // the clip batch: the device views ClipArrays / FrameClips, validation and upload
@@ -15,5 +16,6 @@
 #include "parc_motion_aug.hpp"       // parc_maug_*: stage 0's motion-terrain augmenter and the mirrored copies, batched
 #include "parc_mdm.hpp"              // parc_mdm_*: the motion generator's inference, the MDM denoiser and its DDIM / DDPM loops
 #include "parc_mdm_path.hpp"         // parc_mpath_*: path-following generation, the generator's world-frame wrapper and the rollout along a path
-#include "parc_mdm_loss.hpp"         // parc_mloss_*: the motion generator's training loss, the thirteen terms and their gradient in one launch
+#include "parc_mpath_select.hpp"     // parc_msel_*: the rollout's selection, rows scored on their own terrain slices, filtered and ranked (uses the analyser's SDF)
+#include "parc_mdm_loss.hpp"        // parc_mloss_*: the motion generator's training loss, the thirteen terms and their gradient in one launch
 #include "parc_learner.hpp"          // parc_td_lambda_return, parc_normalize_record, parc_gather_rows: the learner's kernels

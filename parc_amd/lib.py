@@ -315,6 +315,26 @@ class ParcMdmPathRolloutArgs(C.Structure):
                 ("final_frame", C.c_void_p), ("done", C.c_void_p)]
 
 
+MSEL_MAX_SLICE_DIM, MSEL_RUN_LAUNCHES = 1024, 4   # PARC_MSEL_*
+MSEL_STATUS = {1: "a root position is not finite", 2: "a side of the slice exceeds PARC_MSEL_MAX_SLICE_DIM", 4: "the motion has no frame"}
+
+
+class ParcPathSelectParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mpath", C.c_void_p), ("num_points", C.c_int32), ("points_host", f32p), ("point_body_host", i32p),
+                ("contact_body_id", C.c_int32 * MAX_BODIES), ("w_contact", C.c_float), ("w_pen", C.c_float), ("not_finished_penalty", C.c_float),
+                ("slice_padding", C.c_float), ("sdf_mode", C.c_int32)]
+
+
+class ParcPathSelectArgs(C.Structure):
+    _fields_ = [("frames", C.c_void_p), ("num_frames", C.c_int32), ("frame_stride", C.c_int32), ("final_frame", C.c_void_p), ("noise", C.c_void_p),
+                ("slice_terrain", C.c_int32), ("max_contact_loss", C.c_float), ("max_pen_loss", C.c_float), ("max_total_loss", C.c_float)]
+
+
+class ParcPathSelectResults(C.Structure):
+    _fields_ = [("contact_loss", f32p), ("pen_loss", f32p), ("total_loss", f32p), ("valid", i32p), ("status", i32p), ("num_frames", i32p),
+                ("slice_min_point", f32p), ("slice_dims", i32p), ("order", i32p), ("num_valid", i32p)]
+
+
 class ParcEnvBuffers(C.Structure):
     _fields_ = [(n, {"f": f32p, "i": i32p, "l": i64p}[t]) for n, t in BUFFER_FIELDS]
 
@@ -466,6 +486,14 @@ def _signatures():
         "parc_mpath_rollout": (rc, [vp, P(ParcMdmPathRolloutArgs), vp]),
         "parc_mpath_kernel_times": (rc, [vp, f32p]),
         "parc_mpath_describe": (rc, [vp, i64p]),
+        # rollout selection
+        "parc_msel_create": (rc, [P(ParcPathSelectParams), P(vp)]),
+        "parc_msel_destroy": (None, [vp]),
+        "parc_msel_run": (rc, [vp, P(ParcPathSelectArgs), vp]),
+        "parc_msel_results": (rc, [vp, P(ParcPathSelectResults), vp]),
+        "parc_msel_gather": (rc, [vp, i32p, i32, f32p, i64, vp]),
+        "parc_msel_kernel_times": (rc, [vp, f32p]),
+        "parc_msel_describe": (rc, [vp, i64p]),
         # hesitation-frame removal
         "parc_medit_create": (rc, [P(ParcMotionEditParams), P(vp)]),
         "parc_medit_destroy": (None, [vp]),

@@ -344,20 +344,25 @@ class PathMotionGenerator(ToolHandle):
         ff = result.final_frame.cpu().numpy().astype(np.int64)
         return np.where(ff < 0, result.num_frames + ff, np.minimum(ff, result.num_frames))
 
-    def to_clips(self, result: RolloutResult, rows: Optional[Sequence[int]] = None, names: Optional[Sequence[str]] = None):
+    def to_clips(self, result: RolloutResult, rows: Optional[Sequence[int]] = None, names: Optional[Sequence[str]] = None, terrains: Optional[Sequence] = None):
         """The rows as ``motion_opt.OptClip`` (what ``MotionOptimizer``, ``MotionTerrainAnalyzer`` and the ms-file writers of the scripts
-        take), each on its whole terrain."""
+        take), each on its whole terrain, or on ``terrains[i]`` = ``(hf, min_point)`` where given (the slices of
+        ``motion_select.PathSelector.select``)."""
         from parc_amd.motion_opt import OptClip
         self._need_scene()
         rows = list(range(self.N)) if rows is None else [int(r) for r in rows]
+        if terrains is not None and len(terrains) != len(rows):
+            raise ValueError(f"terrains: {len(terrains)} terrains for {len(rows)} rows")
         lens = self.row_lengths(result)
-        host = {k: v.detach().cpu().numpy() for k, v in result.frames().items()}
+        idx = torch.as_tensor(rows, dtype=torch.long, device=result.root_pos.device)
+        host = {k: v.detach()[idx].cpu().numpy() for k, v in result.frames().items()}   # the named rows only
         sc = self._scene
         clips = []
         for i, r in enumerate(rows):
             p, n = int(sc["row_path"][r]), int(lens[r])
-            clips.append(OptClip(host["root_pos"][r, :n].copy(), host["root_rot"][r, :n].copy(), host["joint_rot"][r, :n].copy(), host["contacts"][r, :n].copy(),
-                                 sc["hfs"][p].copy(), sc["min_points"][p].copy(), sc["dx"], int(round(self.fps)), names[i] if names else f"row_{r}"))
+            hf, mp = (sc["hfs"][p], sc["min_points"][p]) if terrains is None else terrains[i]
+            clips.append(OptClip(host["root_pos"][i, :n].copy(), host["root_rot"][i, :n].copy(), host["joint_rot"][i, :n].copy(), host["contacts"][i, :n].copy(),
+                                 np.array(hf, np.float32), np.array(mp, np.float32), sc["dx"], int(round(self.fps)), names[i] if names else f"row_{r}"))
         return clips
 
     def select(self, result: RolloutResult, top_k: Optional[int] = None, noise=None, seed: Optional[int] = None, analyzer=None) -> List[dict]:

@@ -61,9 +61,10 @@ class SubTerrain:
         return self.hf[idx[..., 0], idx[..., 1]]
 
 
-def slice_terrain_around_motion(frames_xyz, terrain: "SubTerrain", padding=1.0):
-    """terrain_util.py:1587-1642 (localize=True): the part of ``terrain`` under a recorded root trajectory plus ``padding``,
-    shifted so that the first frame is at xy = (0, 0) and stands at height hf = 0.  Returns (SubTerrain, localized xyz).
+def slice_terrain_around_motion(frames_xyz, terrain: "SubTerrain", padding=1.0, localize=True):
+    """terrain_util.py:1587-1658: the part of ``terrain`` under a recorded root trajectory plus ``padding``.  ``localize=True``: shifted
+    so that the first frame is at xy = (0, 0) and stands at height hf = 0; returns (SubTerrain, localized xyz).  ``localize=False``
+    (:1643-1658): the un-shifted SubTerrain alone.  Cells beyond the terrain repeat its edge cells (``get_grid_index`` clamps).
     Same arithmetic as the torch code: fp32 tensors, ``torch.arange`` evaluated in double and stored as fp32."""
     fr = np.asarray(frames_xyz, F32)
     mn = np.array([fr[:, 0].min(), fr[:, 1].min()], F32) - F32(padding)
@@ -81,6 +82,11 @@ def slice_terrain_around_motion(frames_xyz, terrain: "SubTerrain", padding=1.0):
     idx = terrain.get_grid_index(pts)
     hf = terrain.hf[idx[..., 0], idx[..., 1]].copy()
     hf_maxmin = terrain.hf_maxmin[idx[..., 0], idx[..., 1]].copy()
+    if not localize:
+        out = SubTerrain(hf.shape[0], hf.shape[1], terrain.dxdy[0], terrain.dxdy[1], float(g0[0]), float(g0[1]))
+        out.hf = hf
+        out.hf_maxmin = hf_maxmin
+        return out
     canon_xy = fr[0, 0:2].copy()
     local = fr.copy()
     local[:, 0:2] -= canon_xy
