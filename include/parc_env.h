@@ -1155,6 +1155,56 @@ int parc_medit_get_flags(ParcMotionEdit *h, uint64_t *raw_host, uint64_t *filter
 /* Device time (hipEvents) of the last run, ms: fk, pairs, scan, and gather (the last parc_medit_get_frames). */
 int parc_medit_kernel_times(ParcMotionEdit *h, float *ms4);
 
+/* Contact labelling, penetration lift and resampling of raw clips for B clips at once, each on its own terrain:
+ * the reference editor's compute_hf_foot_contacts_and_correct_pen, compute_motion_terrain_hand_contacts,
+ * compute_ground_plane_foot_contacts / correct_foot_ground_pen and change_motion_fps (util/motion_edit_lib.py:430-604, :752-784).  Its
+ * own handle; the clips use the optimiser's layout (ParcMotionOptClips, the constraint fields ignored; the input contacts are read only by
+ * keep_existing and by the resampling).  FK in fp32 on the clip's quaternions.
+ * Feet: the eight corners offset +- half of a foot's first box, rotated by the body and added to its position; on the terrain a corner's
+ * cell is get_grid_index (round half to even, clamped) and h its height: contact = any(z < h + contact_eps), gap = min(z - h), lift =
+ * -min(0, gap of either foot).  On the ground plane: contact = any(z - ground_height - contact_eps < 0), gap = min(z - ground_height),
+ * lift = ground_height - min(ground_height, z of every corner of every listed box).
+ * Hands: sd = min over ALL cells of the clip's terrain of sdBox(p - centre, half) - hand_radius, each cell a column from min(hf) - 10 up
+ * to its height on the centres of torch.linspace(0, (dim - 1) d, dim) + min_point; contact = sd < contact_eps.  Terrain mode only.
+ * Labels, gap, lift and hand_sd come from the pose before the lift.  Results do not depend on which other clips are in the batch. */
+#define PARC_MLABEL_MAX_FOOT_BOXES 8            /* box geoms of both feet together */
+typedef struct ParcMotionLabel ParcMotionLabel;
+typedef struct {
+    uint32_t struct_size;                    /* sizeof(ParcMotionLabelParams) */
+    int32_t device;
+    ParcCharModel model;                     /* the tables parc_env_create takes (fk_paths unused) */
+    int32_t foot_body[2];                    /* left, right: columns 0 / 1 of gap */
+    int32_t hand_body[2];                    /* left, right: columns 0 / 1 of hand_sd */
+    float hand_radius[2];                    /* the sphere of each hand's first geom, > 0 */
+    int32_t num_foot_boxes;                  /* 2 .. PARC_MLABEL_MAX_FOOT_BOXES; every foot has at least one */
+    int32_t box_foot[PARC_MLABEL_MAX_FOOT_BOXES];        /* 0 / 1: the foot of box q; the first one listed for a foot is its first geom */
+    float box_offset[PARC_MLABEL_MAX_FOOT_BOXES][3];     /* in the body's frame */
+    float box_half[PARC_MLABEL_MAX_FOOT_BOXES][3];       /* half extents, > 0 */
+    float contact_eps;                       /* metres, compared in fp32 (reference default 0.04) */
+} ParcMotionLabelParams;
+int parc_mlabel_create(const ParcMotionLabelParams *p, ParcMotionLabel **out);
+void parc_mlabel_destroy(ParcMotionLabel *h);
+/* Uploads the clips (num_clips >= 1, every clip >= 1 frame, a terrain of fewer than 2^31 cells each).  As parc_medit_set_clips:
+ * PARC_ERR_INVALID leaves the batch loaded before in place; a failure after the validation leaves no batch. */
+int parc_mlabel_set_clips(ParcMotionLabel *h, const ParcMotionOptClips *c);
+/* k_mlabel_feet, then k_mlabel_hands when hands != 0 and use_ground == 0.  correct_pen: the output root height is z + lift.  use_ground:
+ * the plane at ground_height instead of the terrains (the hand columns are then not labelled).  keep_existing: the columns that are not
+ * labelled hold the clip's own contacts instead of 0. */
+int parc_mlabel_run(ParcMotionLabel *h, int32_t hands, int32_t correct_pen, int32_t use_ground, float ground_height, int32_t keep_existing);
+/* The last run's root_pos [F][3] and contacts [F][num_bodies], frames in batch order. */
+int parc_mlabel_get_frames(ParcMotionLabel *h, float *root_pos_host, float *contacts_host);
+/* TEST entries of the last run: gap [F][2]; lift [F]; hand_sd [F][2] (+inf where the hands were not labelled). */
+int parc_mlabel_get_gap(ParcMotionLabel *h, float *gap_host);
+int parc_mlabel_get_lift(ParcMotionLabel *h, float *lift_host);
+int parc_mlabel_get_hand_sd(ParcMotionLabel *h, float *hand_sd_host);
+/* MotionLib.calc_motion_frame (LoopMode.CLAMP, anim/motion_lib.py:94-126) of the loaded clips at the caller's times: clip c's output
+ * frames are out_off[c] .. out_off[c + 1] (at least one each), times_host [N] seconds, lengths_host [C] the fp32 (frames - 1) / fps > 0.
+ * Root position and contacts are lerped, the rotations normalised (quat_normalize) and slerped.  Outputs [N] rows, as parc_medit_get_frames. */
+int parc_mlabel_resample(ParcMotionLabel *h, const int64_t *out_off_host, const float *times_host, const float *lengths_host,
+                         float *root_pos_host, float *root_rot_host, float *joint_rot_host, float *contacts_host);
+/* Device time (hipEvents) of the last run and the last resample, ms: feet, hands (0 = not run), resample. */
+int parc_mlabel_kernel_times(ParcMotionLabel *h, float *ms3);
+
 #ifdef __cplusplus
 }
 #endif

@@ -108,6 +108,16 @@ class ParcMotionEditParams(C.Structure):
                 ("hesitation_min_seq_len", C.c_int32)]
 
 
+MLABEL_MAX_FOOT_BOXES = 8   # PARC_MLABEL_*
+
+
+class ParcMotionLabelParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("model", ParcCharModel), ("foot_body", C.c_int32 * 2),
+                ("hand_body", C.c_int32 * 2), ("hand_radius", C.c_float * 2), ("num_foot_boxes", C.c_int32),
+                ("box_foot", C.c_int32 * MLABEL_MAX_FOOT_BOXES), ("box_offset", (C.c_float * 3) * MLABEL_MAX_FOOT_BOXES),
+                ("box_half", (C.c_float * 3) * MLABEL_MAX_FOOT_BOXES), ("contact_eps", C.c_float)]
+
+
 class ParcMotionOptClips(C.Structure):
     _fields_ = [("num_clips", C.c_int32), ("frame_off_host", i64p), ("hf_off_host", i64p), ("cons_off_host", i64p),
                 ("hf_dims_host", i32p), ("hf_geom_host", f32p), ("hf_host", f32p), ("root_pos_host", f32p), ("root_rot_host", f32p),
@@ -503,6 +513,17 @@ def _signatures():
         "parc_medit_get_pair_rows": (rc, [vp, i32, u64p]),
         "parc_medit_get_flags": (rc, [vp, u64p, u64p]),
         "parc_medit_kernel_times": (rc, [vp, f32p]),
+        # contact labelling
+        "parc_mlabel_create": (rc, [P(ParcMotionLabelParams), P(vp)]),
+        "parc_mlabel_destroy": (None, [vp]),
+        "parc_mlabel_set_clips": (rc, [vp, P(ParcMotionOptClips)]),
+        "parc_mlabel_run": (rc, [vp, i32, i32, i32, f32, i32]),
+        "parc_mlabel_get_frames": (rc, [vp, f32p, f32p]),
+        "parc_mlabel_get_gap": (rc, [vp, f32p]),
+        "parc_mlabel_get_lift": (rc, [vp, f32p]),
+        "parc_mlabel_get_hand_sd": (rc, [vp, f32p]),
+        "parc_mlabel_resample": (rc, [vp, i64p, f32p, f32p, f32p, f32p, f32p, f32p]),
+        "parc_mlabel_kernel_times": (rc, [vp, f32p]),
     }
 
 
